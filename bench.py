@@ -6,16 +6,21 @@ complex128, one GPU.  A "step" is one pass of the hot path over one batch: the
 full 465-gate stream of qc.qft on 30 qubits (src/lib/circuit.py:320-328), every
 gate submitted through the C-ABI (qh_apply1 / qh_applyc), state resident in HBM.
 
-  python bench.py --gpus N --steps K --warmup W
-  N = 1: BASELINE config 2, the 30-qubit QFT (the headline and the roofline kernel); the line also
-         carries `ladder_base` = the 33-qubit QFT on the same GPU, the N=1 point of config 5's ladder,
-         `configs` = the other single-GPU BASELINE configurations timed the same way (config 3 supremacy-30,
-         config 4 Grover-34, and the QFT at the reference's default width complex64), each with its own
-         roofline, and `single_shot_ms` = ONE qft on a cold queue, planning included, followed by a read.
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+  N = 1: BASELINE config 2, the 30-qubit QFT (the headline and the roofline kernel).  A plain run sets up, runs W warm-up
+         and K timed steps, and prints the line: the headline, `ms_per_step` (one timed step) and the roofline of the
+         timed steps.  --full adds everything that takes runs of its own: `cached_plan` (the steps again with the plan
+         cache on), the roofline's live PMC traffic and energy, `ladder_base` = the 33-qubit QFT on the same GPU, the N=1
+         point of config 5's ladder, `configs` = the other single-GPU BASELINE configurations timed the same way (config 3
+         supremacy-30, config 4 Grover-34, and the QFT at the reference's default width complex64), each with its own
+         roofline, `single_shot_ms` = ONE qft on a cold queue, planning included, followed by a read, the per-gate kernel
+         classes (--fusion 0) and `cpu_baseline`.  The --no-* switches drop single parts of a --full run.
   N > 1: launched by torch.distributed.run, one rank per GPU; BASELINE config 5's ladder --
          34 / 35 / 36 qubits on 2 / 4 / 8 GPUs, the state sharded by its top log2(N) index bits,
          2^33 amplitudes = 128 GiB per GPU (weak scaling).  --qubits overrides.
   `value` is in units of 2^30-amplitude gate applications in every case, so the lines compare.
+  --dump-outputs DIR (one process, one GPU): after the timed steps, the state they left (see dump_outputs) goes to
+  DIR/*.npy; the input is the same basis state in every run, so two builds compare output for output.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
 """
@@ -52,6 +57,11 @@ def parse():
                   help='default: 30 on one GPU (BASELINE config 2); 33 + log2(gpus) on several (config 5 ladder)')
   ap.add_argument('--no-ladder-base', action='store_true', help='N=1: skip the extra 33-qubit measurement')
   ap.add_argument('--no-configs', action='store_true', help='N=1: skip configs 3, 4, complex64 and the single-shot timing')
+  ap.add_argument('--full', action='store_true',
+                  help='also measure what takes runs of its own: cached plan, live traffic, energy, single shot, ladder base, '
+                       'other configs, per-gate kernel classes, CPU baseline (each --no-* switch drops its part)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write the state left by the last timed step to DIR/*.npy (float64; sampled above 2^20 amplitudes)')
   ap.add_argument('--fusion', type=int, default=-1, help='0 per-gate kernels, 1 fused sweeps (default)')
   ap.add_argument('--no-cpu-baseline', action='store_true')
   ap.add_argument('--no-cached-plan', action='store_true', help='skip the extra steps timed with the plan cache on')
@@ -528,6 +538,35 @@ def single_shot(device_index):
   return out
 
 
+DUMP_MAX_AMPS = 1 << 20     # amplitudes written in all: 16 MiB of (re, im) + 8 MiB of indices
+DUMP_BLOCK = 1 << 12        # consecutive amplitudes per sampled block
+DUMP_SEED = 20261015
+
+
+def dump_outputs(eng, out_dir, n, norm2):
+  """--dump-outputs: what the timed path hands its caller after the last step -- the state vector, in logical order
+  (qh_download canonicalises the layout first) -- as float64 .npy files.  Up to 2^20 amplitudes the whole state; above,
+  2^8 blocks of 2^12 consecutive amplitudes at block offsets drawn from a fixed seed, the same indices in every run.
+    state.npy        [M, 2]  (re, im) of the amplitudes
+    state_index.npy  [M]     their logical indices (exact in float64: < 2^53)
+    norm2.npy        [1]     sum of |amplitude|^2 over the whole state"""
+  total = 1 << n
+  if total <= DUMP_MAX_AMPS:
+    block, starts = total, np.zeros(1, dtype=np.int64)
+  else:
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = rng.choice(total // DUMP_BLOCK, size=DUMP_MAX_AMPS // DUMP_BLOCK, replace=False)
+    block, starts = DUMP_BLOCK, np.sort(pick).astype(np.int64) * DUMP_BLOCK
+  amps = np.empty(len(starts) * block, dtype=np.complex128)
+  for j, s in enumerate(starts):
+    eng.download(int(s), block, out=amps[j * block:(j + 1) * block])
+  index = (starts[:, None] + np.arange(block, dtype=np.int64)[None, :]).reshape(-1)
+  os.makedirs(out_dir, exist_ok=True)
+  np.save(os.path.join(out_dir, 'state.npy'), amps.view(np.float64).reshape(-1, 2))
+  np.save(os.path.join(out_dir, 'state_index.npy'), index.astype(np.float64))
+  np.save(os.path.join(out_dir, 'norm2.npy'), np.array([norm2], dtype=np.float64))
+
+
 def main():
   args = parse()
   # every step plans its gate stream from scratch (the engine's plan cache would only save host
@@ -539,6 +578,8 @@ def main():
   if world != args.gpus:
     if world == 1 and args.gpus > 1:
       raise SystemExit('bench.py --gpus N>1 must be launched with torch.distributed.run (one rank per GPU)')
+  if args.dump_outputs and (world > 1 or args.sharded):
+    raise SystemExit('bench.py --dump-outputs: one process on one GPU only (no --sharded, no torch.distributed.run)')
   if world > 1 or args.sharded:
     os.environ['QCC_PRELOAD_TORCH'] = '1'  # one HIP runtime per process: torch's (qcc_amd/native.py)
   from qcc_amd import device, native, workloads
@@ -608,6 +649,8 @@ def main():
   # parity guard inside the bench: the norm (cheap, device-side) and -- with several ranks -- sampled amplitudes of one
   # more QFT against the closed form (a single-GPU run is covered by the GPU tests, which check every amplitude)
   norm2 = eng.norm2_global() if dist is not None else eng.norm2()
+  if args.dump_outputs:
+    dump_outputs(eng, args.dump_outputs, n, norm2)      # before anything below runs more gates on this state
   parity = None
   if dist is not None:
     try:
@@ -619,7 +662,7 @@ def main():
                 RuntimeError(f'max |amplitude - closed form| over {world} ranks x 64 samples = {parity:.3e} > 1e-10 '
                              f'(norm2 {norm2:.15f}): amplitudes are misplaced or wrong'), eng)
   cached = None
-  if (world == 1 and dist is None and fusion != native.QH_FUSE_OFF and os.environ.get('QH_PLAN_CACHE') == '0'
+  if (args.full and world == 1 and dist is None and fusion != native.QH_FUSE_OFF and os.environ.get('QH_PLAN_CACHE') == '0'
       and not args.no_cached_plan):
     # the same steps with the engine's plan cache on (loops over one circuit skip the planner): reported
     # beside the headline, which plans every step from scratch
@@ -637,12 +680,18 @@ def main():
     launches = max(1, stats['kernels_launched'])
     # ---- roofline of the dominant kernel --------------------------------------
     if world == 1 and dist is None:
-      if fusion == native.QH_FUSE_OFF:
+      if fusion == native.QH_FUSE_OFF and args.full:
         classes = unfused_classes(eng, ops, g8, n)
         name = max(classes, key=lambda k: classes[k][0] * classes[k][1])
         ms_l, n_l, bytes_l = classes[name][:3]
         other = {k: {'avg_ms': v[0], 'launches_per_step': v[1], 'GBps_algorithmic': v[2] / v[0] / 1e6,
                      'GBps_moved': v[3] / v[0] / 1e6} for k, v in classes.items()}
+      elif fusion == native.QH_FUSE_OFF:
+        # (each class replayed alone between HIP events takes runs of its own: --full)
+        name = 'k_diag / k_pair (per-gate kernels, mean launch over the timed steps)'
+        ms_l = ev_ms / launches
+        bytes_l = stats['bytes_swept'] / launches
+        other = {}
       else:
         name = 'k_sweep (fused register-tile sweep, read S + write S per launch)'
         ms_l = ev_ms / launches
@@ -707,7 +756,7 @@ def main():
   else:
     eng.close()
   if rank == 0:
-    extras = world == 1 and dist is None and n == 30 and fusion != native.QH_FUSE_OFF
+    extras = args.full and world == 1 and dist is None and n == 30 and fusion != native.QH_FUSE_OFF
     if extras and not args.no_live_traffic:
       # roofline.traffic measured in THIS run (VERDICT r05 "what's weak" 8): the engine is closed, a child process runs the
       # same 30-qubit QFT under rocprofv3's PMC passes; the committed profile's figure stays beside it as traffic_from_profile
@@ -727,7 +776,7 @@ def main():
       out['ladder_base'] = ladder_base(local_rank, fusion)
     if extras and not args.no_configs:
       out['configs'] = other_configs(local_rank)
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
       out['cpu_baseline'] = cpu_baseline(args, ops, g8)
       out['cpu_baseline']['gpu_over_this_baseline'] = out['whole_state_gate_applies_per_s'] / out['cpu_baseline']['value']
     print(json.dumps(out))

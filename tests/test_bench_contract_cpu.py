@@ -26,6 +26,50 @@ def test_gpus_to_workload_ladder():
     b.default_qubits(3)
 
 
+def test_plain_run_is_the_default(monkeypatch):
+  """`bench.py --gpus 1 --steps K --warmup W` is the lean run: --full (everything that takes runs of its own) and
+  --dump-outputs are off unless asked for."""
+  b = _bench()
+  monkeypatch.setattr('sys.argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+  a = b.parse()
+  assert a.gpus == 1 and a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+  monkeypatch.setattr('sys.argv', ['bench.py', '--full', '--dump-outputs', 'out'])
+  a = b.parse()
+  assert a.full is True and a.dump_outputs == 'out'
+  assert b.DUMP_MAX_AMPS * (16 + 8) <= 64 << 20          # what --dump-outputs writes stays under 64 MB
+
+
+def test_dump_outputs_layout(tmp_path):
+  """dump_outputs on a stand-in engine: the whole state up to 2^20 amplitudes; above, 2^20 distinct amplitudes at seeded block
+  offsets, the same in every call, each value next to its own logical index; float64 only, under 64 MB in all."""
+  import numpy as np
+  b = _bench()
+
+  class Eng:
+    def __init__(self, psi):
+      self.psi = psi
+
+    def download(self, offset, count, out):
+      out[:count] = self.psi[offset:offset + count]
+      return out
+
+  rng = np.random.default_rng(7)
+  for n in (10, 22):
+    psi = rng.standard_normal(1 << n) + 1j * rng.standard_normal(1 << n)
+    outs = []
+    for rep in range(2):
+      d = tmp_path / f'{n}_{rep}'
+      b.dump_outputs(Eng(psi), str(d), n, 0.5)
+      outs.append({k: np.load(d / f'{k}.npy') for k in ('state', 'state_index', 'norm2')})
+      assert sum(os.path.getsize(d / f) for f in os.listdir(d)) < 64 << 20
+    o = outs[0]
+    assert all(v.dtype == np.float64 for v in o.values()) and o['norm2'].tolist() == [0.5]
+    idx = o['state_index'].astype(np.int64)
+    assert len(idx) == min(1 << n, 1 << 20) and len(np.unique(idx)) == len(idx)
+    assert np.array_equal(o['state'][:, 0] + 1j * o['state'][:, 1], psi[idx])
+    assert np.array_equal(idx, outs[1]['state_index'].astype(np.int64))
+
+
 def test_qft_gate_counts_of_the_ladder():
   from qcc_amd import workloads
   for n, gates in ((30, 465), (33, 561), (36, 666)):

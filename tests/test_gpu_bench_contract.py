@@ -23,7 +23,7 @@ def _run(*args, env=None):
 
 
 def test_bench_line_small():
-  d = _run('--qubits', '24', '--steps', '3', '--warmup', '2', '--cpu-qubits', '24', '--cpu-gates', '6')
+  d = _run('--full', '--qubits', '24', '--steps', '3', '--warmup', '2', '--cpu-qubits', '24', '--cpu-gates', '6')
   for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
             'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline'):
     assert k in d, k
@@ -44,11 +44,53 @@ def test_bench_line_small():
   assert 'traffic_from_profile' in r and set(r['traffic_from_profile']) == {'bytes', 'source'}
 
 
+def test_bench_plain_line_is_lean():
+  """A plain run (no --full) sets up, warms up, times exactly --steps steps and prints the line: the headline keys, the roofline
+  of the timed steps, and none of the parts that take runs of their own."""
+  d = _run('--qubits', '24', '--steps', '4', '--warmup', '1')
+  for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'steps', 'warmup', 'roofline', 'norm2'):
+    assert k in d, k
+  assert d['steps'] == 4 and d['warmup'] == 1 and d['dtype'] == 'f64' and d['higher_is_better'] is True and d['ms_per_step'] > 0
+  assert len(d['step_ms_min_max']) == 2 and abs(d['norm2'] - 1) < 1e-10
+  assert abs(d['value'] - 300 * 4 * 2 ** (24 - 30) / (d['ms_per_step'] * 4e-3)) / d['value'] < 1e-6
+  for k in ('cpu_baseline', 'cached_plan', 'configs', 'ladder_base', 'single_shot_ms'):
+    assert k not in d, k
+  assert 'energy' not in d['roofline'] and d['roofline']['bytes_per_launch'] == 2 * 16 * 2 ** 24
+
+
+def test_bench_dump_outputs(tmp_path):
+  """--dump-outputs: the state the timed steps left (W + K QFTs of the bench's basis state), sampled above 2^20 amplitudes at the
+  same indices in every run, equals the CPU oracle's; a second run writes the same files."""
+  import numpy as np
+  from qcc_amd import workloads
+  from tests import oracle_lib
+  n, warmup, steps = 21, 1, 2
+  dirs = [tmp_path / 'a', tmp_path / 'b']
+  for d in dirs:
+    line = _run('--qubits', str(n), '--steps', str(steps), '--warmup', str(warmup), '--dump-outputs', str(d))
+    assert line['steps'] == steps
+  a = {k: np.load(dirs[0] / f'{k}.npy') for k in ('state', 'state_index', 'norm2')}
+  b = {k: np.load(dirs[1] / f'{k}.npy') for k in ('state', 'state_index', 'norm2')}
+  assert a['state'].dtype == np.float64 and a['state'].shape == (1 << 20, 2) and a['state_index'].shape == (1 << 20,)
+  assert np.array_equal(a['state_index'], b['state_index']) and np.allclose(a['state'], b['state'], rtol=0, atol=1e-12)
+  idx = a['state_index'].astype(np.int64)
+  assert len(np.unique(idx)) == len(idx) and idx.min() >= 0 and idx.max() < 1 << n
+  ops, g8 = workloads.qft_stream(range(n)).arrays()
+  want = np.zeros(1 << n, dtype=np.complex128)
+  want[0x12CB9A5E3 & ((1 << n) - 1)] = 1
+  orc = oracle_lib.load()
+  for _ in range(warmup + steps):
+    orc.run_stream(want, n, ops, g8)
+  got = a['state'][:, 0] + 1j * a['state'][:, 1]
+  assert float(np.max(np.abs(got - want[idx]))) < 1e-10
+  assert abs(a['norm2'][0] - 1) < 1e-10
+
+
 def test_bench_headline_extras_at_full_size():
-  """The parts of the default line that only exist at the headline's size (30 qubits): `roofline.traffic` measured in the run
+  """The parts of the --full line that only exist at the headline's size (30 qubits): `roofline.traffic` measured in the run
   (rocprofv3 PMC passes in a child process -- or the committed profile's figure with the reason, where rocprofv3 cannot run) and
   `roofline.energy` (Joules per k_sweep launch: stream-only floor vs the QFT).  Neither may cost the line."""
-  d = _run('--steps', '3', '--warmup', '1', '--no-configs', '--no-ladder-base', '--no-cpu-baseline', '--no-cached-plan')
+  d = _run('--full', '--steps', '3', '--warmup', '1', '--no-configs', '--no-ladder-base', '--no-cpu-baseline', '--no-cached-plan')
   r = d['roofline']
   assert d['config']['qubits'] == 30 and r['bytes_per_launch'] == 2 * 16 * 2 ** 30 and 0.5 < r['frac'] < 1.0
   assert r['traffic'] is not None and abs(r['traffic'] / r['bytes_per_launch'] - 1) < 0.01          # no wasted HBM traffic

@@ -285,11 +285,12 @@ def test_qft22_sampled(oracle, golden_dir):
   assert abs(np.vdot(psi, psi).real - float(g['norm2'])) < 1e-12
 
 
-def test_against_live_reference_build(oracle):
-  """When oracle/_ref/libxgates.so is present, compare live on random inputs."""
-  xg = oracle_lib.load_ref_xgates()
-  if xg is None:
-    pytest.skip('oracle/_ref/libxgates.so not built')
+G11 = 'g11_xgates_random.npz'
+
+
+def _random_cases():
+  """Random unit states and random (non-unitary) gates, seed 3: (nbits, psi0, gate, target, control or NO_CTL) -- one apply1
+  and, above one qubit, one applyc per draw."""
   rng = np.random.default_rng(3)
   for n in (1, 2, 3, 11):
     psi0 = rng.standard_normal(1 << n) + 1j * rng.standard_normal(1 << n)
@@ -297,16 +298,40 @@ def test_against_live_reference_build(oracle):
     for _ in range(12):
       gate = rng.standard_normal(4) + 1j * rng.standard_normal(4)
       t = int(rng.integers(n))
-      a, b = psi0.copy(), psi0.copy()
-      xg.apply1(a, gate, n, t, 128)
-      oracle.apply1(b, gate, n, t)
-      assert np.max(np.abs(a - b)) <= 4e-15
+      yield n, psi0, gate, t, NO_CTL
       if n > 1:
-        c = int((t + 1 + rng.integers(n - 1)) % n)
-        a, b = psi0.copy(), psi0.copy()
-        xg.applyc(a, gate, n, c, t, 128)
-        oracle.applyc(b, gate, n, c, t)
-        assert np.max(np.abs(a - b)) <= 4e-15
+        yield n, psi0, gate, t, int((t + 1 + rng.integers(n - 1)) % n)
+
+
+def _apply(lib, psi0, gate, n, t, c, width=None):
+  psi = psi0.copy()
+  extra = () if width is None else (width,)
+  if c == NO_CTL:
+    lib.apply1(psi, gate, n, t, *extra)
+  else:
+    lib.applyc(psi, gate, n, c, t, *extra)
+  return psi
+
+
+def _stored_cases(g):
+  """The cases of g11 as stored: inputs and what the reference's own xgates.cc build computed for them."""
+  for k in range(len(g['n'])):
+    n = int(g['n'][k])
+    lo, hi = int(g['off'][k]), int(g['off'][k + 1])
+    yield n, g[f'psi0_n{n}'], g['gate'][k], int(g['t'][k]), int(g['c'][k]), g['out'][lo:hi]
+
+
+def test_against_live_reference_build(oracle, golden_dir):
+  """Random inputs through our oracle against the reference's own xgates.cc build: what that build computed for them is
+  stored (g11, written by this module's __main__); where oracle/_ref/libxgates.so is present it is also run live."""
+  xg = oracle_lib.load_ref_xgates()
+  cases = list(_stored_cases(_load(golden_dir, G11)))
+  assert len(cases) == 12 * 7 and {c[0] for c in cases} == {1, 2, 3, 11}
+  for n, psi0, gate, t, c, want in cases:
+    b = _apply(oracle, psi0, gate, n, t, c)
+    assert np.max(np.abs(want - b)) <= 4e-15
+    if xg is not None:
+      assert np.max(np.abs(_apply(xg, psi0, gate, n, t, c, 128) - b)) <= 4e-15
 
 
 def test_bad_qubits_are_errors_not_ub(oracle):
@@ -317,3 +342,16 @@ def test_bad_qubits_are_errors_not_ub(oracle):
     oracle.apply1(psi, np.eye(2).reshape(4), 3, -1)
   with pytest.raises(ValueError):
     oracle.applyc(psi, np.eye(2).reshape(4), 3, 3, 0)  # positive out-of-range ctl
+
+
+if __name__ == '__main__':
+  # python -m tests.test_oracle_golden: writes tests/golden/g11 from the reference's own build (oracle/_ref, `make -C oracle ref`)
+  ref = oracle_lib.load_ref_xgates()
+  assert ref is not None, 'oracle/_ref/libxgates.so is missing'
+  rows = list(_random_cases())
+  outs = [_apply(ref, psi0, gate, n, t, c, 128) for n, psi0, gate, t, c in rows]
+  np.savez(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', G11),
+           n=np.array([r[0] for r in rows], dtype=np.int32), t=np.array([r[3] for r in rows], dtype=np.int32),
+           c=np.array([r[4] for r in rows], dtype=np.int32), gate=np.array([r[2] for r in rows]),
+           off=np.cumsum([0] + [1 << r[0] for r in rows]).astype(np.int64),
+           out=np.concatenate(outs), **{f'psi0_n{r[0]}': r[1] for r in rows})

@@ -8,10 +8,10 @@ O=$R/gpurun_out/r${ROUND:-06}p
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 B="python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-ladder-base --no-cached-plan --no-configs --no-live-traffic --no-energy"
-U="python $R/bench.py --fusion 0 --steps 3 --warmup 1 --no-cpu-baseline"
-timeout 1200 python $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
-timeout 600 python $R/bench.py --steps 20 --warmup 5 --no-configs --no-live-traffic --no-energy > $O/bench_driver_style.json 2> $O/bench_driver_style.err
-timeout 300 python $R/bench.py --fusion 0 --steps 2 --no-cpu-baseline > $O/bench_unfused.json 2> $O/bench_unfused.err
+U="python $R/bench.py --full --fusion 0 --steps 3 --warmup 1 --no-cpu-baseline"
+timeout 1200 python $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+timeout 600 python $R/bench.py --full --steps 20 --warmup 5 --no-configs --no-live-traffic --no-energy > $O/bench_driver_style.json 2> $O/bench_driver_style.err
+timeout 300 python $R/bench.py --full --fusion 0 --steps 2 --no-cpu-baseline > $O/bench_unfused.json 2> $O/bench_unfused.err
 trace() {  # trace <tag> <skip sweeps> <command...>: kernel trace -> steady-state stats
   local tag=$1 skip=$2; shift 2
   rm -rf /tmp/st_$tag
@@ -93,8 +93,8 @@ f=$(find /tmp/st_unf -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp $f 
 pmc pmc_fetch_fused FETCH_SIZE $B
 pmc pmc_write_fused WRITE_SIZE $B
 python3 $R/tools/collect_traffic.py $O/pmc_fetch_fused.csv $O/pmc_write_fused.csv $O/traffic_fused.json > /dev/null
-pmc pmc_fetch_unfused FETCH_SIZE python $R/bench.py --fusion 0 --steps 1 --warmup 0 --no-cpu-baseline
-pmc pmc_write_unfused WRITE_SIZE python $R/bench.py --fusion 0 --steps 1 --warmup 0 --no-cpu-baseline
+pmc pmc_fetch_unfused FETCH_SIZE python $R/bench.py --full --fusion 0 --steps 1 --warmup 0 --no-cpu-baseline
+pmc pmc_write_unfused WRITE_SIZE python $R/bench.py --full --fusion 0 --steps 1 --warmup 0 --no-cpu-baseline
 python3 $R/tools/collect_traffic.py $O/pmc_fetch_unfused.csv $O/pmc_write_unfused.csv $O/traffic_unfused.json > /dev/null
 for w in sup30 qft30c64 grover34; do
   pmc pmc_fetch_$w FETCH_SIZE python $R/tools/run_workload.py $w 1
