@@ -106,10 +106,7 @@ unsigned pick_grid(uint64_t nwork, int per_block) {
   return (unsigned)blocks;
 }
 
-int env_int(const char *name, int dflt) {
-  const char *s = getenv(name);
-  return s ? atoi(s) : dflt;
-}
+using qh::env_int;
 // Launch shape of the per-gate kernels (tools/membench on MI355X): small blocks
 // of work, one chunk per block (no grid-stride), non-temporal access.
 
@@ -368,6 +365,10 @@ bool relayout_wanted(const qh_state_s *h) {
   if (h->relayout >= 0) return h->relayout == 1;
   return relayout_eligible(h) && !(h->comm && h->comm->nranks > 1);
 }
+// What the planner works from for this handle, the switches read now (planner.h PlanSwitches)
+qh::PlanRequest plan_request(const qh_state_s *h, bool relayout) {
+  return qh::PlanRequest{h->nloc, h->bw, h->shard, relayout, h->nglob > h->nloc, qh::PlanSwitches::from_env()};
+}
 // A state buffer.  Buffers of 4..32 GiB (QH_ALLOC_CONTIG=1: every buffer >= 64 MiB, =0: none) are asked for as
 // PHYSICALLY contiguous VRAM first (hipDeviceMallocContiguous); if the driver has no contiguous range left it is plain
 // hipMalloc.  Measured, not derived (DESIGN 7 "placement", profiles/r03/alloc_contiguous_*): where the driver puts a
@@ -480,9 +481,8 @@ int flush_impl(qh_state_s *h, qh::SlabIO *split = nullptr, qh::TileMaxOut *tmax 
     const bool relay = relayout_ready(h);
     void *result = h->d_psi;
     uint8_t final_pos[64];
-    rc = qh::run_fused(h->queue, h->nloc, h->shard, h->bw, h->d_psi, h->stream, h->dry,
-                       &h->sweep, &h->stats, &g_err, h->comm ? io : nullptr, h->d_alt, relay, &result, final_pos,
-                       h->nglob > h->nloc, tmax);
+    rc = qh::run_fused(h->queue, plan_request(h, relay), h->d_psi, h->stream, h->dry, &h->sweep, &h->stats, &g_err,
+                       h->comm ? io : nullptr, h->d_alt, &result, final_pos, tmax);
     if (rc == QH_OK && relay) {
       if (result != h->d_psi) std::swap(h->d_psi, h->d_alt);
       for (int b = 0; b < h->nglob; ++b)
@@ -1475,8 +1475,8 @@ int qh_timer_laps(qh_handle h, float *ms, int cap, int *count) {
 
 int qh_plan_json(qh_handle h, char *buf, uint64_t cap, uint64_t *needed) {
   if (!h) return fail(QH_ERR_ARG, "null");
-  std::string s = qh::plan_to_json(h->queue, h->nloc, h->shard, h->bw, qh::sweep_max_rb(),
-                                   qh::sweep_split_lanes(), relayout_wanted(h), h->nglob > h->nloc);
+  std::string s;
+  if (int rc = qh::guard_planning(&g_err, [&] { s = qh::plan_to_json(h->queue, plan_request(h, relayout_wanted(h))); })) return rc;
   if (needed) *needed = s.size() + 1;
   if (buf && cap) {
     const uint64_t n = std::min<uint64_t>(cap - 1, s.size());
@@ -1489,8 +1489,8 @@ int qh_plan_json(qh_handle h, char *buf, uint64_t cap, uint64_t *needed) {
 int qh_plan_export(qh_handle h, void *buf, uint64_t cap, uint64_t *needed) {
   if (!h) return fail(QH_ERR_ARG, "null");
   if (!qh::sweep_supported(h->nloc, h->bw)) return fail(QH_ERR_ARG, "state too small for sweeps");
-  qh::PlanResult pr = qh::plan_best(h->queue, h->nloc, h->shard, h->bw, qh::sweep_max_rb(),
-                                    qh::sweep_split_lanes(), relayout_wanted(h), h->nglob > h->nloc);
+  qh::PlanResult pr;
+  if (int rc = qh::guard_planning(&g_err, [&] { pr = qh::plan_best(h->queue, plan_request(h, relayout_wanted(h))); })) return rc;
   std::vector<uint64_t> out;
   auto put_bytes = [&](const void *p, size_t n) {
     const size_t w = (n + 7) / 8, at = out.size();
@@ -1677,7 +1677,7 @@ int verify_geometry(qh_state_s *h, uint64_t sig) {
 
 // What must be equal on every rank besides the geometry itself: the planner's switches and the build.
 uint64_t env_build_hash() {
-  std::string s = qh::planner_env_signature();
+  std::string s = qh::PlanSwitches::from_env().key();
   // (the EFFECTIVE values: an unset switch and one set to its default are the same plan)
   s += std::to_string(env_int("QH_EXCHANGE_SLAB_BITS", 3)) + ";" + std::to_string(env_int("QH_EXCHANGE_PACK", -1)) + ";" +
        std::to_string(env_int("QH_RELAYOUT", 1) != 0) + ";";

@@ -15,13 +15,15 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
+#include <new>
 #include <string>
-#include <system_error>
 #include <thread>
 #include <vector>
 
@@ -86,9 +88,6 @@ enum : uint32_t { OPF_DEFER_C = 1, OPF_USE_C = 2, OPF_REAL = 4,  // REAL: all fo
                   // waiting for it: fused, tools/gen_sweep_asm.py L_bfr*); the real scale c travels in g[0]
                   OPF_ROT_P = 2048, OPF_ROT_M = 4096 };
 
-// Gates of the form c*M with every entry of M in {1,-1,i,-i} (h, yroot, v = sqrt-x and
-// their adjoints: ops.py:130-132,152-162) cost additions only once the scalar c is moved
-// elsewhere.  Returns the variant (see tools/gen_sweep_asm.py, L_bf) or -1; c = g[0..1].
 inline bool env_flag(const char *name, bool dflt) {
   const char *e = getenv(name);
   return e ? atoi(e) != 0 : dflt;
@@ -99,6 +98,80 @@ inline int env_int(const char *name, int dflt) {
   return e ? atoi(e) : dflt;
 }
 
+// The planner's switches (DESIGN.md, appendix "environment switches"), read by from_env() once per flush on the calling
+// thread -- tests change them in-process; nothing below reads the environment.  key() covers every switch that can change a
+// plan, as parsed (a switch set to its default is an unset one), and none of the diagnostic ones: the plan cache's key and the
+// planner's part of the signature the ranks of a communicator compare before an exchange.
+struct PlanSwitches {
+  bool wave_pinned = false;    // QH_WAVE_BITS set: one greedy plan with wave_bits (clamped to 0..2; unset: 1, the Planner's default)
+  int wave_bits = 1;
+  bool split_lanes = true;     // QH_SPLIT_LANES
+  int max_rb = kMaxRegBits;    // QH_SWEEP_RB, clamped to 2..kMaxRegBits
+  bool bfly = true, propagate_x = true, defer_diag = true, rot_fuse = true;   // QH_BFLY, QH_PROPAGATE_X, QH_DEFER_DIAG, QH_ROT_FUSE
+  int lane_valu = 1, seats = 1;                          // QH_LANE_VALU, QH_SEATS
+  bool search = true, search_wb2 = true;                 // QH_PLAN_SEARCH, QH_PLAN_SEARCH_WB2
+  bool steps_pinned = false; uint64_t steps = 0;          // QH_PLAN_SEARCH_STEPS (unset: the budget follows the sweep time)
+  int streams = 0;             // QH_PLAN_SEARCH_STREAMS, clamped to 1..8 (0: unset)
+  int only_wb = -1, pick = -1;                           // QH_PLAN_ONLY_WB, QH_PLAN_SEARCH_PICK
+  int tiles_wb = 0;            // QH_PLAN_TILES "wb:b,b,..;b,b,..": tiles in the bit numbering of the flush's start (empty: unset)
+  std::vector<std::vector<int>> tiles;
+  bool threads = true, log = false, dag = false, verbose = false;   // diagnostics: QH_PLAN_SEARCH_THREADS, _LOG, QH_PLAN_DAG, _VERBOSE
+
+  static PlanSwitches from_env() {
+    PlanSwitches w;
+    if (const char *e = getenv("QH_WAVE_BITS")) { w.wave_pinned = true; w.wave_bits = std::max(0, std::min(kMaxWaveBits, atoi(e))); }
+    w.split_lanes = env_flag("QH_SPLIT_LANES", true);
+    w.max_rb = std::max(2, std::min(kMaxRegBits, env_int("QH_SWEEP_RB", kMaxRegBits)));
+    w.bfly = env_flag("QH_BFLY", true), w.propagate_x = env_flag("QH_PROPAGATE_X", true);
+    w.defer_diag = env_flag("QH_DEFER_DIAG", true), w.rot_fuse = env_flag("QH_ROT_FUSE", true);
+    w.lane_valu = env_int("QH_LANE_VALU", 1), w.seats = env_int("QH_SEATS", 1);
+    w.search = env_flag("QH_PLAN_SEARCH", true), w.search_wb2 = env_flag("QH_PLAN_SEARCH_WB2", true);
+    if (const char *e = getenv("QH_PLAN_SEARCH_STEPS")) { w.steps_pinned = true; w.steps = strtoull(e, nullptr, 10); }
+    if (const char *e = getenv("QH_PLAN_SEARCH_STREAMS")) w.streams = std::max(1, std::min(8, atoi(e)));
+    w.only_wb = env_int("QH_PLAN_ONLY_WB", -1), w.pick = env_int("QH_PLAN_SEARCH_PICK", -1);
+    if (const char *e = getenv("QH_PLAN_TILES")) {
+      w.tiles.emplace_back();
+      w.tiles_wb = atoi(e);
+      const char *p = strchr(e, ':');
+      for (p = p ? p + 1 : e; *p; ++p) {
+        if (*p == ';') w.tiles.emplace_back();
+        else if (*p != ',') { char *end = nullptr; w.tiles.back().push_back((int)strtol(p, &end, 10)); if (end == p) break; p = end - 1; }
+      }
+    }
+    w.threads = env_flag("QH_PLAN_SEARCH_THREADS", true), w.log = env_flag("QH_PLAN_SEARCH_LOG", false);
+    w.dag = env_flag("QH_PLAN_DAG", false), w.verbose = env_flag("QH_PLAN_VERBOSE", false);
+    return w;
+  }
+  std::string key() const {
+    char b[192];
+    snprintf(b, sizeof b, "%d,%d;%d;%d;%d%d%d%d;%d;%d;%d%d;%d,%llu;%d;%d;%d;%d:", wave_pinned, wave_bits, split_lanes, max_rb, bfly,
+             propagate_x, defer_diag, rot_fuse, lane_valu, seats, search, search_wb2, steps_pinned, (unsigned long long)steps, streams,
+             only_wb, pick, tiles_wb);
+    std::string s = b;
+    for (const auto &t : tiles) {
+      s += ';';
+      for (int v : t) s += std::to_string(v) + ',';
+    }
+    return s;
+  }
+};
+
+// One planning call's input besides the gates: the handle's side and the switches (engine.hip plan_request).
+struct PlanRequest {
+  int nloc, bw;
+  uint64_t shard;
+  bool relayout;      // sweeps may store into the second buffer with the tile bits moved to the low positions
+  bool keep_ghosts;   // sharded handle: gates that do nothing on this rank stay in the list (GateRec::ghost)
+  PlanSwitches sw;
+  std::string key() const {      // (the plan cache's)
+    return std::to_string(nloc) + "," + std::to_string(bw) + "," + std::to_string(shard) + "," + std::to_string(relayout) +
+           std::to_string(keep_ghosts) + ":" + sw.key();
+  }
+};
+
+// Gates of the form c*M with every entry of M in {1,-1,i,-i} (h, yroot, v = sqrt-x and
+// their adjoints: ops.py:130-132,152-162) cost additions only once the scalar c is moved
+// elsewhere.  Returns the variant (see tools/gen_sweep_asm.py, L_bf) or -1; c = g[0..1].
 inline int butterfly_variant(const double *g) {
   const double cr = g[0], ci = g[1];
   if (cr == 0.0 && ci == 0.0) return -1;
@@ -254,14 +327,15 @@ class Planner {
   // one gate as the tile selection sees it (pass_fast / search_run), and the state of a pass in front of a gate
   struct PassRec { uint64_t dense_bits, diag_bits; uint32_t score; int tgt; };
   struct PassState { size_t idx = 0; uint64_t blocked_all = 0, blocked_diag = 0; size_t count = 0, score = 0; bool valid = false; };
-  Planner(int nloc, uint64_t shard, int bw, int max_rb, bool split_lanes = true, int wave_bits = -1,
-          bool allow_relayout = false, bool keep_ghosts = false)
-      : nloc_(nloc), shard_(shard), amp_bytes_(bw == 128 ? 16 : 8), split_lanes_(split_lanes),
-        relayout_(allow_relayout), keep_ghosts_(keep_ghosts) {
-    rb_cap_ = std::min({max_rb, max_reg_bits(bw), nloc - kLaneBits});
-    lane_low_ = bw == 128 ? 3 : 4;   // 128-byte lines: 8 complex128 or 16 complex64 amplitudes
+  // wave_bits: the most wave bits a tile may have (-1: the switches' count)
+  explicit Planner(const PlanRequest &rq, int wave_bits = -1)
+      : nloc_(rq.nloc), shard_(rq.shard), amp_bytes_(rq.bw == 128 ? 16 : 8), split_lanes_(rq.sw.split_lanes),
+        relayout_(rq.relayout), keep_ghosts_(rq.keep_ghosts), butterflies_(rq.sw.bfly),
+        max_wave_(wave_bits >= 0 ? std::min(wave_bits, kMaxWaveBits) : rq.sw.wave_bits), propagate_x_(rq.sw.propagate_x),
+        lane_valu_(rq.sw.lane_valu), defer_diag_(rq.sw.defer_diag), rot_fuse_(rq.sw.rot_fuse), seats_(rq.sw.seats) {
+    rb_cap_ = std::min({rq.sw.max_rb, max_reg_bits(rq.bw), nloc_ - kLaneBits});
+    lane_low_ = rq.bw == 128 ? 3 : 4;   // 128-byte lines: 8 complex128 or 16 complex64 amplitudes
     lane_hi_ = kLaneBits - lane_low_;
-    if (wave_bits >= 0) max_wave_ = std::min(wave_bits, kMaxWaveBits);
   }
 
   // The gates of the queue as the sweeps will see them: shard bits resolved, the reference's 5-gate Toffolis
@@ -671,11 +745,10 @@ class Planner {
   bool split_lanes_;   // allow lane bits 3..5 to sit on arbitrary index bits (8 free tile bits)
   bool relayout_;      // sweeps may store into the second buffer with the tile bits moved to the low positions
   bool keep_ghosts_;   // sharded handle: gates that do nothing on this rank stay in the list (GateRec::ghost)
-  bool butterflies_ = env_flag("QH_BFLY", true);        // unit-entry butterfly ops (emit_ops_with)
+  bool butterflies_;                                     // unit-entry butterfly ops (emit_ops_with)
   static constexpr size_t dense_weight_ = 1;             // score of a dense gate when choosing tile bits (diagonal = 1)
-  // wave bits per tile (see plan_best): QH_WAVE_BITS pins it
-  int max_wave_ = std::max(0, std::min(kMaxWaveBits, env_int("QH_WAVE_BITS", 1)));
-  bool propagate_x_ = env_flag("QH_PROPAGATE_X", true);   // see propagate_x
+  int max_wave_;                                         // wave bits per tile (see plan_best)
+  bool propagate_x_;                                     // see propagate_x
   // Settled by measurement in rounds 2-4 and no longer switchable (profiles/r02..r04): in-place sweeps of
   // contiguous tiles store their wave exchanges un-undone; the least-used tile bits take the lane roles in op-heavy sweeps;
   // lane bits above the 2-MiB page come from the top; a chunk table needs two terms; controlled-phase ladders are factor
@@ -687,11 +760,11 @@ class Planner {
   bool fold_pending_ = false;                            // ... still to be placed in the sweep being emitted
   bool keep_line_bits_ = false;                          // the flush runs on pre-chosen tiles: see emit_ops_with (relayout stores)
   double fold_re_ = 1, fold_im_ = 0;
-  int lane_valu_ = env_int("QH_LANE_VALU", 1);          // 0 never, 1 by cost model (choose_lane_paths), 2 always (tests)
-  bool defer_diag_ = env_flag("QH_DEFER_DIAG", true);   // see build_sweep
+  int lane_valu_;                                        // 0 never, 1 by cost model (choose_lane_paths), 2 always (tests)
+  bool defer_diag_;                                      // see build_sweep
   static constexpr bool lookahead_ = true, reorder_ = true, lswap_early_ = true;   // see finish_relayout, reorder_for_fewer_swaps, emit_ops_with
-  bool rot_fuse_ = env_flag("QH_ROT_FUSE", true);                 // a pi/4-type phase on a butterfly's target rides in the butterfly (emit_ops_with)
-  int seats_ = env_int("QH_SEATS", 1);                             // op-heavy sweeps seat their lane-resident bits by cost (choose_seats)
+  bool rot_fuse_;                        // a pi/4-type phase on a butterfly's target rides in the butterfly (emit_ops_with)
+  int seats_;                            // op-heavy sweeps seat their lane-resident bits by cost (choose_seats)
   std::vector<uint64_t> alg_override_;
   std::vector<uint32_t> weight_;  // reference gate applications each pending record stands for
   std::vector<std::vector<int>> tiles_;   // tile bits of sweep 0, sweep 1, ... chosen for the whole flush (the tile search: set_tiles)
@@ -2099,23 +2172,14 @@ inline unsigned usable_cpus() {
   return n;
 }
 
-inline PlanResult plan_best(const std::vector<GateRec> &queue, int nloc, uint64_t shard, int bw, int max_rb,
-                            bool split_lanes, bool allow_relayout = false, bool keep_ghosts = false) {
-  if (getenv("QH_WAVE_BITS")) return Planner(nloc, shard, bw, max_rb, split_lanes, -1, allow_relayout, keep_ghosts).plan(queue);
-  if (const char *e = getenv("QH_PLAN_TILES")) {      // (probe: "wb:b,b,..;b,b,..": tiles in the bit numbering of the flush's start)
-    std::vector<std::vector<int>> tiles(1);
-    const int wb = atoi(e);
-    const char *p = strchr(e, ':');
-    for (p = p ? p + 1 : e; *p; ) {
-      if (*p == ';') { tiles.emplace_back(); ++p; continue; }
-      if (*p == ',') { ++p; continue; }
-      char *end = nullptr;
-      tiles.back().push_back((int)strtol(p, &end, 10));
-      if (end == p) break;
-      p = end;
-    }
-    Planner forced(nloc, shard, bw, max_rb, split_lanes, wb, allow_relayout, keep_ghosts);
-    forced.set_tiles(tiles);
+inline PlanResult plan_best(const std::vector<GateRec> &queue, const PlanRequest &rq) {
+  const PlanSwitches &sw = rq.sw;
+  const int nloc = rq.nloc, bw = rq.bw;
+  const bool keep_ghosts = rq.keep_ghosts;
+  if (sw.wave_pinned) return Planner(rq).plan(queue);
+  if (!sw.tiles.empty()) {      // (probe: tiles pinned by QH_PLAN_TILES)
+    Planner forced(rq, sw.tiles_wb);
+    forced.set_tiles(sw.tiles);
     return forced.plan(queue);
   }
   // the number of wave bits from the tile selections alone (Planner::skeleton), then ONE full plan: a third of the
@@ -2123,12 +2187,12 @@ inline PlanResult plan_best(const std::vector<GateRec> &queue, int nloc, uint64_
   int best_wb = 1;
   size_t best_n = 0, n_of[kMaxWaveBits + 1] = {0, 0, 0};
   bool have = false, best_far = false, far_of[kMaxWaveBits + 1] = {false, false, false};
-  const int only_wb = env_int("QH_PLAN_ONLY_WB", -1);      // (probe: everything below with a pinned number of wave bits)
+  const int only_wb = sw.only_wb;      // (probe: everything below with a pinned number of wave bits)
   for (int wb : {1, 2, 0}) {
     if (only_wb >= 0 && wb != only_wb) continue;
     size_t n = 0;
     bool far = false;
-    Planner(nloc, shard, bw, max_rb, split_lanes, wb, allow_relayout, keep_ghosts).skeleton(queue, &n, &far);
+    Planner(rq, wb).skeleton(queue, &n, &far);
     n_of[wb] = n;
     far_of[wb] = far;
     if (!have || (best_far && !far) || (best_far == far && n < best_n)) {
@@ -2139,30 +2203,32 @@ inline PlanResult plan_best(const std::vector<GateRec> &queue, int nloc, uint64_
     }
     if (best_n <= 1 && !best_far) break;
   }
-  Planner chosen(nloc, shard, bw, max_rb, split_lanes, best_wb, allow_relayout, keep_ghosts);
+  Planner chosen(rq, best_wb);
   // Fewer sweeps?  Worth a search only where a sweep costs about what the search does: budget = the label changes that
   // fit into ~3 sweep times of one host thread (2 x state bytes at 5.5 TB/s, ~5 ns per change on the GPU box's host: 4 M
   // changes = ~20 ms for a 16-GiB state), hidden behind the GPU whenever circuits are submitted back to back, paid once per
   // circuit with the plan cache on.  QH_PLAN_SEARCH=0 switches it off, QH_PLAN_SEARCH_STEPS pins the budget.
   // Round 6: the search is Planner::search_levels (nested cuts instead of tiles), and it runs as a PORTFOLIO: for the wave-bit
   // count the skeletons chose and for two wave bits (a tile of 13 bits instead of 12), every K from three below the greedy
-  // count (never below what the qubit count allows) up to one below it, each on six generator streams -- one host thread
-  // per task, so the wall time is ONE budget whatever fails (the search for the K that does not exist always does).  A task
-  // that finds tiles builds its plan and prices it (plan_predicted_ms: stream energy + op energy under the socket's power
-  // limit); the cheapest plan wins -- tilings of one circuit differ by 5-10 % in what their ops cost --, the greedy plan
-  // included (a sharded handle: fewest sweeps, then task order -- see below).  Every task is deterministic by itself, so the
-  // outcome does not depend on the threads' timing.  24 supremacy-30 instances (seeds 0-23): greedy 5-8 sweeps, the tile
-  // search 4 4 5 5 5 6 5 5 4 5 5 5 ..., now 4 4 4 4 4 5 4 4 4 4 5 4 4 4 4 4 4 5 4 5 4 4 4 5 -- for every one the minimum an integer
-  // program finds under 13-bit tiles (tools/tiling_milp.py); GPU time per circuit, old library against new on one box: 32.8 ->
-  // 29.8 ms on average, -19 % at best (profiles/r06/level_search.txt).
+  // count (never below what the qubit count allows) up to one below it, each on six generator streams.  The tasks run on a
+  // pool of min(tasks, usable CPUs) host threads that take them in list order, the calling thread joining in once it has the
+  // greedy plan: on an unsharded handle that is one thread per task, so the wall time is ONE budget whatever fails (the search
+  // for the K that does not exist always does).  A task that finds tiles builds its plan and prices it (plan_predicted_ms:
+  // stream energy + op energy under the socket's power limit); the cheapest plan wins -- tilings of one circuit differ by
+  // 5-10 % in what their ops cost --, the greedy plan included (a sharded handle: fewest sweeps, then task order -- see below).
+  // Every task is deterministic by itself, so the outcome depends neither on the threads' timing nor on their number.  A task
+  // that throws has no plan; on a sharded handle it fails the whole call (the ranks could pick different plans otherwise).
+  // 24 supremacy-30 instances (seeds 0-23): greedy 5-8 sweeps, the tile search 4 4 5 5 5 6 5 5 4 5 5 5 ..., now
+  // 4 4 4 4 4 5 4 4 4 4 5 4 4 4 4 4 4 5 4 5 4 4 4 5 -- for every one the minimum an integer program finds under 13-bit tiles
+  // (tools/tiling_milp.py); GPU time per circuit, old library against new on one box: 32.8 -> 29.8 ms on average, -19 % at
+  // best (profiles/r06/level_search.txt).
   uint64_t dense_bits = 0;
   for (const GateRec &q : queue) if (q.tgt >= 0 && q.tgt < nloc && !plan_diag(q.g, q.tgt)) dense_bits |= 1ull << q.tgt;
   const int lane_low = bw == 128 ? 3 : 4;
-  const int cap0 = (kLaneBits - lane_low) + std::min({max_rb, max_reg_bits(bw), nloc - kLaneBits});
-  if (best_n >= 3 && env_flag("QH_PLAN_SEARCH", true)) {
+  const int cap0 = (kLaneBits - lane_low) + std::min({sw.max_rb, max_reg_bits(bw), nloc - kLaneBits});
+  if (best_n >= 3 && sw.search) {
     const double sweep_us = 2.0 * (double)(bw == 128 ? 16 : 8) * (double)(1ull << nloc) / 5.5e6;
-    uint64_t budget = std::min<uint64_t>((uint64_t)(sweep_us * 640.0), 5000000);
-    if (const char *e = getenv("QH_PLAN_SEARCH_STEPS")) budget = strtoull(e, nullptr, 10);
+    const uint64_t budget = sw.steps_pinned ? sw.steps : std::min<uint64_t>((uint64_t)(sweep_us * 640.0), 5000000);
     struct Task {
       int wb;
       size_t K;
@@ -2170,6 +2236,7 @@ inline PlanResult plan_best(const std::vector<GateRec> &queue, int nloc, uint64_
       bool ok = false, planned = false;
       double ms = 0;
       PlanResult pr;
+      std::exception_ptr failed;
     };
     std::vector<Task> tasks;
     const size_t nmovable = (size_t)popc(dense_bits >> lane_low);
@@ -2177,89 +2244,86 @@ inline PlanResult plan_best(const std::vector<GateRec> &queue, int nloc, uint64_
     for (int wb : {1, 2, 0}) {
       // the wave-bit count the skeletons chose, and one and two wave bits (tiles of 12 and 13 bits) wherever they can save a sweep
       if (budget < 5000) break;
-      if (wb != best_wb && (wb == 0 || far_of[wb] || n_of[wb] == 0 || best_n < 4 || (wb == 2 && !env_flag("QH_PLAN_SEARCH_WB2", true)))) continue;
+      if (wb != best_wb && (wb == 0 || far_of[wb] || n_of[wb] == 0 || best_n < 4 || (wb == 2 && !sw.search_wb2))) continue;
       if (only_wb >= 0 && wb != only_wb) continue;
       const size_t cap = (size_t)(cap0 + wb), greedy = n_of[wb];
       const size_t kmin = std::max<size_t>({2, (nmovable + cap - 1) / cap, greedy > 3 ? greedy - 3 : 0});
       for (size_t K = kmin; K + 1 <= greedy && K <= best_n && K <= 8; ++K) shapes.emplace_back(wb, K);
     }
-    // six generator streams per shape (one host thread each) -- fewer on a host with few cores (an unsharded handle only: the
-    // ranks of a sharded state must find the same plan whatever their hosts are); QH_PLAN_SEARCH_STREAMS pins it
+    // six generator streams per shape -- fewer on a host with few cores (an unsharded handle only: the ranks of a sharded
+    // state must find the same plan whatever their hosts are); QH_PLAN_SEARCH_STREAMS pins it
     int streams = 6;
     if (const unsigned hw = usable_cpus(); hw && !keep_ghosts && !shapes.empty())
       streams = std::max(1, std::min(6, (int)(hw / shapes.size())));
-    streams = std::max(1, std::min(8, env_int("QH_PLAN_SEARCH_STREAMS", streams)));
+    if (sw.streams) streams = sw.streams;
     for (const auto &sh : shapes)
       for (int s = 0; s < streams; ++s) { tasks.emplace_back(); tasks.back().wb = sh.first; tasks.back().K = sh.second; tasks.back().stream = (uint64_t)(s + 1); }
-    // (the planners are made HERE: their constructors read the switches, and getenv stays out of the worker threads)
-    std::vector<Planner> searchers, planners;
-    searchers.reserve(tasks.size());
-    planners.reserve(tasks.size());
-    for (const Task &t : tasks) {
-      searchers.emplace_back(nloc, shard, bw, max_rb, split_lanes, t.wb, allow_relayout, keep_ghosts);
-      planners.emplace_back(nloc, shard, bw, max_rb, split_lanes, t.wb, allow_relayout, keep_ghosts);
-    }
     auto run = [&](Task &t) {
       const size_t i = (size_t)(&t - &tasks[0]);
-      std::vector<std::vector<int>> tiles;
-      t.ok = searchers[i].search_levels(queue, t.K, budget, t.stream, &tiles, &t.used);
-      if (!t.ok) return;
-      Planner &forced = planners[i];
-      forced.set_tiles(tiles);
-      t.pr = forced.plan(queue);
-      t.planned = t.pr.sweeps.size() <= t.K && !plan_has_far_tile(t.pr);     // (the model ignores relabelling and tile positions: check)
+      try {
+        std::vector<std::vector<int>> tiles;
+        t.ok = Planner(rq, t.wb).search_levels(queue, t.K, budget, t.stream, &tiles, &t.used);
+        if (!t.ok) return;
+        Planner forced(rq, t.wb);
+        forced.set_tiles(tiles);
+        t.pr = forced.plan(queue);
+        t.planned = t.pr.sweeps.size() <= t.K && !plan_has_far_tile(t.pr);     // (the model ignores relabelling and tile positions: check)
+      } catch (...) { t.failed = std::current_exception(); return; }     // (no plan: t.planned is still false)
       // A sharded handle must pick what every other rank picks, and the price is not rank-invariant (a gate that is a ghost on this
       // rank has left the op list it is computed from): there the fewest sweeps win, ties by the order of the task list.
       if (t.planned) t.ms = keep_ghosts ? 1000.0 * (double)t.pr.sweeps.size() + 1e-3 * (double)(i + 1) : plan_predicted_ms(t.pr, nloc, bw);
     };
+    std::atomic<size_t> next{0};
+    auto drain = [&] { for (size_t i; (i = next++) < tasks.size(); ) run(tasks[i]); };
+    std::vector<std::thread> pool;
+    const size_t workers = sw.threads ? std::min<size_t>(tasks.size(), usable_cpus()) : 0;
+    try { while (pool.size() < workers) pool.emplace_back(drain); } catch (...) {}    // (threads refused: the caller drains the rest)
     PlanResult greedy_plan;
-    if (tasks.empty() || !env_flag("QH_PLAN_SEARCH_THREADS", true)) {
-      for (Task &t : tasks) run(t);
-      greedy_plan = chosen.plan(queue);
-    } else {
-      std::vector<std::thread> th;
-      th.reserve(tasks.size());
-      std::vector<Task *> inline_tasks;       // (a host that refuses another thread: the task runs here -- same answer, later)
-      for (Task &t : tasks) {
-        try { th.emplace_back(run, std::ref(t)); } catch (const std::system_error &) { inline_tasks.push_back(&t); }
-      }
-      greedy_plan = chosen.plan(queue);
-      for (Task *t : inline_tasks) run(*t);
-      for (std::thread &x : th) x.join();
-    }
+    std::exception_ptr greedy_failed;
+    try { greedy_plan = chosen.plan(queue); } catch (...) { greedy_failed = std::current_exception(); next = tasks.size(); }
+    drain();
+    for (std::thread &x : pool) x.join();
+    if (greedy_failed) std::rethrow_exception(greedy_failed);
     // every task is deterministic by itself (its generator, its budget in label changes); the winner is the plan with the
     // smallest predicted time, ties by the order of the task list -- whatever the threads' timing was
     const Task *win = nullptr;
     double best_ms = keep_ghosts ? 1000.0 * (double)greedy_plan.sweeps.size() : plan_predicted_ms(greedy_plan, nloc, bw);
     for (const Task &t : tasks)
       if (t.planned && t.pr.sweeps.size() <= greedy_plan.sweeps.size() && t.ms < best_ms) { win = &t; best_ms = t.ms; }
-    if (const int pick = env_int("QH_PLAN_SEARCH_PICK", -1); pick >= 0) {      // (probe: the pick-th task of the list, if it has a plan -- tools/probes/r06_candidates.sh)
-      if ((size_t)pick < tasks.size() && tasks[pick].planned) win = &tasks[pick];
+    if (sw.pick >= 0) {      // (probe: the pick-th task of the list, if it has a plan -- tools/probes/r06_candidates.sh)
+      if ((size_t)sw.pick < tasks.size() && tasks[sw.pick].planned) win = &tasks[sw.pick];
     }
-    if (env_flag("QH_PLAN_SEARCH_LOG", false)) {
+    if (sw.log) {
       for (const Task &t : tasks)
         fprintf(stderr, "[qh plan search]   task %d: wave bits %d K=%zu stream %llu: %s after %llu label changes%s\n", (int)(&t - &tasks[0]), t.wb, t.K, (unsigned long long)t.stream,
-                t.ok ? "found" : "not found", (unsigned long long)t.used,
+                t.failed ? "FAILED (exception)" : t.ok ? "found" : "not found", (unsigned long long)t.used,
                 t.planned ? (", " + std::to_string(t.pr.sweeps.size()) + " sweeps, predicted " + std::to_string(t.ms) + " ms").c_str() : "");
       fprintf(stderr, "[qh plan search] greedy: %d wave bit(s), %zu sweeps, predicted %.2f ms; chosen: %s (%zu tasks, budget %llu label changes each)\n", best_wb,
               greedy_plan.sweeps.size(), plan_predicted_ms(greedy_plan, nloc, bw),
               win ? (std::to_string(win->pr.sweeps.size()) + " sweeps with " + std::to_string(win->wb) + " wave bit(s), predicted " + std::to_string(win->ms) + " ms").c_str() : "greedy",
               tasks.size(), (unsigned long long)budget);
     }
+    if (keep_ghosts)
+      for (const Task &t : tasks) if (t.failed) std::rethrow_exception(t.failed);
     if (win) return win->pr;
     return greedy_plan;
   }
   return chosen.plan(queue);
 }
 
-inline std::string plan_to_json(const std::vector<GateRec> &queue, int nloc, uint64_t shard, int bw = 128,
-                                int max_rb = kMaxRegBits, bool split_lanes = true, bool allow_relayout = false,
-                                bool keep_ghosts = false) {
-  if (nloc < kLaneBits + 2) return "{\"sweeps\":[],\"note\":\"state too small for sweeps\"}";
-  PlanResult pr = plan_best(queue, nloc, shard, bw, max_rb, split_lanes, allow_relayout, keep_ghosts);
+// The barrier in front of the C-ABI: planning may throw (std::bad_alloc; a failed search task on a sharded handle).
+template <class F> int guard_planning(std::string *err, F &&f) {
+  try { f(); } catch (const std::bad_alloc &) { *err = "planning: out of host memory"; return QH_ERR_NOMEM; }
+  catch (const std::exception &e) { *err = std::string("planning: ") + e.what(); return QH_ERR_ARG; }
+  return QH_OK;
+}
+
+inline std::string plan_to_json(const std::vector<GateRec> &queue, const PlanRequest &rq) {
+  if (rq.nloc < kLaneBits + 2) return "{\"sweeps\":[],\"note\":\"state too small for sweeps\"}";
+  PlanResult pr = plan_best(queue, rq);
   std::string s = "{\"noop_gates\":" + std::to_string(pr.noop_gates);
-  if (env_flag("QH_PLAN_DAG", false))         // (tools/tiling_milp.py)
-    s += ",\"dag\":" + Planner(nloc, shard, bw, max_rb, split_lanes, 1, allow_relayout, keep_ghosts).dag_json(queue);
+  if (rq.sw.dag)         // (tools/tiling_milp.py)
+    s += ",\"dag\":" + Planner(rq, 1).dag_json(queue);
   s += ",\"sweeps\":[";
   char buf[384];
   for (size_t i = 0; i < pr.sweeps.size(); ++i) {
@@ -2287,7 +2351,7 @@ inline std::string plan_to_json(const std::vector<GateRec> &queue, int nloc, uin
              sp.tables.size() / 2, rp.c_str(), (unsigned long long)sp.fixed_ones, (unsigned long long)sp.ntiles,
              (unsigned long long)sp.alg_bytes, (unsigned long long)sp.swept_bytes);
     s += buf;
-    if (env_flag("QH_PLAN_VERBOSE", false)) {   // op list for tools/plan_dump.py (debugging aid)
+    if (rq.sw.verbose) {   // op list for tools/plan_dump.py (debugging aid)
       s.pop_back();
       s += ",\"ops\":[";
       for (size_t k = 0; k < sp.ops.size(); ++k) {

@@ -77,6 +77,25 @@ def test_ranks_with_other_planner_switches_are_told_apart(monkeypatch):
   assert c['signature'] != a['signature']
 
 
+# every plan-changing switch whose default can be written as a value (not QH_WAVE_BITS, QH_PLAN_TILES, nor the automatic search
+# budget and stream count), set to that default
+_DEFAULTS = {'QH_SPLIT_LANES': '1', 'QH_SWEEP_RB': '6', 'QH_BFLY': '1', 'QH_LANE_VALU': '1', 'QH_DEFER_DIAG': '1',
+             'QH_PROPAGATE_X': '1', 'QH_ROT_FUSE': '1', 'QH_SEATS': '1', 'QH_PLAN_SEARCH': '1', 'QH_PLAN_SEARCH_WB2': '1',
+             'QH_PLAN_ONLY_WB': '-1', 'QH_PLAN_SEARCH_PICK': '-1'}
+
+
+def test_a_switch_set_to_its_default_is_an_unset_one(monkeypatch):
+  """The signature is built from the switches as parsed: one set to its default gives the signature of an unset one (ranks
+  whose launch scripts differ only there exchange), while QH_WAVE_BITS=-1 -- a pin to no wave bit, not the default -- does not."""
+  base = _plan_ladder_point(34, 2, reps=1)[0]['geometries'][0]['signature']
+  for name, value in _DEFAULTS.items():
+    monkeypatch.setenv(name, value)
+    assert _plan_ladder_point(34, 2, reps=1)[0]['geometries'][0]['signature'] == base, name
+    monkeypatch.delenv(name)
+  monkeypatch.setenv('QH_WAVE_BITS', '-1')
+  assert _plan_ladder_point(34, 2, reps=1)[0]['geometries'][0]['signature'] != base
+
+
 def test_slab_bits_are_capped_at_three(monkeypatch):
   """ADVICE r3 (medium): UnitPerm::slab_pos has three entries; QH_EXCHANGE_SLAB_BITS above that must not reach the kernel."""
   monkeypatch.setenv('QH_EXCHANGE_SLAB_BITS', '5')

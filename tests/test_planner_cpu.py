@@ -175,3 +175,41 @@ def test_dry_flush_builds_the_device_op_buffers(name):
       native.check(lib.qh_apply1(h, t, gp) if c == workloads.NO_CTL else lib.qh_applyc(h, c, t, gp))
     native.check(lib.qh_flush(h))
   lib.qh_destroy(h)
+
+
+def test_a_changed_switch_is_not_a_cached_plan(monkeypatch):
+  """The plan cache's key is the parsed switches: QH_WAVE_BITS=-1 pins the tiles to no wave bit (a greedy plan, no
+  search), so the same queue flushed again after it is set must be planned anew, not served the plan from before."""
+  lib = native.load()
+  monkeypatch.setenv('QH_RELAYOUT', '0')
+  ops, g8 = workloads.supremacy_stream(30, 20, seed=2).arrays()
+  g8 = np.ascontiguousarray(g8, dtype=np.float64)
+
+  def flush_sweeps(h):
+    for k in range(len(ops)):
+      gp = ctypes.cast(g8.ctypes.data + 64 * k, _dp)
+      c, t = int(ops[k, 0]), int(ops[k, 1])
+      native.check(lib.qh_apply1(h, t, gp) if c == workloads.NO_CTL else lib.qh_applyc(h, c, t, gp))
+    before = native.QhStats()
+    native.check(lib.qh_get_stats(h, ctypes.byref(before)))
+    native.check(lib.qh_flush(h))
+    after = native.QhStats()
+    native.check(lib.qh_get_stats(h, ctypes.byref(after)))
+    return after.sweeps - before.sweeps
+
+  def dry():
+    h = ctypes.c_void_p()
+    native.check(lib.qh_create_dry(30, 128, ctypes.byref(h)))
+    native.check(lib.qh_set_fusion(h, native.QH_FUSE_SWEEP))
+    return h
+
+  h = dry()
+  first = flush_sweeps(h)
+  monkeypatch.setenv('QH_WAVE_BITS', '-1')
+  again = flush_sweeps(h)
+  lib.qh_destroy(h)
+  h = dry()
+  fresh = flush_sweeps(h)
+  lib.qh_destroy(h)
+  assert fresh != first, (first, fresh, 'the switch no longer changes this plan: the test does not test what it is for')
+  assert again == fresh, (first, again, fresh)

@@ -1,6 +1,10 @@
 """The planner's output executed on the CPU (tests/plan_interp.py) against the oracle: random
 circuits, every plan shape the engine can be switched to, single and sharded handles.  No GPU."""
 import ctypes
+import json
+import os
+import subprocess
+import sys
 import zlib
 
 import numpy as np
@@ -320,3 +324,32 @@ def test_level_search_saves_sweeps_and_keeps_the_amplitudes(oracle, monkeypatch)
     got = psi.copy()
     plan_interp.run_plan(got, sweeps, n)
     assert np.max(np.abs(got - want)) < 1e-11, (n, seed, len(base), len(sweeps))
+
+
+_PLAN_IN_CHILD = """
+import os, sys, json
+cpus = sys.argv[1]
+if cpus == 'one':
+  os.sched_setaffinity(0, {min(os.sched_getaffinity(0))})     # before the library is loaded
+from tests.test_planner_cpu import _plan
+from qcc_amd import workloads
+print(json.dumps(_plan(30, *workloads.supremacy_stream(30, 20, seed=2).arrays())))
+"""
+
+
+def test_the_number_of_search_threads_does_not_change_the_plan():
+  """plan_best runs its portfolio on min(tasks, usable CPUs) host threads that take the tasks in list order; every task is
+  deterministic by itself.  With the task list pinned (streams and budget), a process restricted to one CPU, one with every
+  CPU and one without search threads (QH_PLAN_SEARCH_THREADS=0) must plan supremacy-30 seed 2 alike."""
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  env = dict(os.environ, QH_PLAN_SEARCH_STREAMS='6', QH_PLAN_SEARCH_STEPS='400000', QH_PLAN_VERBOSE='1')
+  env.pop('QH_PLAN_SEARCH_THREADS', None)
+
+  def plan(cpus, **extra):
+    out = subprocess.run([sys.executable, '-c', _PLAN_IN_CHILD, cpus], cwd=root, env=dict(env, **extra), check=True,
+                         capture_output=True, text=True, timeout=600).stdout
+    return json.loads(out)
+
+  one, every, serial = plan('one'), plan('all'), plan('all', QH_PLAN_SEARCH_THREADS='0')
+  assert one == every == serial
+  assert len(one['sweeps']) >= 1
