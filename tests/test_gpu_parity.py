@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from qcc_amd import device, gates, native, workloads
+from tests import torch_reference
 from tests.oracle_lib import NO_CTL
 
 pytestmark = pytest.mark.gpu
@@ -388,11 +389,12 @@ def test_full_size_30q_properties(fusion):
     idx = rng.integers(0, 1 << n, size=512)
     want = workloads.qft_analytic(n, x, idx)
     got = np.array([st.amplitude(int(i)) for i in idx])
-    assert np.max(np.abs(got - want)) <= 1e-10
+    tol = 1e-12 * 2.0 ** (-n / 2)          # relative to the amplitude modulus 2^(-n/2) (every amplitude: test_gpu_fullstate.py)
+    assert np.max(np.abs(got - want)) <= tol
     # a contiguous window too (exercises low bits)
     win = st.download(offset=(1 << 29) + 12345, count=4096)
     wantw = workloads.qft_analytic(n, x, np.arange((1 << 29) + 12345, (1 << 29) + 12345 + 4096))
-    assert np.max(np.abs(win - wantw)) <= 1e-10
+    assert np.max(np.abs(win - wantw)) <= tol
     # inverse: adjoint gates in reverse order
     inv_ops = ops[::-1].copy()
     inv_g = g8[::-1].copy().reshape(-1, 4, 2)
@@ -478,7 +480,8 @@ def test_complex64_fused_streams_vs_oracle(oracle, n, ngates, seed):
 @pytest.mark.parametrize('n,bw', [(20, 64), (27, 64), (27, 128)])
 def test_qft_fused_analytic(n, bw):
   """QFT of a basis state against the closed form, every amplitude: 20 qubits in one or two
-  sweeps; 27 qubits with super-tiles (wave bits, OP_WSWAP) in both element widths."""
+  sweeps; 27 qubits with super-tiles (wave bits, OP_WSWAP) in both element widths.  (The closed form
+  of tests/torch_reference.py: exact integer phases, 2^22 amplitudes at a time on the host.)"""
   x = 0xBEEF5 & ((1 << n) - 1)
   ops, g8 = workloads.qft_stream(range(n)).arrays()
   with device.DeviceState(n, bw, fusion=native.QH_FUSE_SWEEP) as st:
@@ -488,10 +491,10 @@ def test_qft_fused_analytic(n, bw):
     sweeps = st.stats()['sweeps']
   assert sweeps <= 4
   tol = (3e-5 if bw == 64 else 1e-12) * 2.0 ** (-n / 2)      # relative to the amplitude modulus 2^(-n/2)
-  for lo in range(0, 1 << n, 1 << 22):                     # closed form in slices (python-int phases)
-    idx = np.arange(lo, min(lo + (1 << 22), 1 << n), 4099 if n > 22 else 1)
-    want = workloads.qft_analytic(n, x, idx)
-    assert np.max(np.abs(got[idx] - want)) < tol
+  for lo in range(0, 1 << n, 1 << 22):
+    cnt = min(1 << 22, (1 << n) - lo)
+    want = torch_reference.qft_closed_form(n, x, lo, cnt).numpy()
+    assert np.max(np.abs(got[lo:lo + cnt] - want)) < tol, lo
 
 
 @pytest.mark.parametrize('lane_valu', ['1', '2'])
