@@ -128,6 +128,14 @@ int qh_applyc(qh_handle h, int ctl, int tgt, const double gate[8]);
  * multi-controlled gates.                                                    */
 int qh_apply_bits(qh_handle h, uint64_t ctl_mask, int tgt_bit,
                   const double gate[8]);
+/* Dense 2^k x 2^k complex matrix (row-major, 2*4^k doubles, interleaved re,im) on LOGICAL bits bits[0..k-1];
+ * bit j of the matrix's row/column index is logical bit bits[j] (bits[0] least significant); applied where every
+ * bit of ctl_mask is 1.  1 <= k <= 6.  The caller's matrix is not referenced after the call returns.
+ * Any matrix, unitary or not.  A barrier: what is queued runs first (one kernel of its own, never fused).
+ * Errors: QH_ERR_ARG (null pointer, k out of range, k + local controls above 15, dry handle), QH_ERR_BAD_QUBIT,
+ * QH_ERR_SAME_QUBIT (a bit twice, a control that is also a target), QH_ERR_NONLOCAL (a target held by the shard
+ * index: nothing changes).  A control on a shard bit is dropped where met, and the call is a counted no-op where not. */
+int qh_apply_matrix(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, const double *matrix);
 
 /* The whole stream in one call: ops[2k] = control qubit of gate k or QH_NO_CTL (then qh_apply1), ops[2k+1] =
  * target qubit, gates + 8k = its 8 doubles -- exactly `count` qh_apply1/qh_applyc calls (xgates.cc:89-145), without

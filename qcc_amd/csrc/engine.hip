@@ -22,6 +22,7 @@
 
 #include "../../include/qcc_hip.h"
 #include "kernels_gate.hip.h"
+#include "kernels_dense.hip.h"
 #include "planner.h"
 #include "kernels_sweep.hip.h"
 
@@ -48,6 +49,8 @@ int fail(int code, const char *fmt, ...) {
   } while (0)
 
 constexpr int kRedBlocks = 1024;
+constexpr int kMatSlots = 8;                                              // qh_apply_matrix staging ring
+constexpr size_t kMatSlotBytes = (size_t)16 << (2 * qh::kMaxDenseBits);   // one complex128 2^6 x 2^6 matrix
 
 }  // namespace
 
@@ -74,6 +77,12 @@ struct qh_state_s {
   uint64_t *d_tmax = nullptr;  // per-unit maxima the last sweep of a flush leaves for qh_argmax (SweepParams::tilemax)
   uint64_t tmax_cap = 0;       // entries
   qh::Comm *comm = nullptr;    // multi-GPU exchange (exchange.hip.h)
+  // qh_apply_matrix: the caller's matrix is copied into pinned slot i, uploaded on the stream into device slot i, and slot i
+  // is reused only after the event recorded behind the kernel that read it has completed
+  void *mat_host = nullptr, *mat_dev = nullptr;
+  hipEvent_t mat_ev[kMatSlots] = {};
+  bool mat_used[kMatSlots] = {};
+  unsigned mat_next = 0;
   uint64_t amp_bytes() const { return bw == 128 ? 16 : 8; }
   uint64_t local_mask() const { return nloc >= 64 ? ~0ull : ((1ull << nloc) - 1ull); }
 };
@@ -625,7 +634,7 @@ int select_device(int device) {
 extern "C" {
 
 const char *qh_last_error(void) { return g_err.c_str(); }
-int qh_version(void) { return 105; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
+int qh_version(void) { return 106; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
 
 int qh_device_count(int *count) {
   if (!count) return fail(QH_ERR_ARG, "null");
@@ -757,6 +766,9 @@ int qh_destroy(qh_handle h) {
     if (h->d_redi) (void)hipFree(h->d_redi);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
+    for (hipEvent_t e : h->mat_ev) if (e) (void)hipEventDestroy(e);
+    if (h->mat_dev) (void)hipFree(h->mat_dev);
+    if (h->mat_host) (void)hipHostFree(h->mat_host);
     for (hipEvent_t e : h->laps) (void)hipEventDestroy(e);
     if (h->owns_mem && h->d_psi) (void)hipFree(h->d_psi);
     if (h->d_alt) (void)hipFree(h->d_alt);
@@ -1411,6 +1423,139 @@ int qh_project_bit(qh_handle h, int logical_bit, int value) {
   else
     hipLaunchKernelGGL(qh::k_project<float>, dim3(grid), dim3(256), 0, h->stream, (float2 *)h->d_psi, nwork, ins);
   return check_launch(h);
+}
+}  // extern "C"
+
+namespace {
+
+// Copies the caller's matrix (4^k complex128) into the next staging slot, converted to the state's width, and uploads
+// it on the handle's stream.  *dev = the device copy; *slot = the slot whose event goes behind the kernel.
+int stage_matrix(qh_state_s *h, int k, const double *m, const void **dev, unsigned *slot) {
+  if (!h->mat_host) {
+    HIP_TRY(hipHostMalloc(&h->mat_host, kMatSlots * kMatSlotBytes, hipHostMallocDefault));
+    HIP_TRY(hipMalloc(&h->mat_dev, kMatSlots * kMatSlotBytes));
+    for (hipEvent_t &e : h->mat_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  const unsigned s = h->mat_next++ % kMatSlots;
+  if (h->mat_used[s]) {
+    const int rc = wait_event(h, h->mat_ev[s], "qh_apply_matrix");   // the kernel that last read slot s has finished
+    if (rc) return rc;
+  }
+  const size_t n = (size_t)1 << (2 * k);
+  char *host = (char *)h->mat_host + s * kMatSlotBytes;
+  char *d = (char *)h->mat_dev + s * kMatSlotBytes;
+  size_t bytes = n * 16;
+  if (h->bw == 128) {
+    memcpy(host, m, bytes);
+  } else {
+    float *f = (float *)host;
+    for (size_t i = 0; i < 2 * n; ++i) f[i] = (float)m[i];
+    bytes = n * 8;
+  }
+  HIP_TRY(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, h->stream));
+  *dev = d;
+  *slot = s;
+  return QH_OK;
+}
+
+template <typename R, int K>
+void launch_dense_k(qh_state_s *h, const qh::DenseArgs &a, const void *mat) {
+  using A = typename qh::AmpT<R>::type;
+  if constexpr (K <= 4) {
+    constexpr int U = K == 1 ? 4 : K == 2 ? 2 : 1;   // >= 8 amplitude loads in flight per thread
+    hipLaunchKernelGGL((qh::k_dense_reg<R, K, U>), dim3(pick_grid(a.nwork, 256 * U)), dim3(256), 0, h->stream, (A *)h->d_psi,
+                       (const A *)mat, a);
+  } else {
+    // every block stages M in LDS first: a grid of a few blocks per CU, grid-stride over the groups
+    const unsigned grid = (unsigned)std::min<uint64_t>(pick_grid(a.nwork << (K - 4), 256), 2048);
+    hipLaunchKernelGGL((qh::k_dense_split<R, K>), dim3(grid), dim3(256), 0, h->stream, (A *)h->d_psi, (const A *)mat, a);
+  }
+}
+
+template <typename R>
+void launch_dense(qh_state_s *h, int k, const qh::DenseArgs &a, const void *mat) {
+  switch (k) {
+    case 1: return launch_dense_k<R, 1>(h, a, mat);
+    case 2: return launch_dense_k<R, 2>(h, a, mat);
+    case 3: return launch_dense_k<R, 3>(h, a, mat);
+    case 4: return launch_dense_k<R, 4>(h, a, mat);
+    case 5: return launch_dense_k<R, 5>(h, a, mat);
+    default: return launch_dense_k<R, 6>(h, a, mat);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int qh_apply_matrix(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, const double *matrix) {
+  if (!h || !bits || !matrix) return fail(QH_ERR_ARG, "apply_matrix: null handle, bits or matrix");
+  if (k < 1 || k > qh::kMaxDenseBits) return fail(QH_ERR_ARG, "apply_matrix: k = %d outside [1,%d]", k, qh::kMaxDenseBits);
+  uint64_t tmask = 0;
+  for (int j = 0; j < k; ++j)
+    if (bits[j] < 0 || bits[j] >= h->nglob)
+      return fail(QH_ERR_BAD_QUBIT, "apply_matrix: bit %d out of range [0,%d)", bits[j], h->nglob);
+  if (h->nglob < 64 && (ctl_mask >> h->nglob))
+    return fail(QH_ERR_BAD_QUBIT, "apply_matrix: control mask 0x%llx has bits >= %d", (unsigned long long)ctl_mask, h->nglob);
+  for (int j = 0; j < k; ++j) {
+    if ((tmask >> bits[j]) & 1ull) return fail(QH_ERR_SAME_QUBIT, "apply_matrix: bit %d appears twice", bits[j]);
+    tmask |= 1ull << bits[j];
+  }
+  if (ctl_mask & tmask)
+    return fail(QH_ERR_SAME_QUBIT, "apply_matrix: control and target share bits 0x%llx", (unsigned long long)(ctl_mask & tmask));
+  int nlc = 0;                 // (a logical bit stays local or in the shard index whatever the relayout sweeps do)
+  for (int b = 0; b < h->nglob; ++b)
+    if (((ctl_mask >> b) & 1ull) && h->perm[b] < h->nloc) ++nlc;
+  if (k + nlc > qh::kMaxIns)
+    return fail(QH_ERR_ARG, "apply_matrix: %d targets + %d local controls exceed the %d bits one index enumeration inserts (kMaxIns)",
+                k, nlc, qh::kMaxIns);
+  for (int j = 0; j < k; ++j)
+    if (h->perm[bits[j]] >= h->nloc)
+      return fail(QH_ERR_NONLOCAL, "apply_matrix: logical bit %d is held by the shard index (physical bit %d, local bits: %d); "
+                  "exchange first", bits[j], h->perm[bits[j]], h->nloc);
+  if (h->dry) return fail(QH_ERR_ARG, "null/dry");
+  HIP_TRY(hipSetDevice(h->device));
+  int rc = flush_impl(h);      // a barrier: what is queued runs first, on whatever layout it leaves
+  if (rc) return rc;
+  uint64_t cm_all = 0;         // physical local control bits
+  for (int b = 0; b < h->nglob; ++b) {
+    if (!((ctl_mask >> b) & 1ull)) continue;
+    const int pb = h->perm[b];
+    if (pb < h->nloc) {
+      cm_all |= 1ull << pb;
+    } else if (!((h->shard >> (pb - h->nloc)) & 1ull)) {   // a shard-bit control that is 0 on this shard
+      h->stats.gates_submitted++;
+      h->stats.gates_noop++;
+      return QH_OK;
+    }                                                        // (met: dropped)
+  }
+  const uint64_t kLow = (h->nloc > 2) ? 3ull : 0ull;         // as launch_single: bits 0-1 are a predicate
+  qh::DenseArgs a{};
+  a.lowpred = (uint32_t)(cm_all & kLow);
+  const uint64_t cm = cm_all & ~kLow;
+  uint64_t ptmask = 0;
+  for (int j = 0; j < k; ++j) {
+    a.t[j] = h->perm[bits[j]];
+    ptmask |= 1ull << a.t[j];
+  }
+  a.ins.ones = cm;
+  for (int b = 0; b < 64; ++b)
+    if (((cm | ptmask) >> b) & 1ull) a.ins.pos[a.ins.n++] = b;
+  a.nwork = 1ull << (h->nloc - k - __builtin_popcountll(cm));
+  const void *dmat = nullptr;
+  unsigned slot = 0;
+  if ((rc = stage_matrix(h, k, matrix, &dmat, &slot))) return rc;
+  if (h->bw == 128) launch_dense<double>(h, k, a, dmat);
+  else launch_dense<float>(h, k, a, dmat);
+  if ((rc = check_launch(h))) return rc;
+  HIP_TRY(hipEventRecord(h->mat_ev[slot], h->stream));
+  h->mat_used[slot] = true;
+  const uint64_t ab = h->amp_bytes();
+  h->stats.gates_submitted++;
+  h->stats.kernels_launched++;
+  h->stats.bytes_algorithmic += (1ull << (h->nloc - __builtin_popcountll(cm_all))) * ab * 2;
+  h->stats.bytes_swept += (a.nwork << k) * ab * 2;
+  return QH_OK;
 }
 
 int qh_get_stats(qh_handle h, qh_stats *out) {

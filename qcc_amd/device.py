@@ -194,6 +194,17 @@ class DeviceState:
     _keep, p = _g8(gate)
     native.check(self.lib.qh_apply_bits(self.h, int(ctl_mask), int(tgt_bit), p))
 
+  def apply_matrix(self, matrix, bits, ctl_mask=0):
+    """Dense (2^k, 2^k) matrix, 1 <= k <= 6, on LOGICAL bits (as apply_bits): bit j of the matrix's row / column index is
+    logical bit bits[j], bits[0] the least significant; applied where every bit of ctl_mask is 1 (qh_apply_matrix)."""
+    m = np.ascontiguousarray(matrix, dtype=np.complex128)
+    bits = np.ascontiguousarray([int(b) for b in bits], dtype=np.int32)
+    k = len(bits)
+    if m.shape != (1 << k, 1 << k):
+      raise ValueError(f'apply_matrix: a {m.shape} matrix for {k} bits')
+    native.check(self.lib.qh_apply_matrix(self.h, k, bits.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(ctl_mask),
+                                          m.ctypes.data_as(_dp)))
+
   def apply_bits_raw(self, ctl_mask, tgt_bit, addr):
     """apply_bits with the gate given as the address of 8 contiguous doubles."""
     rc = self.lib.qh_apply_bits(self.h, ctl_mask, tgt_bit, ctypes.cast(addr, _dp))

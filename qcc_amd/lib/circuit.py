@@ -74,6 +74,18 @@ def _u1_operator(value):
 
 
 
+_DENSE_MAX_BITS = 6        # qh_apply_matrix: dense operators on up to 6 qubits run on the device
+
+
+def _dense_bits(op):
+    """k if op is a square 2^k x 2^k matrix with 1 <= k <= 6, else 0."""
+    shape = np.shape(op)
+    if len(shape) != 2 or shape[0] != shape[1] or shape[0] < 2 or shape[0] & (shape[0] - 1):
+        return 0
+    k = int(shape[0]).bit_length() - 1
+    return k if k <= _DENSE_MAX_BITS else 0
+
+
 def _dump_flags_set():
     if _flags is None:
         return False
@@ -550,8 +562,41 @@ class qc:
         self.applyc(ops.RotationZ(theta), ctl, idx, 'crz', val=theta)
 
     def unitary(self, op, idx):
-        """Arbitrary multi-qubit unitary via the full matrix (host, small n only)."""
+        """Multi-qubit operator on qubits idx .. idx+k-1 (qubit idx the matrix's most significant bit, np.kron order).
+        Up to 6 qubits in range it runs on the device (qh_apply_matrix: no download, no 2^n x 2^n matrix); anything
+        else, and devices without apply_matrix, take the reference's route through the full matrix on the host."""
+        k = _dense_bits(op)
+        if k and isinstance(idx, (int, np.integer)) and 0 <= idx and idx + k <= self._nbits:
+            dev = self._ensure_device()
+            if hasattr(dev, 'apply_matrix'):
+                n = self._nbits
+                dev.apply_matrix(np.asarray(ops.Operator(op)), [n - int(idx) - k + j for j in range(k)])
+                self._gate_done()
+                return
         self.psi = ops.Operator(op)(self.psi, idx)
+
+    def apply_matrix(self, op, qubits, ctl=()):
+        """Dense (2^k, 2^k) operator, 1 <= k <= 6, on the qubits `qubits` (any order, not necessarily adjacent;
+        qubits[0] is the matrix's most significant bit), applied where every qubit of `ctl` is 1.  An extension: the
+        reference has no such method; qc.unitary(op, idx) is apply_matrix(op, range(idx, idx + k))."""
+        k = _dense_bits(op)
+        qubits, ctl = [int(q) for q in qubits], [int(c) for c in ctl]
+        if not k or len(qubits) != k:
+            raise ValueError(f'apply_matrix: a {np.shape(op)} operator for {len(qubits)} qubits (want 2^k x 2^k, 1 <= k <= 6)')
+        every = qubits + ctl
+        if any(q < 0 or q >= self._nbits for q in every):
+            raise ValueError(f'apply_matrix: qubits {every} out of range for {self._nbits} qubits')
+        if len(set(every)) != len(every):
+            raise ValueError(f'apply_matrix: a qubit appears twice among targets {qubits} and controls {ctl}')
+        dev = self._ensure_device()
+        if not hasattr(dev, 'apply_matrix'):
+            raise NotImplementedError(f'apply_matrix: {type(dev).__name__} has no dense-matrix kernel')
+        n = self._nbits
+        mask = 0
+        for c in ctl:
+            mask |= 1 << (n - 1 - c)
+        dev.apply_matrix(np.asarray(ops.Operator(op)), [n - 1 - q for q in reversed(qubits)], mask)
+        self._gate_done()
 
     # ------------------------------------------------------------------ readers / measurement
     def maxprob(self):
