@@ -256,6 +256,23 @@ int qh_prob_bit_value(qh_handle h, int logical_bit, int value, double *p); /* ..
 int qh_scale(qh_handle h, double re, double im);              /* a *= (re + i im) */
 /* Project on logical_bit == value (zero the rest); caller renormalises with qh_scale. */
 int qh_project_bit(qh_handle h, int logical_bit, int value);
+/* Register readout (kernels_measure.hip.h).  Bits are LOGICAL (bit 0 = least significant index bit = reference qubit
+ * nbits-1); every call is per shard and runs what is queued first.
+ * out[j] = sum |a_i|^2 over the shard's indices i whose bit bits[t] equals bit t of j, for 0 <= j < 2^k.
+ * 0 <= k <= 16 (k = 0: out[0] = the shard's norm).  Bits may sit anywhere in the current layout, shard bits included
+ * (fixed per shard: every j whose shard-bit part disagrees gets 0).  Not normalised.  Bitwise reproducible for a
+ * given state and layout: one read of the state, fixed-order sums in double.
+ * Errors: QH_ERR_ARG (null, k out of range, dry handle), QH_ERR_BAD_QUBIT, QH_ERR_SAME_QUBIT.                     */
+int qh_marginal(qh_handle h, int k, const int32_t *bits, double *out);
+/* Inverse-CDF sampling: for each u[s] (ascending, 0 <= u < 1), the LOGICAL index of the first amplitude, in the
+ * engine's current physical order, at which the running sum of |a|^2 exceeds u[s] * (shard norm).  Never returns
+ * an index whose amplitude is exactly 0.  count = 0 is allowed.  At most two reads of the state + O(count).
+ * QH_ERR_ARG if u is not ascending or out of [0,1), or if the shard's norm is 0.                                  */
+int qh_sample(qh_handle h, uint64_t count, const double *u, uint64_t *logical_out);
+/* Zero every amplitude whose logical bits under `mask` differ from `value` (value & ~mask must be 0: QH_ERR_ARG); the
+ * caller renormalises with qh_scale.  Shard bits in the mask: a shard that disagrees is zeroed whole (as
+ * qh_project_bit).  Writes zeros only.  QH_ERR_BAD_QUBIT for mask bits >= nbits_global.                           */
+int qh_project_bits(qh_handle h, uint64_t mask, uint64_t value);
 
 /* ---- measurement of the engine itself ----------------------------------- */
 typedef struct {

@@ -23,6 +23,7 @@
 #include "../../include/qcc_hip.h"
 #include "kernels_gate.hip.h"
 #include "kernels_dense.hip.h"
+#include "kernels_measure.hip.h"
 #include "planner.h"
 #include "kernels_sweep.hip.h"
 
@@ -83,6 +84,8 @@ struct qh_state_s {
   hipEvent_t mat_ev[kMatSlots] = {};
   bool mat_used[kMatSlots] = {};
   unsigned mat_next = 0;
+  void *d_meas = nullptr;      // qh_marginal / qh_sample scratch (slab, chunk sums, shot lists), grown on demand
+  size_t meas_bytes = 0;
   uint64_t amp_bytes() const { return bw == 128 ? 16 : 8; }
   uint64_t local_mask() const { return nloc >= 64 ? ~0ull : ((1ull << nloc) - 1ull); }
 };
@@ -634,7 +637,7 @@ int select_device(int device) {
 extern "C" {
 
 const char *qh_last_error(void) { return g_err.c_str(); }
-int qh_version(void) { return 106; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
+int qh_version(void) { return 107; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
 
 int qh_device_count(int *count) {
   if (!count) return fail(QH_ERR_ARG, "null");
@@ -769,6 +772,7 @@ int qh_destroy(qh_handle h) {
     for (hipEvent_t e : h->mat_ev) if (e) (void)hipEventDestroy(e);
     if (h->mat_dev) (void)hipFree(h->mat_dev);
     if (h->mat_host) (void)hipHostFree(h->mat_host);
+    if (h->d_meas) (void)hipFree(h->d_meas);
     for (hipEvent_t e : h->laps) (void)hipEventDestroy(e);
     if (h->owns_mem && h->d_psi) (void)hipFree(h->d_psi);
     if (h->d_alt) (void)hipFree(h->d_alt);
@@ -1556,6 +1560,213 @@ int qh_apply_matrix(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, 
   h->stats.bytes_algorithmic += (1ull << (h->nloc - __builtin_popcountll(cm_all))) * ab * 2;
   h->stats.bytes_swept += (a.nwork << k) * ab * 2;
   return QH_OK;
+}
+
+}  // extern "C"
+
+// ---- register readout: qh_marginal, qh_sample, qh_project_bits (kernels_measure.hip.h) -------------------------------
+namespace {
+
+constexpr uint64_t kMeasBlocks = 1024;      // k_marginal_bins: blocks to aim for (four 32 KiB-LDS blocks per CU)
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int meas_scratch(qh_state_s *h, size_t bytes, char **out) {
+  if (h->meas_bytes < bytes) {
+    if (h->d_meas) HIP_TRY(hipFree(h->d_meas));
+    h->d_meas = nullptr;
+    h->meas_bytes = 0;
+    HIP_TRY(hipMalloc(&h->d_meas, bytes));
+    h->meas_bytes = bytes;
+  }
+  *out = (char *)h->d_meas;
+  return QH_OK;
+}
+
+int meas_chunk_bits(const qh_state_s *h) { return std::min(h->nloc, qh::kMeasChunkBits); }
+
+// physical -> logical of the local bits, and the logical bits the shard index holds, as they are on this shard
+qh::MeasMap meas_map(const qh_state_s *h) {
+  qh::MeasMap m{};
+  for (int b = 0; b < h->nglob; ++b) {
+    const int p = h->perm[b];
+    if (p < h->nloc) m.to[p] = (uint8_t)b;
+    else if ((h->shard >> (p - h->nloc)) & 1ull) m.shard_logical |= 1ull << b;
+  }
+  return m;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qh_marginal(qh_handle h, int k, const int32_t *bits, double *out) {
+  if (!h || !out || (k > 0 && !bits)) return fail(QH_ERR_ARG, "marginal: null handle, bits or out");
+  if (k < 0 || k > qh::kMaxMarginalBits) return fail(QH_ERR_ARG, "marginal: k = %d outside [0,%d]", k, qh::kMaxMarginalBits);
+  uint64_t seen = 0;
+  for (int t = 0; t < k; ++t) {
+    if (bits[t] < 0 || bits[t] >= h->nglob) return fail(QH_ERR_BAD_QUBIT, "marginal: bit %d out of range [0,%d)", bits[t], h->nglob);
+    if ((seen >> bits[t]) & 1ull) return fail(QH_ERR_SAME_QUBIT, "marginal: bit %d appears twice", bits[t]);
+    seen |= 1ull << bits[t];
+  }
+  if (h->dry) return fail(QH_ERR_ARG, "null/dry");
+  HIP_TRY(hipSetDevice(h->device));
+  int rc = flush_impl(h);
+  if (rc) return rc;
+  const int c = meas_chunk_bits(h);
+  qh::MarginalArgs a{};
+  qh::FoldArgs f{};
+  a.c = c;
+  std::vector<std::pair<int, int>> loc;     // (physical bit, output bit) of the register bits this shard holds locally
+  for (int t = 0; t < k; ++t) {
+    const int p = h->perm[bits[t]];
+    if (p >= h->nloc) {
+      if ((h->shard >> (p - h->nloc)) & 1ull) f.fixed |= 1ull << t;     // fixed on this shard
+    } else {
+      loc.push_back({p, t});
+    }
+  }
+  std::sort(loc.begin(), loc.end());
+  for (const auto &pt : loc) {
+    if (pt.first < c) {
+      a.inner |= 1u << pt.first;
+      f.tin[a.ki++] = (uint8_t)pt.second;
+    } else {
+      a.opos[a.ko] = (uint8_t)(pt.first - c);
+      f.tout[a.ko++] = (uint8_t)pt.second;
+    }
+  }
+  f.ki = a.ki;
+  f.ko = a.ko;
+  const uint64_t rest_chunks = 1ull << (h->nloc - c - a.ko);    // chunks per outer value
+  uint32_t bpo = 1;
+  while (bpo * 2ull <= rest_chunks && ((bpo * 2ull) << a.ko) <= kMeasBlocks) bpo *= 2;
+  a.bpo = f.bpo = bpo;
+  a.cpb = rest_chunks / bpo;
+  const uint64_t nblk = (uint64_t)bpo << a.ko;
+  const size_t slab_bytes = align256((size_t)(nblk << a.ki) * sizeof(double));
+  const size_t out_bytes = ((size_t)1 << k) * sizeof(double);
+  char *scr = nullptr;
+  if ((rc = meas_scratch(h, slab_bytes + out_bytes, &scr))) return rc;
+  double *slab = (double *)scr, *dout = (double *)(scr + slab_bytes);
+  HIP_TRY(hipMemsetAsync(dout, 0, out_bytes, h->stream));
+  if (h->bw == 128)
+    hipLaunchKernelGGL(qh::k_marginal_bins<double>, dim3((unsigned)nblk), dim3(256), 0, h->stream, (const double2 *)h->d_psi, a, slab);
+  else
+    hipLaunchKernelGGL(qh::k_marginal_bins<float>, dim3((unsigned)nblk), dim3(256), 0, h->stream, (const float2 *)h->d_psi, a, slab);
+  const uint64_t nfold = 1ull << (a.ki + a.ko);
+  hipLaunchKernelGGL(qh::k_marginal_fold, dim3((unsigned)std::min<uint64_t>((nfold + 255) / 256, kRedBlocks)), dim3(256), 0,
+                     h->stream, (const double *)slab, f, dout);
+  if ((rc = check_launch(h))) return rc;
+  HIP_TRY(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, h->stream));
+  return wait_stream(h, h->stream, "reader");
+}
+
+int qh_sample(qh_handle h, uint64_t count, const double *u, uint64_t *logical_out) {
+  if (!h || (count && (!u || !logical_out))) return fail(QH_ERR_ARG, "sample: null handle, u or out");
+  for (uint64_t s = 0; s < count; ++s) {
+    if (!(u[s] >= 0.0 && u[s] < 1.0)) return fail(QH_ERR_ARG, "sample: u[%llu] = %g outside [0,1)", (unsigned long long)s, u[s]);
+    if (s && u[s] < u[s - 1]) return fail(QH_ERR_ARG, "sample: u is not ascending at %llu", (unsigned long long)s);
+  }
+  if (h->dry) return fail(QH_ERR_ARG, "null/dry");
+  HIP_TRY(hipSetDevice(h->device));
+  int rc = flush_impl(h);
+  if (rc) return rc;
+  if (count == 0) return QH_OK;
+  const int c = meas_chunk_bits(h);
+  const uint64_t nchunks = 1ull << (h->nloc - c);
+  const uint64_t maxlist = std::min<uint64_t>(nchunks, count);
+  const size_t sums_b = align256(nchunks * 8), tgt_b = align256(count * 8), ids_b = align256(maxlist * 8),
+               first_b = align256((maxlist + 1) * 8), out_b = align256(count * 8);
+  char *scr = nullptr;
+  if ((rc = meas_scratch(h, sums_b + tgt_b + ids_b + first_b + out_b, &scr))) return rc;
+  double *d_sums = (double *)scr, *d_tgt = (double *)(scr + sums_b);
+  uint64_t *d_ids = (uint64_t *)(scr + sums_b + tgt_b), *d_first = (uint64_t *)(scr + sums_b + tgt_b + ids_b);
+  uint64_t *d_out = (uint64_t *)(scr + sums_b + tgt_b + ids_b + first_b);
+  const unsigned g1 = (unsigned)std::min<uint64_t>(nchunks, 2048);
+  if (h->bw == 128)
+    hipLaunchKernelGGL(qh::k_chunk_sums<double>, dim3(g1), dim3(256), 0, h->stream, (const double2 *)h->d_psi, c, nchunks, d_sums);
+  else
+    hipLaunchKernelGGL(qh::k_chunk_sums<float>, dim3(g1), dim3(256), 0, h->stream, (const float2 *)h->d_psi, c, nchunks, d_sums);
+  if ((rc = check_launch(h))) return rc;
+  std::vector<double> sums(nchunks);
+  HIP_TRY(hipMemcpyAsync(sums.data(), d_sums, nchunks * 8, hipMemcpyDeviceToHost, h->stream));
+  if ((rc = wait_stream(h, h->stream, "reader"))) return rc;
+  // the CDF over chunks, in physical order; every shot goes to the first chunk whose inclusive prefix exceeds u * norm
+  double total = 0.0;
+  uint64_t lastc = 0;
+  for (uint64_t q = 0; q < nchunks; ++q) {
+    total += sums[q];
+    if (sums[q] > 0.0) lastc = q;
+  }
+  if (!(total > 0.0)) return fail(QH_ERR_ARG, "sample: the shard's norm is 0");
+  std::vector<double> tgt(count);
+  std::vector<uint64_t> ids, first;
+  ids.reserve(maxlist);
+  first.reserve(maxlist + 1);
+  uint64_t j = 0;
+  double excl = 0.0, incl = sums[0];
+  for (uint64_t s = 0; s < count; ++s) {
+    const double x = u[s] * total;
+    while (j < lastc && incl <= x) {
+      excl = incl;
+      incl += sums[++j];
+    }
+    if (ids.empty() || ids.back() != j) {
+      ids.push_back(j);
+      first.push_back(s);
+    }
+    tgt[s] = std::max(0.0, x - excl);      // (at or above the chunk's sum: the kernel clamps to its last nonzero amplitude)
+  }
+  first.push_back(count);
+  const uint64_t m = ids.size();
+  HIP_TRY(hipMemcpyAsync(d_tgt, tgt.data(), count * 8, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(d_ids, ids.data(), m * 8, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(d_first, first.data(), (m + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  const qh::MeasMap mm = meas_map(h);
+  const unsigned g2 = (unsigned)std::min<uint64_t>(m, 2048);
+  if (h->bw == 128)
+    hipLaunchKernelGGL(qh::k_chunk_locate<double>, dim3(g2), dim3(256), 0, h->stream, (const double2 *)h->d_psi, c,
+                       (const uint64_t *)d_ids, (const uint64_t *)d_first, m, (const double *)d_tgt, mm, d_out);
+  else
+    hipLaunchKernelGGL(qh::k_chunk_locate<float>, dim3(g2), dim3(256), 0, h->stream, (const float2 *)h->d_psi, c,
+                       (const uint64_t *)d_ids, (const uint64_t *)d_first, m, (const double *)d_tgt, mm, d_out);
+  if ((rc = check_launch(h))) return rc;
+  HIP_TRY(hipMemcpyAsync(logical_out, d_out, count * 8, hipMemcpyDeviceToHost, h->stream));
+  return wait_stream(h, h->stream, "reader");
+}
+
+int qh_project_bits(qh_handle h, uint64_t mask, uint64_t value) {
+  if (!h) return fail(QH_ERR_ARG, "project_bits: null handle");
+  if (value & ~mask)
+    return fail(QH_ERR_ARG, "project_bits: value 0x%llx has bits outside mask 0x%llx", (unsigned long long)value, (unsigned long long)mask);
+  if (h->nglob < 64 && (mask >> h->nglob))
+    return fail(QH_ERR_BAD_QUBIT, "project_bits: mask 0x%llx has bits >= %d", (unsigned long long)mask, h->nglob);
+  if (h->dry) return fail(QH_ERR_ARG, "null/dry");
+  HIP_TRY(hipSetDevice(h->device));
+  int rc = flush_impl(h);
+  if (rc) return rc;
+  uint64_t pm = 0, pw = 0;
+  bool disagree = false;
+  for (int b = 0; b < h->nglob; ++b) {
+    if (!((mask >> b) & 1ull)) continue;
+    const int p = h->perm[b];
+    const uint64_t v = (value >> b) & 1ull;
+    if (p >= h->nloc) disagree |= ((h->shard >> (p - h->nloc)) & 1ull) != v;
+    else { pm |= 1ull << p; pw |= v << p; }
+  }
+  if (disagree) {      // (as qh_project_bit: a shard whose index contradicts the value is zeroed whole)
+    HIP_TRY(hipMemsetAsync(h->d_psi, 0, (1ull << h->nloc) * h->amp_bytes(), h->stream));
+    return QH_OK;
+  }
+  if (!pm) return QH_OK;
+  const uint64_t n = 1ull << h->nloc;
+  const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 20);
+  if (h->bw == 128)
+    hipLaunchKernelGGL(qh::k_project_mask<double>, dim3(grid), dim3(256), 0, h->stream, (double2 *)h->d_psi, n, pm, pw);
+  else
+    hipLaunchKernelGGL(qh::k_project_mask<float>, dim3(grid), dim3(256), 0, h->stream, (float2 *)h->d_psi, n, pm, pw);
+  return check_launch(h);
 }
 
 int qh_get_stats(qh_handle h, qh_stats *out) {

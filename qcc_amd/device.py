@@ -14,6 +14,7 @@ from qcc_amd import gates as _gates
 from qcc_amd import native
 
 _dp = ctypes.POINTER(ctypes.c_double)
+MAX_MARGINAL_BITS = 16     # qh_marginal: k <= 16
 
 
 def _g8(gate):
@@ -312,6 +313,29 @@ class DeviceState:
 
   def project_bit(self, logical_bit, value):
     native.check(self.lib.qh_project_bit(self.h, int(logical_bit), int(value)))
+
+  def marginal(self, bits):
+    """(2^k,) float64: entry j = sum |a|^2 over the indices whose LOGICAL bit bits[t] equals bit t of j (qh_marginal;
+    0 <= k <= 16, not normalised, bitwise reproducible)."""
+    b = np.ascontiguousarray([int(x) for x in bits], dtype=np.int32)
+    if b.size > MAX_MARGINAL_BITS:      # (before sizing the 2^k result: the engine would refuse it anyway)
+      raise native.QhError(native.QH_ERR_ARG, f'marginal: k = {b.size} outside [0,{MAX_MARGINAL_BITS}]')
+    out = np.zeros(1 << b.size, dtype=np.float64)
+    native.check(self.lib.qh_marginal(self.h, int(b.size), b.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                      out.ctypes.data_as(_dp)))
+    return out
+
+  def sample(self, u):
+    """LOGICAL indices drawn by inverse CDF for the ascending uniforms u in [0, 1) (qh_sample)."""
+    u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+    out = np.zeros(u.size, dtype=np.uint64)
+    native.check(self.lib.qh_sample(self.h, int(u.size), u.ctypes.data_as(_dp),
+                                    out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+    return out
+
+  def project_bits(self, mask, value):
+    """Zero every amplitude whose LOGICAL bits under mask differ from value (qh_project_bits); renormalise with scale."""
+    native.check(self.lib.qh_project_bits(self.h, int(mask), int(value)))
 
   def phys_to_logical(self, i):
     o = ctypes.c_uint64()

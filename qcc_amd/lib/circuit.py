@@ -75,6 +75,7 @@ def _u1_operator(value):
 
 
 _DENSE_MAX_BITS = 6        # qh_apply_matrix: dense operators on up to 6 qubits run on the device
+_MARGINAL_MAX_BITS = 16    # qh_marginal: registers of up to 16 qubits (2^16 probabilities)
 
 
 def _dense_bits(op):
@@ -640,6 +641,110 @@ class qc:
         if self._nbits <= _MEASURE_SNAPSHOT_BITS or self._aliased():
             return prob, self.psi
         return prob, _LazyPsi(self)
+
+    # Register readout (extensions: the reference loops psi.prob(*bits) over basis states).  qubits[0] is the most
+    # significant bit of a register value (np.kron order, helper.bits2val); the engine takes LOGICAL bits (qubit q is
+    # bit n-1-q).  Devices without marginal / sample / project_bits read qc.psi on the host instead.
+    def _register(self, qubits, what):
+        n = self._nbits
+        qubits = list(range(n)) if qubits is None else [int(q) for q in qubits]
+        if any(q < 0 or q >= n for q in qubits):
+            raise ValueError(f'{what}: qubits {qubits} out of range for {n} qubits')
+        if len(set(qubits)) != len(qubits):
+            raise ValueError(f'{what}: a qubit appears twice in {qubits}')
+        return qubits
+
+    def _register_values(self, idx, qubits):
+        """Register values (uint64) of full basis indices idx."""
+        n, k = self._nbits, len(qubits)
+        idx = np.asarray(idx, dtype=np.uint64)
+        val = np.zeros(idx.shape, dtype=np.uint64)
+        for t, q in enumerate(qubits):
+            val |= ((idx >> np.uint64(n - 1 - q)) & np.uint64(1)) << np.uint64(k - 1 - t)
+        return val
+
+    def probabilities(self, qubits):
+        """(2^k,) float64: P(register == v) for every value v of the qubits `qubits` (k <= 16), one read of the state
+        on the device (qh_marginal).  Not renormalised."""
+        qubits = self._register(qubits, 'probabilities')
+        n, k = self._nbits, len(qubits)
+        if k > _MARGINAL_MAX_BITS:
+            raise ValueError(f'probabilities: {k} qubits (at most {_MARGINAL_MAX_BITS})')
+        dev = self._ensure_device()
+        if hasattr(dev, 'marginal'):
+            return np.asarray(dev.marginal([n - 1 - q for q in reversed(qubits)]), dtype=np.float64)
+        p = np.abs(np.asarray(self.psi, dtype=np.complex128).reshape(-1)) ** 2
+        out = np.zeros(1 << k, dtype=np.float64)
+        np.add.at(out, self._register_values(np.arange(p.size, dtype=np.uint64), qubits).astype(np.int64), p)
+        return out
+
+    @staticmethod
+    def _uniforms(count, seed, dev):
+        """`count` uniforms in [0, 1): np.random.default_rng(seed), or the legacy global np.random stream for seed=None.
+        A device that spans several processes (ShardedDevice) hands every rank rank 0's draws."""
+        u = np.random.random_sample(count) if seed is None else np.random.default_rng(seed).random(count)
+        if hasattr(dev, 'from_rank0'):
+            u = np.asarray(dev.from_rank0(u), dtype=np.float64)
+        return u
+
+    def sample(self, shots, qubits=None, seed=None):
+        """`shots` register values (uint64, in draw order) of the qubits `qubits` (None: all), sampled by inverse CDF on
+        the device (qh_sample).  The uniforms come from np.random.default_rng(seed); seed=None draws from the legacy
+        global np.random stream, so np.random.seed(...) reproduces a run."""
+        qubits = self._register(qubits, 'sample')
+        shots = int(shots)
+        if shots < 0:
+            raise ValueError(f'sample: {shots} shots')
+        dev = self._ensure_device()
+        u = self._uniforms(shots, seed, dev)
+        order = np.argsort(u, kind='stable')
+        if hasattr(dev, 'sample'):
+            idx = np.asarray(dev.sample(u[order]), dtype=np.uint64)
+        else:
+            p = np.abs(np.asarray(self.psi, dtype=np.complex128).reshape(-1)) ** 2
+            cdf = np.cumsum(p)
+            if not cdf[-1] > 0:
+                raise ValueError('sample: the state has norm 0')
+            idx = np.minimum(np.searchsorted(cdf, u[order] * cdf[-1], side='right'), np.flatnonzero(p)[-1]).astype(np.uint64)
+        out = np.empty(shots, dtype=np.uint64)
+        out[order] = self._register_values(idx, qubits)
+        return out
+
+    def measure(self, qubits, *, seed=None, collapse=True):
+        """One shot of the register `qubits` (k <= 16): (value, probability).  One marginal (qh_marginal: one read of the
+        state) gives the register's distribution; the value is its inverse CDF, in register-value order, at one uniform
+        drawn as in sample().  With collapse the state is projected on the outcome and renormalised in place
+        (qh_project_bits + qh_scale)."""
+        qubits = self._register(qubits, 'measure')
+        n, k = self._nbits, len(qubits)
+        if k > _MARGINAL_MAX_BITS:
+            raise ValueError(f'measure: {k} qubits (at most {_MARGINAL_MAX_BITS})')
+        probs = self.probabilities(qubits)
+        nz = np.flatnonzero(probs > 0)
+        if not nz.size:
+            raise ValueError('measure: the state has norm 0')
+        cdf = np.cumsum(probs)
+        u = float(self._uniforms(1, seed, self._ensure_device())[0])
+        value = int(min(int(np.searchsorted(cdf, u * cdf[-1], side='right')), int(nz[-1])))
+        if probs[value] == 0:                    # (rounding at a boundary: the next value that has weight)
+            value = int(nz[np.searchsorted(nz, value)])
+        prob = float(probs[value])
+        if collapse:
+            assert prob > 1e-20, 'Measurement collapses to 0.0.'
+            dev = self._ensure_device()
+            mask = vbits = 0
+            for t, q in enumerate(qubits):
+                mask |= 1 << (n - 1 - q)
+                if (value >> (k - 1 - t)) & 1:
+                    vbits |= 1 << (n - 1 - q)
+            if hasattr(dev, 'project_bits'):
+                dev.project_bits(mask, vbits)
+            else:
+                for q in qubits:
+                    dev.project_bit(n - 1 - q, (vbits >> (n - 1 - q)) & 1)
+            dev.scale(1.0 / math.sqrt(prob))
+            self._gate_done()
+        return value, prob
 
     def pauli_expectation(self, idx):
         p0, _ = self.measure_bit(idx, 0, False)

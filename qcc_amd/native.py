@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB_PATH = os.environ.get('QCC_HIP_LIB') or os.path.join(PKG, 'libqcc_hip.so')  # env: A/B builds only
 SOURCES = [os.path.join(PKG, 'csrc', f) for f in
-           ('engine.hip', 'kernels_gate.hip.h', 'kernels_dense.hip.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h',
+           ('engine.hip', 'kernels_gate.hip.h', 'kernels_dense.hip.h', 'kernels_measure.hip.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h',
             'sweep_island_rb2.inc', 'sweep_island_rb3.inc', 'sweep_island_rb4.inc',
             'sweep_island_rb5.inc', 'sweep_island_f32_rb2.inc', 'sweep_island_f32_rb3.inc',
             'sweep_island_f32_rb4.inc', 'sweep_island_f32_rb5.inc', 'sweep_island_f32_rb6.inc', 'sweep_handlers.inc',
@@ -77,6 +77,9 @@ SIGNATURES = {
     'qh_prob_bit_value': (_i32, [_vp, _i32, _i32, _dp]),
     'qh_scale': (_i32, [_vp, ctypes.c_double, ctypes.c_double]),
     'qh_project_bit': (_i32, [_vp, _i32, _i32]),
+    'qh_marginal': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _dp]),
+    'qh_sample': (_i32, [_vp, _u64, _dp, ctypes.POINTER(ctypes.c_uint64)]),
+    'qh_project_bits': (_i32, [_vp, _u64, _u64]),
     'qh_get_stats': (_i32, [_vp, ctypes.POINTER(QhStats)]),
     'qh_reset_stats': (_i32, [_vp]),
     'qh_timer_begin': (_i32, [_vp]),

@@ -709,6 +709,64 @@ class ShardedDevice:
   def scale(self, z):
     self.st.eng.scale(z)
 
+  def _all_sum_array(self, values):
+    """Sum over ranks of a float64 array (the engine's all-reduce takes at most 1024 doubles a call)."""
+    st = self.st
+    a = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    if st.exchange_path == 'rccl':
+      return np.concatenate([st.eng.allreduce_sum(a[i:i + 1024]) for i in range(0, a.size, 1024)]) if a.size else a
+    t = st.torch.from_numpy(a.copy())
+    if st._red_device() != 'cpu':
+      t = t.to(st._red_device())
+    st.dist.all_reduce(t)
+    return t.cpu().numpy()
+
+  def marginal(self, bits):
+    """(2^k,) marginal of the LOGICAL bits (DeviceState.marginal), summed over the ranks: each shard's engine resolves
+    the register bits its shard index holds."""
+    st = self.st
+    return self._all_sum_array(st.eng.marginal([st.perm[int(b)] for b in bits]))
+
+  def from_rank0(self, values):
+    """Rank 0's float64 array on every rank (its values plus zeros from the others: exact).  Host-side random draws
+    (qc.sample / qc.measure) go through here, so that ranks whose NumPy streams differ still agree on one outcome."""
+    a = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    return self._all_sum_array(a if self.st.rank == 0 else np.zeros_like(a))
+
+  def sample(self, u):
+    """LOGICAL indices for the ascending uniforms u (DeviceState.sample), the same on every rank: rank 0's u are used
+    everywhere.  The ranks' norms split [0, 1) in rank order; each rank samples the uniforms that fall in its range,
+    rescaled to [0, 1)."""
+    st = self.st
+    u = self.from_rank0(u)
+    if u.size and not (np.all(u >= 0.0) and np.all(u < 1.0) and np.all(np.diff(u) >= 0.0)):
+      raise ValueError('sample: u must be ascending and in [0, 1)')           # (every rank sees the same u: all raise)
+    norms = np.zeros(st.world)
+    norms[st.rank] = st.eng.marginal([])[0]
+    norms = self._all_sum_array(norms)
+    edges = np.concatenate([[0.0], np.cumsum(norms)])
+    total = edges[-1]
+    if not total > 0:
+      raise ValueError('sample: the state has norm 0')
+    x = u * total
+    owner = np.searchsorted(edges[1:], x, side='right')         # first rank whose range ends above x
+    owner = np.minimum(owner, int(np.flatnonzero(norms > 0)[-1]))  # (x rounded up to the total: the last rank with weight)
+    mine = np.flatnonzero(owner == st.rank)
+    out = np.zeros(u.size, dtype=np.float64)
+    if mine.size:
+      ul = np.clip((x[mine] - edges[st.rank]) / norms[st.rank], 0.0, np.nextafter(1.0, 0.0))
+      got = np.asarray(st.eng.sample(ul), dtype=np.uint64)     # the engine's logical = this layer's physical index
+      lo = np.zeros_like(got)
+      for b, p in enumerate(st.perm):
+        lo |= ((got >> np.uint64(p)) & np.uint64(1)) << np.uint64(b)
+      out[mine] = lo.astype(np.float64)                         # (indices < 2^53: exact in a double)
+    return self._all_sum_array(out).astype(np.uint64)
+
+  def project_bits(self, mask, value):
+    st = self.st
+    m, v = int(mask), int(value)
+    st.eng.project_bits(st.logical_to_phys(m), st.logical_to_phys(v))
+
   def stats(self):
     return self.st.stats()
 
