@@ -273,6 +273,14 @@ int qh_sample(qh_handle h, uint64_t count, const double *u, uint64_t *logical_ou
  * caller renormalises with qh_scale.  Shard bits in the mask: a shard that disagrees is zeroed whole (as
  * qh_project_bit).  Writes zeros only.  QH_ERR_BAD_QUBIT for mask bits >= nbits_global.                           */
 int qh_project_bits(qh_handle h, uint64_t mask, uint64_t value);
+/* Pauli-string expectations (kernels_expect.hip.h).  Term t is two masks over LOGICAL bits: xmask (X or Y on the bit) and
+ * zmask (Z or Y).  out[t] = Re sum over the shard's i of conj(a_i) (P_t a)_i: per shard, not normalised (x = z = 0 gives
+ * the shard's norm).  Runs what is queued first; reads only (state, bit map and relayout mode are as before).  Terms that
+ * share an x mask share a read of the state, 16 at a time: qh_stats.kernels_launched grows by the number of reads,
+ * sum over distinct x masks of ceil(terms / 16).  A z bit held by the shard index is a sign fixed per shard; an x bit
+ * held by the shard index is QH_ERR_NONLOCAL (nothing computed, out untouched).  Bitwise reproducible for a given state
+ * and layout.  nterms = 0 is allowed.  Errors: QH_ERR_ARG (null, dry handle), QH_ERR_BAD_QUBIT (mask bits >= nbits_global). */
+int qh_expect_pauli(qh_handle h, uint64_t nterms, const uint64_t *xmask, const uint64_t *zmask, double *out);
 
 /* ---- measurement of the engine itself ----------------------------------- */
 typedef struct {

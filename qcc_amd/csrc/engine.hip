@@ -24,6 +24,7 @@
 #include "kernels_gate.hip.h"
 #include "kernels_dense.hip.h"
 #include "kernels_measure.hip.h"
+#include "kernels_expect.hip.h"
 #include "planner.h"
 #include "kernels_sweep.hip.h"
 
@@ -637,7 +638,7 @@ int select_device(int device) {
 extern "C" {
 
 const char *qh_last_error(void) { return g_err.c_str(); }
-int qh_version(void) { return 107; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
+int qh_version(void) { return 108; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
 
 int qh_device_count(int *count) {
   if (!count) return fail(QH_ERR_ARG, "null");
@@ -1767,6 +1768,111 @@ int qh_project_bits(qh_handle h, uint64_t mask, uint64_t value) {
   else
     hipLaunchKernelGGL(qh::k_project_mask<float>, dim3(grid), dim3(256), 0, h->stream, (float2 *)h->d_psi, n, pm, pw);
   return check_launch(h);
+}
+
+}  // extern "C"
+
+// ---- Pauli-string expectations: qh_expect_pauli (kernels_expect.hip.h) -----------------------------------------------
+namespace {
+
+constexpr uint64_t kExpectBlocks = 4096;    // k_expect_batch: blocks at most (one slab row each)
+
+template <typename R, int TT>
+void launch_expect(qh_state_s *h, bool pair, unsigned nblk, const qh::ExpectArgs &a, double *slab) {
+  using A = typename qh::AmpT<R>::type;
+  if (pair)
+    hipLaunchKernelGGL((qh::k_expect_batch<R, TT, true>), dim3(nblk), dim3(256), 0, h->stream, (const A *)h->d_psi, a, slab);
+  else
+    hipLaunchKernelGGL((qh::k_expect_batch<R, TT, false>), dim3(nblk), dim3(256), 0, h->stream, (const A *)h->d_psi, a, slab);
+}
+
+}  // namespace
+
+extern "C" {
+
+int qh_expect_pauli(qh_handle h, uint64_t nterms, const uint64_t *xmask, const uint64_t *zmask, double *out) {
+  if (!h || (nterms && (!xmask || !zmask || !out))) return fail(QH_ERR_ARG, "expect_pauli: null handle, masks or out");
+  if (h->nglob < 64)
+    for (uint64_t t = 0; t < nterms; ++t)
+      if ((xmask[t] | zmask[t]) >> h->nglob)
+        return fail(QH_ERR_BAD_QUBIT, "expect_pauli: term %llu (x 0x%llx, z 0x%llx) has bits >= %d", (unsigned long long)t,
+                    (unsigned long long)xmask[t], (unsigned long long)zmask[t], h->nglob);
+  if (h->dry) return fail(QH_ERR_ARG, "null/dry");
+  HIP_TRY(hipSetDevice(h->device));
+  int rc = flush_impl(h);
+  if (rc) return rc;
+  if (nterms == 0) return QH_OK;
+  // masks through the bit map: local bits stay masks, a z bit the shard index holds is a sign fixed on this shard
+  struct Term { uint64_t px, pz, idx; uint32_t neg, ny; };
+  std::vector<Term> terms(nterms);
+  for (uint64_t t = 0; t < nterms; ++t) {
+    Term &tm = terms[t];
+    tm = Term{0, 0, t, 0, (uint32_t)__builtin_popcountll(xmask[t] & zmask[t]) & 3u};
+    for (int b = 0; b < h->nglob; ++b) {
+      const int p = h->perm[b];
+      if ((xmask[t] >> b) & 1ull) {
+        if (p >= h->nloc)
+          return fail(QH_ERR_NONLOCAL, "expect_pauli: term %llu has X or Y on logical bit %d, held by the shard index (physical bit %d, "
+                      "local bits: %d); exchange first", (unsigned long long)t, b, p, h->nloc);
+        tm.px |= 1ull << p;
+      }
+      if ((zmask[t] >> b) & 1ull) {
+        if (p >= h->nloc) tm.neg ^= (uint32_t)((h->shard >> (p - h->nloc)) & 1ull);
+        else tm.pz |= 1ull << p;
+      }
+    }
+  }
+  // terms that share a physical x mask share a read of the state, kExpectT at a time
+  std::stable_sort(terms.begin(), terms.end(), [](const Term &l, const Term &r) { return l.px < r.px; });
+  const size_t slab_bytes = align256((size_t)kExpectBlocks * qh::kExpectT * sizeof(double));
+  char *scr = nullptr;
+  if ((rc = meas_scratch(h, slab_bytes + (size_t)nterms * sizeof(double), &scr))) return rc;
+  double *slab = (double *)scr, *dout = (double *)(scr + slab_bytes);
+  uint64_t batches = 0;
+  for (uint64_t first = 0; first < nterms;) {
+    uint64_t cnt = 1;
+    while (first + cnt < nterms && cnt < (uint64_t)qh::kExpectT && terms[first + cnt].px == terms[first].px) ++cnt;
+    const uint64_t px = terms[first].px;
+    const bool pair = (px >> 6) != 0;
+    qh::ExpectArgs a{};
+    a.x = px;
+    a.tb = pair ? 63 - __builtin_clzll(px) : 0;
+    const int per_bits = pair ? 3 : 4, nom = 8 + per_bits, wbits = pair ? h->nloc - 1 : h->nloc;
+    a.cw = std::min(nom, wbits);
+    const uint64_t nchunks = 1ull << (wbits - a.cw), nblk = std::min(nchunks, kExpectBlocks);
+    a.cpb = (uint32_t)(nchunks / nblk);
+    for (uint64_t k = 0; k < cnt; ++k) {
+      const Term &tm = terms[first + k];
+      uint64_t z = tm.pz;     // in work-index bits: bit tb (0 in the i of every pair) squeezed out
+      if (pair) z = (z & ((1ull << a.tb) - 1ull)) | ((z >> (a.tb + 1)) << a.tb);
+      a.zt[k] = (uint8_t)(z & 255ull);
+      const uint32_t zu = (uint32_t)(z >> 8) & ((1u << per_bits) - 1u);
+      for (uint32_t u = 0; u < (1u << per_bits); ++u) a.zu[k] |= (uint16_t)((__builtin_popcount(u & zu) & 1) << u);
+      a.zc[k] = z >> nom;
+      const uint32_t one = (((tm.ny >> 1) ^ tm.neg) & 1u) ? 0xBFF00000u : 0x3FF00000u;     // nY mod 4: +Re, +Im, -Re, -Im
+      if (tm.ny & 1u) a.cim[k] = one; else a.cre[k] = one;
+    }
+    const int tt = cnt <= 4 ? 4 : qh::kExpectT;
+    if (h->bw == 128) {
+      if (tt == 4) launch_expect<double, 4>(h, pair, (unsigned)nblk, a, slab);
+      else launch_expect<double, qh::kExpectT>(h, pair, (unsigned)nblk, a, slab);
+    } else {
+      if (tt == 4) launch_expect<float, 4>(h, pair, (unsigned)nblk, a, slab);
+      else launch_expect<float, qh::kExpectT>(h, pair, (unsigned)nblk, a, slab);
+    }
+    hipLaunchKernelGGL(qh::k_expect_fold, dim3((unsigned)cnt), dim3(256), 0, h->stream, (const double *)slab, (uint32_t)nblk, tt,
+                       pair ? 2.0 : 1.0, dout + first);
+    if ((rc = check_launch(h))) return rc;
+    first += cnt;
+    ++batches;
+  }
+  std::vector<double> vals(nterms);
+  HIP_TRY(hipMemcpyAsync(vals.data(), dout, (size_t)nterms * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if ((rc = wait_stream(h, h->stream, "reader"))) return rc;
+  for (uint64_t k = 0; k < nterms; ++k) out[terms[k].idx] = vals[k];
+  h->stats.kernels_launched += batches;      // reads of the state: one per batch
+  h->stats.bytes_swept += batches * ((1ull << h->nloc) * h->amp_bytes());
+  return QH_OK;
 }
 
 int qh_get_stats(qh_handle h, qh_stats *out) {

@@ -333,6 +333,19 @@ class DeviceState:
                                     out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
     return out
 
+  def expect_pauli(self, xmasks, zmasks):
+    """(T,) float64: Re <psi|P_t|psi> of the Pauli strings given as LOGICAL bit masks (x: X or Y on the bit, z: Z or Y),
+    summed over this shard, not normalised (qh_expect_pauli: strings that share an x mask share a read of the state)."""
+    x = np.ascontiguousarray([int(v) for v in xmasks], dtype=np.uint64)
+    z = np.ascontiguousarray([int(v) for v in zmasks], dtype=np.uint64)
+    if x.size != z.size:
+      raise ValueError(f'expect_pauli: {x.size} x masks, {z.size} z masks')
+    out = np.zeros(x.size, dtype=np.float64)
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    native.check(self.lib.qh_expect_pauli(self.h, int(x.size), x.ctypes.data_as(u64p), z.ctypes.data_as(u64p),
+                                          out.ctypes.data_as(_dp)))
+    return out
+
   def project_bits(self, mask, value):
     """Zero every amplitude whose LOGICAL bits under mask differ from value (qh_project_bits); renormalise with scale."""
     native.check(self.lib.qh_project_bits(self.h, int(mask), int(value)))

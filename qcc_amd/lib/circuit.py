@@ -746,6 +746,68 @@ class qc:
             self._gate_done()
         return value, prob
 
+    def _pauli_masks(self, paulis):
+        """(x, z) masks over LOGICAL bits of one Pauli string: a str over IXYZ of length nbits (character q = qubit q)
+        or a dict {qubit: 'X' | 'Y' | 'Z' | 'I'}."""
+        n = self._nbits
+        if isinstance(paulis, str):
+            if len(paulis) != n:
+                raise ValueError(f'expectation: string {paulis!r} has {len(paulis)} letters for {n} qubits')
+            items = enumerate(paulis)
+        elif isinstance(paulis, dict):
+            items = paulis.items()
+        else:
+            raise ValueError(f'expectation: a Pauli string is a str or a dict, not {type(paulis).__name__}')
+        x = z = 0
+        for q, p in items:
+            if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or q < 0 or q >= n:
+                raise ValueError(f'expectation: qubit {q!r} out of range for {n} qubits')
+            if not isinstance(p, str) or p.upper() not in ('I', 'X', 'Y', 'Z'):
+                raise ValueError(f'expectation: {p!r} on qubit {q} is not one of I, X, Y, Z')
+            bit = 1 << (n - 1 - int(q))
+            if p.upper() in 'XY':
+                x |= bit
+            if p.upper() in 'ZY':
+                z |= bit
+        return x, z
+
+    def expectation(self, terms, *, per_term=False):
+        """sum_t c_t <psi|P_t|psi> for terms = [(c_t, paulis_t), ...] (paulis: see _pauli_masks), on the device
+        (qh_expect_pauli: strings with the same X/Y positions share one read of the state).  Real coefficients give a
+        float, complex ones a complex; per_term=True returns the float64 array of the <P_t> instead.  Not divided by
+        the norm: like probabilities, it reports what the state holds."""
+        coeffs, xs, zs = [], [], []
+        for term in terms:
+            try:
+                c, paulis = term
+            except (TypeError, ValueError):
+                raise ValueError(f'expectation: term {term!r} is not a (coefficient, paulis) pair') from None
+            x, z = self._pauli_masks(paulis)
+            coeffs.append(complex(c))
+            xs.append(x)
+            zs.append(z)
+        dev = self._ensure_device()
+        if not xs:
+            vals = np.zeros(0, dtype=np.float64)
+        elif hasattr(dev, 'expect_pauli'):
+            vals = np.asarray(dev.expect_pauli(xs, zs), dtype=np.float64)
+        else:
+            a = np.asarray(self.psi, dtype=np.complex128).reshape(-1)
+            idx = np.arange(a.size, dtype=np.uint64)
+            vals = np.zeros(len(xs), dtype=np.float64)
+            for t, (x, z) in enumerate(zip(xs, zs)):
+                par = np.zeros(a.size, dtype=np.uint64)
+                for b in range(self._nbits):
+                    if (z >> b) & 1:
+                        par ^= (idx >> np.uint64(b)) & np.uint64(1)
+                s = np.vdot(a, (1.0 - 2.0 * par.astype(np.float64)) * a[idx ^ np.uint64(x)])
+                vals[t] = ((-1j) ** (bin(x & z).count('1') % 4) * s).real
+        if per_term:
+            return vals
+        c = np.asarray(coeffs, dtype=np.complex128)
+        total = complex(np.dot(c, vals)) if len(coeffs) else 0j
+        return total if np.any(c.imag != 0) else float(total.real)
+
     def pauli_expectation(self, idx):
         p0, _ = self.measure_bit(idx, 0, False)
         return p0 - (1 - p0)

@@ -727,6 +727,52 @@ class ShardedDevice:
     st = self.st
     return self._all_sum_array(st.eng.marginal([st.perm[int(b)] for b in bits]))
 
+  def _local_group(self, xphys):
+    """Base of g consecutive local bits that hold no bit of the physical mask xphys (the all-to-all's candidates, top
+    group first), or None."""
+    st = self.st
+    g, nloc = st.g, st.nloc
+    for b in range(nloc - g, min(st.min_evict_bit, nloc - g) - 1, -g):
+      if not (xphys >> b) & ((1 << g) - 1):
+        return b
+    return None
+
+  def expect_pauli(self, xmasks, zmasks):
+    """(T,) float64: <psi|P_t|psi> of Pauli strings given as LOGICAL bit masks (DeviceState.expect_pauli), summed over
+    the ranks; collective, the same floats on every rank.  Z on a shard bit is a sign per shard (the engine's).  Strings
+    whose x mask is local are evaluated first, in one engine call; then, as long as strings remain, the shard bits are
+    exchanged with a group of local bits that the first remaining string leaves alone, and the round repeats.  Every
+    decision is taken from the masks and the bit map alone: all ranks take the same branch."""
+    st = self.st
+    xs, zs = [int(v) for v in xmasks], [int(v) for v in zmasks]
+    if len(xs) != len(zs):
+      raise ValueError(f'expect_pauli: {len(xs)} x masks, {len(zs)} z masks')
+    if any((x | z) >> st.nbits for x, z in zip(xs, zs)):
+      raise ValueError(f'expect_pauli: a mask has bits at or above {st.nbits}')
+    vals = np.zeros(len(xs), dtype=np.float64)
+    todo = list(range(len(xs)))
+    while todo:
+      px = {t: st.logical_to_phys(xs[t]) for t in todo}
+      now = [t for t in todo if not px[t] >> st.nloc]
+      if now:
+        vals[now] = st.eng.expect_pauli([px[t] for t in now], [st.logical_to_phys(zs[t]) for t in now])
+        todo = [t for t in todo if px[t] >> st.nloc]
+        continue
+      t = todo[0]
+      shard_bits = [b for b in range(st.nloc, st.nbits) if (px[t] >> b) & 1]
+      if st.exchange_mode == 'alltoall':
+        base = self._local_group(px[t])
+        if base is None:
+          raise NotImplementedError(f'expect_pauli: string x=0x{xs[t]:x} z=0x{zs[t]:x} has X or Y on shard bits and on every '
+                                    f'group of {st.g} local bits that could be exchanged for them')
+        st._exchange(shard_bits[0], base)                # pylint: disable=protected-access
+      else:
+        if len(shard_bits) > 1 or (px[t] >> (st.nloc - 1)) & 1:
+          raise NotImplementedError(f'expect_pauli: string x=0x{xs[t]:x} z=0x{zs[t]:x} needs more than one pairwise exchange '
+                                    f'(X or Y on {len(shard_bits)} shard bits, or on the local bit that gives way)')
+        st._exchange(shard_bits[0])                      # pylint: disable=protected-access
+    return self._all_sum_array(vals)
+
   def from_rank0(self, values):
     """Rank 0's float64 array on every rank (its values plus zeros from the others: exact).  Host-side random draws
     (qc.sample / qc.measure) go through here, so that ranks whose NumPy streams differ still agree on one outcome."""
