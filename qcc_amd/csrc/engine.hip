@@ -93,6 +93,41 @@ struct qh_state_s {
 
 namespace {
 
+// The one choice of the amplitude width: f(double{}) on complex128 handles, f(float{}) on complex64 ones.  Launch sites are
+// generic lambdas that take R = decltype(x) (and A = qh::AmpT<R>::type, i.e. double2 / float2) from their argument x.
+template <typename F> decltype(auto) with_real(const qh_state_s *h, F &&f) {
+  if (h->bw == 128) return f(double{});
+  return f(float{});
+}
+
+// Logical -> physical through the handle's bit map, on whole masks, and back.
+uint64_t to_phys(const qh_state_s *h, uint64_t logical) {
+  uint64_t p = 0;
+  for (int b = 0; b < h->nglob; ++b)
+    if ((logical >> b) & 1ull) p |= 1ull << h->perm[b];
+  return p;
+}
+uint64_t to_logical(const qh_state_s *h, uint64_t phys) {
+  uint64_t l = 0;
+  for (int b = 0; b < h->nglob; ++b)
+    if ((phys >> h->perm[b]) & 1ull) l |= 1ull << b;
+  return l;
+}
+// A physical mask split at nloc: `local` are index bits of this shard's amplitudes, `held` are bits of the shard index
+// (h->shard & held = the ones among them on this shard).  Host arithmetic only: valid on dry handles.
+struct Placed { uint64_t local, held; };
+Placed place(const qh_state_s *h, uint64_t phys) { return {phys & h->local_mask(), phys >> h->nloc}; }
+Placed place_bit(const qh_state_s *h, int logical_bit) { return place(h, 1ull << h->perm[logical_bit]); }
+
+unsigned grid_for(uint64_t n, uint64_t cap) { return (unsigned)std::min<uint64_t>((n + 255) / 256, cap); }   // 256-thread blocks
+
+// one kernel over the state: amplitudes the gate had to touch / amplitudes the kernel did, each read and written
+void count_kernel(qh_state_s *h, uint64_t algorithmic_amps, uint64_t swept_amps) {
+  h->stats.kernels_launched++;
+  h->stats.bytes_algorithmic += algorithmic_amps * h->amp_bytes() * 2;
+  h->stats.bytes_swept += swept_amps * h->amp_bytes() * 2;
+}
+
 template <typename R> qh::Gate2<R> to_gate(const double g[8]) {
   qh::Gate2<R> o;
   o.g0r = (R)g[0]; o.g0i = (R)g[1]; o.g1r = (R)g[2]; o.g1i = (R)g[3];
@@ -199,12 +234,12 @@ void launch_diag(qh_state_s *h, uint64_t nwork, int sel, const qh::BitIns &ins, 
 
 // One gate, physical bit positions, one kernel.  Returns QH_* status.
 int launch_single(qh_state_s *h, const qh::GateRec &r) {
-  const uint64_t cm_hi = r.ctl_mask >> h->nloc;
-  if ((h->shard & cm_hi) != cm_hi) {
+  const Placed ctl = place(h, r.ctl_mask);
+  if ((h->shard & ctl.held) != ctl.held) {
     h->stats.gates_noop++;
     return QH_OK;
   }
-  const uint64_t cm_all = r.ctl_mask & h->local_mask();
+  const uint64_t cm_all = ctl.local;
   // bits 0,1 are never skipped in the enumeration (same 64-byte half line): predicate
   const uint64_t kLow = (h->nloc > 2) ? 3ull : 0ull;
   uint32_t lowpred = (uint32_t)(cm_all & kLow);
@@ -214,7 +249,12 @@ int launch_single(qh_state_s *h, const qh::GateRec &r) {
   if (nc + 1 > qh::kMaxIns) return fail(QH_ERR_ARG, "too many local control bits (%d)", nc);
   const double *g = r.g;
   const bool diag = qh::is_diag(g);
-  const uint64_t ab = h->amp_bytes();
+  // a diagonal kernel: factors (f0, f1) by bit `sel` of the index (-1: f1 everywhere), `ones` inserted as 1s
+  auto diag_kernel = [&](uint64_t nwork, int sel, uint64_t ones, double f0r, double f0i, double f1r, double f1i) {
+    if (h->dry) return;
+    const qh::BitIns ins = make_ins(ones, -1);
+    with_real(h, [&](auto x) { launch_diag<decltype(x)>(h, nwork, sel, ins, f0r, f0i, f1r, f1i, lowpred); });
+  };
   if (r.tgt >= h->nloc) {
     if (!diag)
       return fail(QH_ERR_NONLOCAL,
@@ -228,14 +268,8 @@ int launch_single(qh_state_s *h, const qh::GateRec &r) {
       return QH_OK;
     }
     const uint64_t nwork = 1ull << (h->nloc - nc);
-    if (!h->dry) {
-      const qh::BitIns ins = make_ins(cm, -1);
-      if (h->bw == 128) launch_diag<double>(h, nwork, -1, ins, 1, 0, fr, fi, lowpred);
-      else launch_diag<float>(h, nwork, -1, ins, 1, 0, fr, fi, lowpred);
-    }
-    h->stats.kernels_launched++;
-    h->stats.bytes_algorithmic += (1ull << (h->nloc - nc_all)) * ab * 2;
-    h->stats.bytes_swept += nwork * ab * 2;
+    diag_kernel(nwork, -1, cm, 1, 0, fr, fi);
+    count_kernel(h, 1ull << (h->nloc - nc_all), nwork);
     return QH_OK;
   }
   if (diag) {
@@ -248,35 +282,21 @@ int launch_single(qh_state_s *h, const qh::GateRec &r) {
       const bool tgt_low = ((kLow >> r.tgt) & 1ull) != 0;   // target itself inside the half line
       if (tgt_low) lowpred |= 1u << r.tgt;
       const uint64_t nwork = 1ull << (h->nloc - nc - (tgt_low ? 0 : 1));
-      if (!h->dry) {
-        const qh::BitIns ins = make_ins(tgt_low ? cm : (cm | (1ull << r.tgt)), -1);
-        if (h->bw == 128) launch_diag<double>(h, nwork, -1, ins, 1, 0, g[6], g[7], lowpred);
-        else launch_diag<float>(h, nwork, -1, ins, 1, 0, g[6], g[7], lowpred);
-      }
-      h->stats.bytes_algorithmic += (1ull << (h->nloc - nc_all - 1)) * ab * 2;
-      h->stats.bytes_swept += nwork * ab * 2;
+      diag_kernel(nwork, -1, tgt_low ? cm : (cm | (1ull << r.tgt)), 1, 0, g[6], g[7]);
+      count_kernel(h, 1ull << (h->nloc - nc_all - 1), nwork);
     } else {
       const uint64_t nwork = 1ull << (h->nloc - nc);
-      if (!h->dry) {
-        const qh::BitIns ins = make_ins(cm, -1);
-        if (h->bw == 128) launch_diag<double>(h, nwork, r.tgt, ins, g[0], g[1], g[6], g[7], lowpred);
-        else launch_diag<float>(h, nwork, r.tgt, ins, g[0], g[1], g[6], g[7], lowpred);
-      }
-      h->stats.bytes_algorithmic += (1ull << (h->nloc - nc_all)) * ab * 2;
-      h->stats.bytes_swept += nwork * ab * 2;
+      diag_kernel(nwork, r.tgt, cm, g[0], g[1], g[6], g[7]);
+      count_kernel(h, 1ull << (h->nloc - nc_all), nwork);
     }
-    h->stats.kernels_launched++;
     return QH_OK;
   }
-  const uint64_t nwork = 1ull << (h->nloc - nc - 1);
+  const uint64_t nwork = 1ull << (h->nloc - nc - 1);      // pairs
   if (!h->dry) {
     const qh::BitIns ins = make_ins(cm, r.tgt), ins1 = make_ins(cm, -1);
-    if (h->bw == 128) launch_pair<double>(h, nwork, r.tgt, ins, ins1, g, lowpred);
-    else launch_pair<float>(h, nwork, r.tgt, ins, ins1, g, lowpred);
+    with_real(h, [&](auto x) { launch_pair<decltype(x)>(h, nwork, r.tgt, ins, ins1, g, lowpred); });
   }
-  h->stats.kernels_launched++;
-  h->stats.bytes_algorithmic += (1ull << (h->nloc - nc_all - 1)) * 2 * ab * 2;
-  h->stats.bytes_swept += nwork * 2 * ab * 2;
+  count_kernel(h, 1ull << (h->nloc - nc_all), 2 * nwork);
   return QH_OK;
 }
 
@@ -458,11 +478,11 @@ int canonicalize(qh_state_s *h) {
   bp.n = h->nloc;
   for (size_t k = 0; k < loc.size(); ++k) bp.src_of_dst[posn[k]] = (uint8_t)h->perm[loc[k]];
   const uint64_t n = 1ull << h->nloc;
-  const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, 1ull << 22);
-  if (h->bw == 128)
-    hipLaunchKernelGGL(qh::k_permute_bits<double>, dim3(grid), dim3(256), 0, h->stream, (const double2 *)h->d_psi, (double2 *)h->d_alt, n, bp);
-  else
-    hipLaunchKernelGGL(qh::k_permute_bits<float>, dim3(grid), dim3(256), 0, h->stream, (const float2 *)h->d_psi, (float2 *)h->d_alt, n, bp);
+  with_real(h, [&](auto x) {
+    using R = decltype(x);
+    using A = typename qh::AmpT<R>::type;
+    hipLaunchKernelGGL(qh::k_permute_bits<R>, dim3(grid_for(n, 1ull << 22)), dim3(256), 0, h->stream, (const A *)h->d_psi, (A *)h->d_alt, n, bp);
+  });
   int rc = check_launch(h);
   if (rc) return rc;
   std::swap(h->d_psi, h->d_alt);
@@ -524,6 +544,18 @@ int flush_impl(qh_state_s *h, qh::SlabIO *split = nullptr, qh::TileMaxOut *tmax 
   return rc;
 }
 
+// The prologue of every entry point that works on the amplitudes, called after its argument checks: planner-only handles are
+// refused, the handle's device becomes current and what is queued runs (flush_impl begins with use_device).
+int enter(qh_state_s *h) {
+  if (h->dry) return fail(QH_ERR_ARG, "not on a dry (planner-only) handle");
+  return flush_impl(h);
+}
+// ... and the tail of the readers: `bytes` from the device to the caller on the handle's stream, then the host waits.
+int read_back(qh_state_s *h, void *host, const void *dev, size_t bytes, const char *what = "reader") {
+  HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream));
+  return wait_stream(h, h->stream, what);
+}
+
 // on: allocate the second buffer now (false if it does not fit); off: queued gates run, the layout returns to
 // canonical order, the second buffer is freed.  *actual (optional) = the resulting mode.
 int set_relayout(qh_state_s *h, bool on, int *actual = nullptr) {
@@ -581,10 +613,7 @@ int apply_logical(qh_state_s *h, uint64_t ctl_mask, int tgt_bit, const double g[
     return fail(QH_ERR_BAD_QUBIT, "control mask 0x%llx has bits >= %d",
                 (unsigned long long)ctl_mask, h->nglob);
   if ((ctl_mask >> tgt_bit) & 1ull) return fail(QH_ERR_SAME_QUBIT, "control == target (bit %d)", tgt_bit);
-  uint64_t pm = 0;
-  for (int b = 0; b < h->nglob; ++b)
-    if ((ctl_mask >> b) & 1ull) pm |= 1ull << h->perm[b];
-  return submit_phys(h, pm, h->perm[tgt_bit], g);
+  return submit_phys(h, to_phys(h, ctl_mask), h->perm[tgt_bit], g);
 }
 
 // Reference control semantics incl. quirk Q7 (see oracle/xgates_oracle.c):
@@ -823,18 +852,12 @@ int qh_nbits(qh_handle h, int *nl, int *ng) {
 
 int qh_logical_to_phys(qh_handle h, uint64_t logical, uint64_t *phys) {
   if (!h || !phys) return fail(QH_ERR_ARG, "null");
-  uint64_t p = 0;
-  for (int b = 0; b < h->nglob; ++b)
-    if ((logical >> b) & 1ull) p |= 1ull << h->perm[b];
-  *phys = p;
+  *phys = to_phys(h, logical);
   return QH_OK;
 }
 int qh_phys_to_logical(qh_handle h, uint64_t phys, uint64_t *logical) {
   if (!h || !logical) return fail(QH_ERR_ARG, "null");
-  uint64_t l = 0;
-  for (int b = 0; b < h->nglob; ++b)
-    if ((phys >> h->perm[b]) & 1ull) l |= 1ull << b;
-  *logical = l;
+  *logical = to_logical(h, phys);
   return QH_OK;
 }
 int qh_get_bitmap(qh_handle h, int32_t *out) {
@@ -875,16 +898,13 @@ int qh_init_basis(qh_handle h, uint64_t index) {
   if (h->dry) return QH_OK;
   HIP_TRY(hipSetDevice(h->device));
   if (h->comm) qh::wait_all_arrivals(&h->comm->arrivals, h->stream);
-  uint64_t phys;
-  qh_logical_to_phys(h, index, &phys);
+  const Placed at = place(h, to_phys(h, index));
   HIP_TRY(hipMemsetAsync(h->d_psi, 0, (1ull << h->nloc) * h->amp_bytes(), h->stream));
-  if ((phys >> h->nloc) == h->shard) {
-    const uint64_t li = phys & h->local_mask();
-    if (h->bw == 128)
-      hipLaunchKernelGGL(qh::k_set_one<double>, dim3(1), dim3(1), 0, h->stream, (double2 *)h->d_psi, li);
-    else
-      hipLaunchKernelGGL(qh::k_set_one<float>, dim3(1), dim3(1), 0, h->stream, (float2 *)h->d_psi, li);
-  }
+  if (at.held == h->shard)
+    with_real(h, [&](auto x) {
+      using R = decltype(x);
+      hipLaunchKernelGGL(qh::k_set_one<R>, dim3(1), dim3(1), 0, h->stream, (typename qh::AmpT<R>::type *)h->d_psi, at.local);
+    });
   return check_launch(h);
 }
 
@@ -949,12 +969,12 @@ int qh_init_product(qh_handle h, int nfactors, const int *nq, const double *cons
   hipError_t e = hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) {
     const uint64_t n = 1ull << h->nloc;
-    const dim3 grid((unsigned)std::min<uint64_t>((n + 255) / 256, 1ull << 22)), block(256);
     const uint64_t idx_high = h->shard << h->nloc;
-    if (h->bw == 128)
-      hipLaunchKernelGGL(qh::k_init_product<double>, grid, block, 0, h->stream, (double2 *)h->d_psi, n, idx_high, sp, d_tab);
-    else
-      hipLaunchKernelGGL(qh::k_init_product<float>, grid, block, 0, h->stream, (float2 *)h->d_psi, n, idx_high, sp, d_tab);
+    with_real(h, [&](auto x) {
+      using R = decltype(x);
+      hipLaunchKernelGGL(qh::k_init_product<R>, dim3(grid_for(n, 1ull << 22)), dim3(256), 0, h->stream,
+                         (typename qh::AmpT<R>::type *)h->d_psi, n, idx_high, sp, d_tab);
+    });
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // `tab` and d_tab are released below
   }
@@ -964,17 +984,16 @@ int qh_init_product(qh_handle h, int nfactors, const int *nq, const double *cons
 }
 
 int qh_upload(qh_handle h, const void *host, uint64_t offset, uint64_t count) {
-  if (!h || !host || h->dry) return fail(QH_ERR_ARG, "null/dry");
+  if (!h || !host) return fail(QH_ERR_ARG, "null handle or buffer");
   if (offset + count > (1ull << h->nloc)) return fail(QH_ERR_ARG, "upload range out of bounds");
-  HIP_TRY(hipSetDevice(h->device));
-  if (offset == 0 && count == (1ull << h->nloc)) {
+  if (!h->dry && offset == 0 && count == (1ull << h->nloc)) {
     // the whole shard is replaced: a fresh start -- nothing queued is worth running, a failed flush is forgotten, and a
     // plain handle goes back to canonical order without moving a byte (like the initialisations)
     h->queue.clear();
     h->poisoned = false;
     reset_layout_for_init(h);
   }
-  int rc = flush_impl(h);
+  int rc = enter(h);
   if (rc == QH_OK) rc = canonicalize(h);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync((char *)h->d_psi + offset * h->amp_bytes(), host, count * h->amp_bytes(),
@@ -983,38 +1002,29 @@ int qh_upload(qh_handle h, const void *host, uint64_t offset, uint64_t count) {
 }
 
 int qh_download(qh_handle h, void *host, uint64_t offset, uint64_t count) {
-  if (!h || !host || h->dry) return fail(QH_ERR_ARG, "null/dry");
+  if (!h || !host) return fail(QH_ERR_ARG, "null handle or buffer");
   if (offset + count > (1ull << h->nloc)) return fail(QH_ERR_ARG, "download range out of bounds");
-  HIP_TRY(hipSetDevice(h->device));
-  int rc = flush_impl(h);
+  int rc = enter(h);
   if (rc == QH_OK) rc = canonicalize(h);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(host, (const char *)h->d_psi + offset * h->amp_bytes(),
-                         count * h->amp_bytes(), hipMemcpyDeviceToHost, h->stream));
-  return wait_stream(h, h->stream, "qh_download");
+  return read_back(h, host, (const char *)h->d_psi + offset * h->amp_bytes(), count * h->amp_bytes(), "qh_download");
 }
 
 int qh_amplitude(qh_handle h, uint64_t logical_index, double out[2]) {
-  if (!h || !out || h->dry) return fail(QH_ERR_ARG, "null/dry");
+  if (!h || !out) return fail(QH_ERR_ARG, "null handle or out");
   if (h->nglob < 64 && (logical_index >> h->nglob)) return fail(QH_ERR_ARG, "index out of range");
-  HIP_TRY(hipSetDevice(h->device));
-  int rc = flush_impl(h);
+  int rc = enter(h);
   if (rc) return rc;
-  uint64_t phys;
-  qh_logical_to_phys(h, logical_index, &phys);
-  if ((phys >> h->nloc) != h->shard) return fail(QH_ERR_NONLOCAL, "amplitude %llu lives on shard %llu", (unsigned long long)logical_index, (unsigned long long)(phys >> h->nloc));
-  const uint64_t li = phys & h->local_mask();
-  if (h->bw == 128) {
-    HIP_TRY(hipMemcpyAsync(out, (const char *)h->d_psi + li * 16, 16, hipMemcpyDeviceToHost, h->stream));
-    if ((rc = wait_stream(h, h->stream, "qh_amplitude"))) return rc;
-  } else {
-    float f[2];
-    HIP_TRY(hipMemcpyAsync(f, (const char *)h->d_psi + li * 8, 8, hipMemcpyDeviceToHost, h->stream));
-    if ((rc = wait_stream(h, h->stream, "qh_amplitude"))) return rc;
-    out[0] = f[0];
-    out[1] = f[1];
-  }
-  return QH_OK;
+  const Placed at = place(h, to_phys(h, logical_index));
+  if (at.held != h->shard) return fail(QH_ERR_NONLOCAL, "amplitude %llu lives on shard %llu", (unsigned long long)logical_index, (unsigned long long)at.held);
+  return with_real(h, [&](auto x) {
+    decltype(x) v[2];
+    const int rc = read_back(h, v, (const char *)h->d_psi + at.local * sizeof v, sizeof v, "qh_amplitude");
+    if (rc) return rc;
+    out[0] = v[0];
+    out[1] = v[1];
+    return (int)QH_OK;
+  });
 }
 
 int qh_apply_bits(qh_handle h, uint64_t ctl_mask, int tgt_bit, const double gate[8]) {
@@ -1100,55 +1110,36 @@ int qh_apply_stream(qh_handle h, uint64_t count, const int32_t *ops, const doubl
   return QH_OK;
 }
 
-int qh_norm2(qh_handle h, double *out) {
-  if (!h || !out || h->dry) return fail(QH_ERR_ARG, "null/dry");
-  HIP_TRY(hipSetDevice(h->device));
-  int rc = flush_impl(h);
-  if (rc) return rc;
+// sum of |amplitude|^2 over the local indices i with (i & mask) == want
+static int masked_norm2(qh_handle h, uint64_t mask, uint64_t want, double *out) {
   HIP_TRY(hipMemsetAsync(h->d_red, 0, sizeof(double), h->stream));
   const uint64_t n = 1ull << h->nloc;
-  const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, 4096);
-  if (h->bw == 128)
-    hipLaunchKernelGGL(qh::k_norm2<double>, dim3(grid), dim3(256), 0, h->stream,
-                       (const double2 *)h->d_psi, n, 0ull, 0ull, h->d_red);
-  else
-    hipLaunchKernelGGL(qh::k_norm2<float>, dim3(grid), dim3(256), 0, h->stream,
-                       (const float2 *)h->d_psi, n, 0ull, 0ull, h->d_red);
-  HIP_TRY(hipMemcpyAsync(out, h->d_red, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if ((rc = wait_stream(h, h->stream, "reader"))) return rc;
-  return QH_OK;
+  with_real(h, [&](auto x) {
+    using R = decltype(x);
+    hipLaunchKernelGGL(qh::k_norm2<R>, dim3(grid_for(n, 4096)), dim3(256), 0, h->stream,
+                       (const typename qh::AmpT<R>::type *)h->d_psi, n, mask, want, h->d_red);
+  });
+  return read_back(h, out, h->d_red, sizeof(double));
+}
+
+int qh_norm2(qh_handle h, double *out) {
+  if (!h || !out) return fail(QH_ERR_ARG, "null handle or out");
+  const int rc = enter(h);
+  if (rc) return rc;
+  return masked_norm2(h, 0ull, 0ull, out);
 }
 
 int qh_prob_bit_value(qh_handle h, int logical_bit, int value, double *p) {
-  if (!h || !p || h->dry) return fail(QH_ERR_ARG, "null/dry");
+  if (!h || !p) return fail(QH_ERR_ARG, "null handle or out");
   if (logical_bit < 0 || logical_bit >= h->nglob) return fail(QH_ERR_BAD_QUBIT, "bit %d", logical_bit);
-  HIP_TRY(hipSetDevice(h->device));
-  int rc = flush_impl(h);
+  const int rc = enter(h);
   if (rc) return rc;
-  value = value ? 1 : 0;
-  const int pb = h->perm[logical_bit];
-  uint64_t mask = 0, want = 0;
-  if (pb >= h->nloc) {
-    if ((int)((h->shard >> (pb - h->nloc)) & 1ull) != value) {
-      *p = 0.0;
-      return QH_OK;
-    }
-  } else {
-    mask = 1ull << pb;
-    want = value ? mask : 0;
+  const Placed b = place_bit(h, logical_bit);
+  if (b.held && ((h->shard & b.held) != 0) != (value != 0)) {   // held by the shard index at the other value
+    *p = 0.0;
+    return QH_OK;
   }
-  HIP_TRY(hipMemsetAsync(h->d_red, 0, sizeof(double), h->stream));
-  const uint64_t n = 1ull << h->nloc;
-  const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, 4096);
-  if (h->bw == 128)
-    hipLaunchKernelGGL(qh::k_norm2<double>, dim3(grid), dim3(256), 0, h->stream,
-                       (const double2 *)h->d_psi, n, mask, want, h->d_red);
-  else
-    hipLaunchKernelGGL(qh::k_norm2<float>, dim3(grid), dim3(256), 0, h->stream,
-                       (const float2 *)h->d_psi, n, mask, want, h->d_red);
-  HIP_TRY(hipMemcpyAsync(p, h->d_red, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if ((rc = wait_stream(h, h->stream, "reader"))) return rc;
-  return QH_OK;
+  return masked_norm2(h, b.local, value ? b.local : 0ull, p);
 }
 
 int qh_prob_bit(qh_handle h, int logical_bit, double *p1) { return qh_prob_bit_value(h, logical_bit, 1, p1); }
@@ -1163,6 +1154,29 @@ __device__ __forceinline__ uint64_t map_bits(uint64_t v, const BitMap &m) {
   uint64_t o = 0;
   for (int p = 0; p < m.n; ++p) o |= ((v >> p) & 1ull) << m.to[p];
   return o;
+}
+// The tables of the kernels that report LOGICAL indices, as the layout is now: physical -> logical of the local bits
+// (p2l, meas.to), its inverse (l2p), and the logical bits the shard index holds at 1 on this shard (meas.shard_logical).
+struct LocalBits {
+  BitMap p2l{}, l2p{};
+  qh::MeasMap meas{};
+  bool mapped = false;      // some local bit is off its canonical position
+};
+LocalBits local_bits(const qh_state_s *h) {
+  LocalBits lb;
+  lb.p2l.n = lb.l2p.n = h->nloc;
+  for (int b = 0; b < h->nglob; ++b) {
+    const Placed at = place_bit(h, b);
+    if (at.held) {
+      if (h->shard & at.held) lb.meas.shard_logical |= 1ull << b;
+      continue;
+    }
+    const int p = h->perm[b];
+    lb.p2l.to[p] = lb.meas.to[p] = (uint8_t)b;
+    lb.l2p.to[b] = (uint8_t)p;
+    lb.mapped |= p != b;
+  }
+  return lb;
 }
 __device__ __forceinline__ double prob_of(double2 a) { return __builtin_fma(a.y, a.y, a.x * a.x); }   // (as the sweep islands compute it)
 __device__ __forceinline__ double prob_of(float2 a) { return __builtin_fma((double)a.y, (double)a.y, (double)a.x * (double)a.x); }
@@ -1268,13 +1282,12 @@ __global__ __launch_bounds__(256) void k_prefix_scan(const A *__restrict__ psi, 
 // smallest logical index that has it.  Few units hold it (a peaked state: Grover, most algorithms' outputs): those units are
 // scanned.  Many do (a flat state: a QFT's output ties at a tenth of its amplitudes): the first of them in LOGICAL order is
 // near the start -- growing prefixes of the logical index range are scanned until one has a hit.  Exact either way.
-int argmax_from_tilemax(qh_state_s *h, const qh::TileMaxOut &tm, const BitMap &bm, uint64_t *logical, double *prob, bool *found) {
+int argmax_from_tilemax(qh_state_s *h, const qh::TileMaxOut &tm, const LocalBits &lb, uint64_t *logical, double *prob, bool *found) {
   *found = false;
-  const unsigned grid = (unsigned)std::min<uint64_t>((tm.nunits + 255) / 256, kRedBlocks);
+  const unsigned grid = grid_for(tm.nunits, kRedBlocks);
   hipLaunchKernelGGL(k_tmax_reduce, dim3(grid), dim3(256), 0, h->stream, (const uint64_t *)tm.buf, tm.nunits, h->d_redi);
   std::vector<uint64_t> part(grid);
-  HIP_TRY(hipMemcpyAsync(part.data(), h->d_redi, grid * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-  int rc = wait_stream(h, h->stream, "reader");
+  int rc = read_back(h, part.data(), h->d_redi, grid * sizeof(uint64_t));
   if (rc) return rc;
   uint64_t top = 0;
   for (uint64_t v : part) top = std::max(top, v);
@@ -1286,24 +1299,19 @@ int argmax_from_tilemax(qh_state_s *h, const qh::TileMaxOut &tm, const BitMap &b
   HIP_TRY(hipMemsetAsync(ids + 1 + kTmaxIds, 0xff, 8, h->stream));
   hipLaunchKernelGGL(k_tmax_collect, dim3(grid), dim3(256), 0, h->stream, (const uint64_t *)tm.buf, tm.nunits, top, ids);
   unsigned long long cnt = 0;
-  HIP_TRY(hipMemcpyAsync(&cnt, ids, 8, hipMemcpyDeviceToHost, h->stream));
-  if ((rc = wait_stream(h, h->stream, "reader"))) return rc;
+  if ((rc = read_back(h, &cnt, ids, 8))) return rc;
   if (cnt == 0) return QH_OK;
   if (cnt > kTmaxIds) {
-    BitMap l2p{};
-    l2p.n = h->nloc;
-    for (int p = 0; p < h->nloc; ++p) l2p.to[bm.to[p]] = (uint8_t)p;       // (bm: physical -> logical, a permutation of the local bits)
     const uint64_t n = 1ull << h->nloc;
     uint64_t l0 = 0;
     for (uint64_t l1 = std::min<uint64_t>(n, 1ull << 16); l0 < n; l0 = l1, l1 = std::min<uint64_t>(n, l1 << 6)) {
-      const unsigned g = (unsigned)std::min<uint64_t>((l1 - l0 + 255) / 256, 1u << 16);
-      if (h->bw == 128)
-        hipLaunchKernelGGL(k_prefix_scan<double2>, dim3(g), dim3(256), 0, h->stream, (const double2 *)h->d_psi, l0, l1, want, l2p, ids + 1 + kTmaxIds);
-      else
-        hipLaunchKernelGGL(k_prefix_scan<float2>, dim3(g), dim3(256), 0, h->stream, (const float2 *)h->d_psi, l0, l1, want, l2p, ids + 1 + kTmaxIds);
+      with_real(h, [&](auto x) {
+        using A = typename qh::AmpT<decltype(x)>::type;
+        hipLaunchKernelGGL(k_prefix_scan<A>, dim3(grid_for(l1 - l0, 1u << 16)), dim3(256), 0, h->stream, (const A *)h->d_psi, l0, l1, want,
+                           lb.l2p, ids + 1 + kTmaxIds);
+      });
       unsigned long long hit = ~0ull;
-      HIP_TRY(hipMemcpyAsync(&hit, ids + 1 + kTmaxIds, 8, hipMemcpyDeviceToHost, h->stream));
-      if ((rc = wait_stream(h, h->stream, "reader"))) return rc;
+      if ((rc = read_back(h, &hit, ids + 1 + kTmaxIds, 8))) return rc;
       if (hit != ~0ull) {
         *logical = hit;
         *prob = want;
@@ -1313,15 +1321,13 @@ int argmax_from_tilemax(qh_state_s *h, const qh::TileMaxOut &tm, const BitMap &b
     }
     return QH_OK;      // (cannot happen)
   }
-  if (h->bw == 128)
-    hipLaunchKernelGGL(k_tmax_scan<double2>, dim3((unsigned)cnt), dim3(256), 0, h->stream, (const double2 *)h->d_psi, ids, tm.ins, tm.tile_mask,
-                       __builtin_popcountll(tm.tile_mask), want, bm, ids + 1 + kTmaxIds);
-  else
-    hipLaunchKernelGGL(k_tmax_scan<float2>, dim3((unsigned)cnt), dim3(256), 0, h->stream, (const float2 *)h->d_psi, ids, tm.ins, tm.tile_mask,
-                       __builtin_popcountll(tm.tile_mask), want, bm, ids + 1 + kTmaxIds);
+  with_real(h, [&](auto x) {
+    using A = typename qh::AmpT<decltype(x)>::type;
+    hipLaunchKernelGGL(k_tmax_scan<A>, dim3((unsigned)cnt), dim3(256), 0, h->stream, (const A *)h->d_psi, ids, tm.ins, tm.tile_mask,
+                       __builtin_popcountll(tm.tile_mask), want, lb.p2l, ids + 1 + kTmaxIds);
+  });
   unsigned long long li = ~0ull;
-  HIP_TRY(hipMemcpyAsync(&li, ids + 1 + kTmaxIds, 8, hipMemcpyDeviceToHost, h->stream));
-  if ((rc = wait_stream(h, h->stream, "reader"))) return rc;
+  if ((rc = read_back(h, &li, ids + 1 + kTmaxIds, 8))) return rc;
   if (li == ~0ull) return QH_OK;       // (cannot happen: a unit's maximum is one of its amplitudes) -> the full pass decides
   *logical = li;
   *prob = want;
@@ -1353,32 +1359,25 @@ extern "C" int qh_argmax(qh_handle h, uint64_t *phys_index, double *prob) {
   int rc = flush_impl(h, nullptr, tm.buf ? &tm : nullptr);
   if (rc) return rc;
   // ties go to the smallest LOGICAL index, whatever layout relayout sweeps have left the state in
-  BitMap bm{};
-  bm.n = h->nloc;
-  bool mapped = false;
-  for (int b = 0; b < h->nglob; ++b)
-    if (h->perm[b] < h->nloc) { bm.to[h->perm[b]] = (uint8_t)b; mapped |= h->perm[b] != b; }
+  const LocalBits lb = local_bits(h);
   uint64_t logical = 0;
   bool found = false;
   if (tm.valid) {
-    rc = argmax_from_tilemax(h, tm, bm, &logical, prob, &found);
+    rc = argmax_from_tilemax(h, tm, lb, &logical, prob, &found);
     if (rc) return rc;
   }
   if (!found) {
     const uint64_t n = 1ull << h->nloc;
-    const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, kRedBlocks);
-    if (h->bw == 128) {
-      if (mapped) hipLaunchKernelGGL((k_argmax_logical<double2, true>), dim3(grid), dim3(256), 0, h->stream, (const double2 *)h->d_psi, n, bm, h->d_red, h->d_redi);
-      else hipLaunchKernelGGL((k_argmax_logical<double2, false>), dim3(grid), dim3(256), 0, h->stream, (const double2 *)h->d_psi, n, bm, h->d_red, h->d_redi);
-    } else {
-      if (mapped) hipLaunchKernelGGL((k_argmax_logical<float2, true>), dim3(grid), dim3(256), 0, h->stream, (const float2 *)h->d_psi, n, bm, h->d_red, h->d_redi);
-      else hipLaunchKernelGGL((k_argmax_logical<float2, false>), dim3(grid), dim3(256), 0, h->stream, (const float2 *)h->d_psi, n, bm, h->d_red, h->d_redi);
-    }
+    const unsigned grid = grid_for(n, kRedBlocks);
+    with_real(h, [&](auto x) {
+      using A = typename qh::AmpT<decltype(x)>::type;
+      if (lb.mapped) hipLaunchKernelGGL((k_argmax_logical<A, true>), dim3(grid), dim3(256), 0, h->stream, (const A *)h->d_psi, n, lb.p2l, h->d_red, h->d_redi);
+      else hipLaunchKernelGGL((k_argmax_logical<A, false>), dim3(grid), dim3(256), 0, h->stream, (const A *)h->d_psi, n, lb.p2l, h->d_red, h->d_redi);
+    });
     std::vector<double> bp(grid);
     std::vector<uint64_t> bi(grid);
     HIP_TRY(hipMemcpyAsync(bp.data(), h->d_red, grid * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(bi.data(), h->d_redi, grid * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    if ((rc = wait_stream(h, h->stream, "reader"))) return rc;
+    if ((rc = read_back(h, bi.data(), h->d_redi, grid * sizeof(uint64_t)))) return rc;
     double best = -1.0;
     uint64_t idx = 0;
     for (unsigned k = 0; k < grid; ++k)
@@ -1387,46 +1386,37 @@ extern "C" int qh_argmax(qh_handle h, uint64_t *phys_index, double *prob) {
     *prob = best;
   }
   // the caller gets the PHYSICAL index of the shard-local amplitude (qh_phys_to_logical turns it back)
-  uint64_t phys = 0;
-  for (int b = 0; b < h->nglob; ++b)
-    if (h->perm[b] < h->nloc && ((logical >> b) & 1ull)) phys |= 1ull << h->perm[b];
-  *phys_index = (h->shard << h->nloc) | phys;
+  *phys_index = (h->shard << h->nloc) | place(h, to_phys(h, logical)).local;
   return QH_OK;
 }
 
 extern "C" {
 int qh_scale(qh_handle h, double re, double im) {
-  if (!h || h->dry) return fail(QH_ERR_ARG, "null/dry");
-  HIP_TRY(hipSetDevice(h->device));
-  int rc = flush_impl(h);
+  if (!h) return fail(QH_ERR_ARG, "null handle");
+  const int rc = enter(h);
   if (rc) return rc;
-  qh::BitIns ins{};
-  const uint64_t nwork = 1ull << h->nloc;
-  if (h->bw == 128) launch_diag<double>(h, nwork, -1, ins, 1, 0, re, im);
-  else launch_diag<float>(h, nwork, -1, ins, 1, 0, re, im);
+  const qh::BitIns ins{};
+  with_real(h, [&](auto x) { launch_diag<decltype(x)>(h, 1ull << h->nloc, -1, ins, 1, 0, re, im); });
   return check_launch(h);
 }
 
 int qh_project_bit(qh_handle h, int logical_bit, int value) {
-  if (!h || h->dry) return fail(QH_ERR_ARG, "null/dry");
+  if (!h) return fail(QH_ERR_ARG, "null handle");
   if (logical_bit < 0 || logical_bit >= h->nglob) return fail(QH_ERR_BAD_QUBIT, "bit %d", logical_bit);
-  HIP_TRY(hipSetDevice(h->device));
-  int rc = flush_impl(h);
+  const int rc = enter(h);
   if (rc) return rc;
-  const int pb = h->perm[logical_bit];
-  value = value ? 1 : 0;
-  if (pb >= h->nloc) {
-    if ((int)((h->shard >> (pb - h->nloc)) & 1ull) != value)
+  const Placed b = place_bit(h, logical_bit);
+  if (b.held) {      // a shard whose index contradicts the value is zeroed whole
+    if (((h->shard & b.held) != 0) != (value != 0))
       HIP_TRY(hipMemsetAsync(h->d_psi, 0, (1ull << h->nloc) * h->amp_bytes(), h->stream));
     return QH_OK;
   }
-  qh::BitIns ins = make_ins(value ? 0ull : (1ull << pb), value ? pb : -1);
+  const qh::BitIns ins = make_ins(value ? 0ull : b.local, value ? h->perm[logical_bit] : -1);
   const uint64_t nwork = 1ull << (h->nloc - 1);
-  const unsigned grid = (unsigned)std::min<uint64_t>((nwork + 255) / 256, 1u << 20);
-  if (h->bw == 128)
-    hipLaunchKernelGGL(qh::k_project<double>, dim3(grid), dim3(256), 0, h->stream, (double2 *)h->d_psi, nwork, ins);
-  else
-    hipLaunchKernelGGL(qh::k_project<float>, dim3(grid), dim3(256), 0, h->stream, (float2 *)h->d_psi, nwork, ins);
+  with_real(h, [&](auto x) {
+    using R = decltype(x);
+    hipLaunchKernelGGL(qh::k_project<R>, dim3(grid_for(nwork, 1u << 20)), dim3(256), 0, h->stream, (typename qh::AmpT<R>::type *)h->d_psi, nwork, ins);
+  });
   return check_launch(h);
 }
 }  // extern "C"
@@ -1508,9 +1498,8 @@ int qh_apply_matrix(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, 
   }
   if (ctl_mask & tmask)
     return fail(QH_ERR_SAME_QUBIT, "apply_matrix: control and target share bits 0x%llx", (unsigned long long)(ctl_mask & tmask));
-  int nlc = 0;                 // (a logical bit stays local or in the shard index whatever the relayout sweeps do)
-  for (int b = 0; b < h->nglob; ++b)
-    if (((ctl_mask >> b) & 1ull) && h->perm[b] < h->nloc) ++nlc;
+  // (a logical bit stays local or in the shard index whatever the relayout sweeps do)
+  const int nlc = __builtin_popcountll(place(h, to_phys(h, ctl_mask)).local);
   if (k + nlc > qh::kMaxIns)
     return fail(QH_ERR_ARG, "apply_matrix: %d targets + %d local controls exceed the %d bits one index enumeration inserts (kMaxIns)",
                 k, nlc, qh::kMaxIns);
@@ -1518,22 +1507,15 @@ int qh_apply_matrix(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, 
     if (h->perm[bits[j]] >= h->nloc)
       return fail(QH_ERR_NONLOCAL, "apply_matrix: logical bit %d is held by the shard index (physical bit %d, local bits: %d); "
                   "exchange first", bits[j], h->perm[bits[j]], h->nloc);
-  if (h->dry) return fail(QH_ERR_ARG, "null/dry");
-  HIP_TRY(hipSetDevice(h->device));
-  int rc = flush_impl(h);      // a barrier: what is queued runs first, on whatever layout it leaves
+  int rc = enter(h);           // a barrier: what is queued runs first, on whatever layout it leaves
   if (rc) return rc;
-  uint64_t cm_all = 0;         // physical local control bits
-  for (int b = 0; b < h->nglob; ++b) {
-    if (!((ctl_mask >> b) & 1ull)) continue;
-    const int pb = h->perm[b];
-    if (pb < h->nloc) {
-      cm_all |= 1ull << pb;
-    } else if (!((h->shard >> (pb - h->nloc)) & 1ull)) {   // a shard-bit control that is 0 on this shard
-      h->stats.gates_submitted++;
-      h->stats.gates_noop++;
-      return QH_OK;
-    }                                                        // (met: dropped)
+  const Placed ctl = place(h, to_phys(h, ctl_mask));
+  if ((h->shard & ctl.held) != ctl.held) {   // a shard-bit control that is 0 on this shard (met: dropped)
+    h->stats.gates_submitted++;
+    h->stats.gates_noop++;
+    return QH_OK;
   }
+  const uint64_t cm_all = ctl.local;         // physical local control bits
   const uint64_t kLow = (h->nloc > 2) ? 3ull : 0ull;         // as launch_single: bits 0-1 are a predicate
   qh::DenseArgs a{};
   a.lowpred = (uint32_t)(cm_all & kLow);
@@ -1550,16 +1532,12 @@ int qh_apply_matrix(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, 
   const void *dmat = nullptr;
   unsigned slot = 0;
   if ((rc = stage_matrix(h, k, matrix, &dmat, &slot))) return rc;
-  if (h->bw == 128) launch_dense<double>(h, k, a, dmat);
-  else launch_dense<float>(h, k, a, dmat);
+  with_real(h, [&](auto x) { launch_dense<decltype(x)>(h, k, a, dmat); });
   if ((rc = check_launch(h))) return rc;
   HIP_TRY(hipEventRecord(h->mat_ev[slot], h->stream));
   h->mat_used[slot] = true;
-  const uint64_t ab = h->amp_bytes();
   h->stats.gates_submitted++;
-  h->stats.kernels_launched++;
-  h->stats.bytes_algorithmic += (1ull << (h->nloc - __builtin_popcountll(cm_all))) * ab * 2;
-  h->stats.bytes_swept += (a.nwork << k) * ab * 2;
+  count_kernel(h, 1ull << (h->nloc - __builtin_popcountll(cm_all)), a.nwork << k);
   return QH_OK;
 }
 
@@ -1586,17 +1564,6 @@ int meas_scratch(qh_state_s *h, size_t bytes, char **out) {
 
 int meas_chunk_bits(const qh_state_s *h) { return std::min(h->nloc, qh::kMeasChunkBits); }
 
-// physical -> logical of the local bits, and the logical bits the shard index holds, as they are on this shard
-qh::MeasMap meas_map(const qh_state_s *h) {
-  qh::MeasMap m{};
-  for (int b = 0; b < h->nglob; ++b) {
-    const int p = h->perm[b];
-    if (p < h->nloc) m.to[p] = (uint8_t)b;
-    else if ((h->shard >> (p - h->nloc)) & 1ull) m.shard_logical |= 1ull << b;
-  }
-  return m;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1610,9 +1577,7 @@ int qh_marginal(qh_handle h, int k, const int32_t *bits, double *out) {
     if ((seen >> bits[t]) & 1ull) return fail(QH_ERR_SAME_QUBIT, "marginal: bit %d appears twice", bits[t]);
     seen |= 1ull << bits[t];
   }
-  if (h->dry) return fail(QH_ERR_ARG, "null/dry");
-  HIP_TRY(hipSetDevice(h->device));
-  int rc = flush_impl(h);
+  int rc = enter(h);
   if (rc) return rc;
   const int c = meas_chunk_bits(h);
   qh::MarginalArgs a{};
@@ -1620,12 +1585,9 @@ int qh_marginal(qh_handle h, int k, const int32_t *bits, double *out) {
   a.c = c;
   std::vector<std::pair<int, int>> loc;     // (physical bit, output bit) of the register bits this shard holds locally
   for (int t = 0; t < k; ++t) {
-    const int p = h->perm[bits[t]];
-    if (p >= h->nloc) {
-      if ((h->shard >> (p - h->nloc)) & 1ull) f.fixed |= 1ull << t;     // fixed on this shard
-    } else {
-      loc.push_back({p, t});
-    }
+    const Placed b = place_bit(h, bits[t]);
+    if (!b.held) loc.push_back({h->perm[bits[t]], t});
+    else if (h->shard & b.held) f.fixed |= 1ull << t;     // fixed on this shard
   }
   std::sort(loc.begin(), loc.end());
   for (const auto &pt : loc) {
@@ -1651,16 +1613,14 @@ int qh_marginal(qh_handle h, int k, const int32_t *bits, double *out) {
   if ((rc = meas_scratch(h, slab_bytes + out_bytes, &scr))) return rc;
   double *slab = (double *)scr, *dout = (double *)(scr + slab_bytes);
   HIP_TRY(hipMemsetAsync(dout, 0, out_bytes, h->stream));
-  if (h->bw == 128)
-    hipLaunchKernelGGL(qh::k_marginal_bins<double>, dim3((unsigned)nblk), dim3(256), 0, h->stream, (const double2 *)h->d_psi, a, slab);
-  else
-    hipLaunchKernelGGL(qh::k_marginal_bins<float>, dim3((unsigned)nblk), dim3(256), 0, h->stream, (const float2 *)h->d_psi, a, slab);
+  with_real(h, [&](auto x) {
+    using R = decltype(x);
+    hipLaunchKernelGGL(qh::k_marginal_bins<R>, dim3((unsigned)nblk), dim3(256), 0, h->stream, (const typename qh::AmpT<R>::type *)h->d_psi, a, slab);
+  });
   const uint64_t nfold = 1ull << (a.ki + a.ko);
-  hipLaunchKernelGGL(qh::k_marginal_fold, dim3((unsigned)std::min<uint64_t>((nfold + 255) / 256, kRedBlocks)), dim3(256), 0,
-                     h->stream, (const double *)slab, f, dout);
+  hipLaunchKernelGGL(qh::k_marginal_fold, dim3(grid_for(nfold, kRedBlocks)), dim3(256), 0, h->stream, (const double *)slab, f, dout);
   if ((rc = check_launch(h))) return rc;
-  HIP_TRY(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, h->stream));
-  return wait_stream(h, h->stream, "reader");
+  return read_back(h, out, dout, out_bytes);
 }
 
 int qh_sample(qh_handle h, uint64_t count, const double *u, uint64_t *logical_out) {
@@ -1669,9 +1629,7 @@ int qh_sample(qh_handle h, uint64_t count, const double *u, uint64_t *logical_ou
     if (!(u[s] >= 0.0 && u[s] < 1.0)) return fail(QH_ERR_ARG, "sample: u[%llu] = %g outside [0,1)", (unsigned long long)s, u[s]);
     if (s && u[s] < u[s - 1]) return fail(QH_ERR_ARG, "sample: u is not ascending at %llu", (unsigned long long)s);
   }
-  if (h->dry) return fail(QH_ERR_ARG, "null/dry");
-  HIP_TRY(hipSetDevice(h->device));
-  int rc = flush_impl(h);
+  int rc = enter(h);
   if (rc) return rc;
   if (count == 0) return QH_OK;
   const int c = meas_chunk_bits(h);
@@ -1685,14 +1643,13 @@ int qh_sample(qh_handle h, uint64_t count, const double *u, uint64_t *logical_ou
   uint64_t *d_ids = (uint64_t *)(scr + sums_b + tgt_b), *d_first = (uint64_t *)(scr + sums_b + tgt_b + ids_b);
   uint64_t *d_out = (uint64_t *)(scr + sums_b + tgt_b + ids_b + first_b);
   const unsigned g1 = (unsigned)std::min<uint64_t>(nchunks, 2048);
-  if (h->bw == 128)
-    hipLaunchKernelGGL(qh::k_chunk_sums<double>, dim3(g1), dim3(256), 0, h->stream, (const double2 *)h->d_psi, c, nchunks, d_sums);
-  else
-    hipLaunchKernelGGL(qh::k_chunk_sums<float>, dim3(g1), dim3(256), 0, h->stream, (const float2 *)h->d_psi, c, nchunks, d_sums);
+  with_real(h, [&](auto x) {
+    using R = decltype(x);
+    hipLaunchKernelGGL(qh::k_chunk_sums<R>, dim3(g1), dim3(256), 0, h->stream, (const typename qh::AmpT<R>::type *)h->d_psi, c, nchunks, d_sums);
+  });
   if ((rc = check_launch(h))) return rc;
   std::vector<double> sums(nchunks);
-  HIP_TRY(hipMemcpyAsync(sums.data(), d_sums, nchunks * 8, hipMemcpyDeviceToHost, h->stream));
-  if ((rc = wait_stream(h, h->stream, "reader"))) return rc;
+  if ((rc = read_back(h, sums.data(), d_sums, nchunks * 8))) return rc;
   // the CDF over chunks, in physical order; every shot goes to the first chunk whose inclusive prefix exceeds u * norm
   double total = 0.0;
   uint64_t lastc = 0;
@@ -1724,17 +1681,15 @@ int qh_sample(qh_handle h, uint64_t count, const double *u, uint64_t *logical_ou
   HIP_TRY(hipMemcpyAsync(d_tgt, tgt.data(), count * 8, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(d_ids, ids.data(), m * 8, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(d_first, first.data(), (m + 1) * 8, hipMemcpyHostToDevice, h->stream));
-  const qh::MeasMap mm = meas_map(h);
+  const qh::MeasMap mm = local_bits(h).meas;
   const unsigned g2 = (unsigned)std::min<uint64_t>(m, 2048);
-  if (h->bw == 128)
-    hipLaunchKernelGGL(qh::k_chunk_locate<double>, dim3(g2), dim3(256), 0, h->stream, (const double2 *)h->d_psi, c,
+  with_real(h, [&](auto x) {
+    using R = decltype(x);
+    hipLaunchKernelGGL(qh::k_chunk_locate<R>, dim3(g2), dim3(256), 0, h->stream, (const typename qh::AmpT<R>::type *)h->d_psi, c,
                        (const uint64_t *)d_ids, (const uint64_t *)d_first, m, (const double *)d_tgt, mm, d_out);
-  else
-    hipLaunchKernelGGL(qh::k_chunk_locate<float>, dim3(g2), dim3(256), 0, h->stream, (const float2 *)h->d_psi, c,
-                       (const uint64_t *)d_ids, (const uint64_t *)d_first, m, (const double *)d_tgt, mm, d_out);
+  });
   if ((rc = check_launch(h))) return rc;
-  HIP_TRY(hipMemcpyAsync(logical_out, d_out, count * 8, hipMemcpyDeviceToHost, h->stream));
-  return wait_stream(h, h->stream, "reader");
+  return read_back(h, logical_out, d_out, count * 8);
 }
 
 int qh_project_bits(qh_handle h, uint64_t mask, uint64_t value) {
@@ -1743,30 +1698,20 @@ int qh_project_bits(qh_handle h, uint64_t mask, uint64_t value) {
     return fail(QH_ERR_ARG, "project_bits: value 0x%llx has bits outside mask 0x%llx", (unsigned long long)value, (unsigned long long)mask);
   if (h->nglob < 64 && (mask >> h->nglob))
     return fail(QH_ERR_BAD_QUBIT, "project_bits: mask 0x%llx has bits >= %d", (unsigned long long)mask, h->nglob);
-  if (h->dry) return fail(QH_ERR_ARG, "null/dry");
-  HIP_TRY(hipSetDevice(h->device));
-  int rc = flush_impl(h);
+  const int rc = enter(h);
   if (rc) return rc;
-  uint64_t pm = 0, pw = 0;
-  bool disagree = false;
-  for (int b = 0; b < h->nglob; ++b) {
-    if (!((mask >> b) & 1ull)) continue;
-    const int p = h->perm[b];
-    const uint64_t v = (value >> b) & 1ull;
-    if (p >= h->nloc) disagree |= ((h->shard >> (p - h->nloc)) & 1ull) != v;
-    else { pm |= 1ull << p; pw |= v << p; }
-  }
-  if (disagree) {      // (as qh_project_bit: a shard whose index contradicts the value is zeroed whole)
+  const Placed m = place(h, to_phys(h, mask)), v = place(h, to_phys(h, value));
+  if ((h->shard ^ v.held) & m.held) {      // (as qh_project_bit: a shard whose index contradicts the value is zeroed whole)
     HIP_TRY(hipMemsetAsync(h->d_psi, 0, (1ull << h->nloc) * h->amp_bytes(), h->stream));
     return QH_OK;
   }
-  if (!pm) return QH_OK;
+  if (!m.local) return QH_OK;
   const uint64_t n = 1ull << h->nloc;
-  const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 20);
-  if (h->bw == 128)
-    hipLaunchKernelGGL(qh::k_project_mask<double>, dim3(grid), dim3(256), 0, h->stream, (double2 *)h->d_psi, n, pm, pw);
-  else
-    hipLaunchKernelGGL(qh::k_project_mask<float>, dim3(grid), dim3(256), 0, h->stream, (float2 *)h->d_psi, n, pm, pw);
+  with_real(h, [&](auto x) {
+    using R = decltype(x);
+    hipLaunchKernelGGL(qh::k_project_mask<R>, dim3(grid_for(n, 1u << 20)), dim3(256), 0, h->stream, (typename qh::AmpT<R>::type *)h->d_psi, n,
+                       m.local, v.local);
+  });
   return check_launch(h);
 }
 
@@ -1797,30 +1742,21 @@ int qh_expect_pauli(qh_handle h, uint64_t nterms, const uint64_t *xmask, const u
       if ((xmask[t] | zmask[t]) >> h->nglob)
         return fail(QH_ERR_BAD_QUBIT, "expect_pauli: term %llu (x 0x%llx, z 0x%llx) has bits >= %d", (unsigned long long)t,
                     (unsigned long long)xmask[t], (unsigned long long)zmask[t], h->nglob);
-  if (h->dry) return fail(QH_ERR_ARG, "null/dry");
-  HIP_TRY(hipSetDevice(h->device));
-  int rc = flush_impl(h);
+  int rc = enter(h);
   if (rc) return rc;
   if (nterms == 0) return QH_OK;
   // masks through the bit map: local bits stay masks, a z bit the shard index holds is a sign fixed on this shard
   struct Term { uint64_t px, pz, idx; uint32_t neg, ny; };
   std::vector<Term> terms(nterms);
   for (uint64_t t = 0; t < nterms; ++t) {
-    Term &tm = terms[t];
-    tm = Term{0, 0, t, 0, (uint32_t)__builtin_popcountll(xmask[t] & zmask[t]) & 3u};
-    for (int b = 0; b < h->nglob; ++b) {
-      const int p = h->perm[b];
-      if ((xmask[t] >> b) & 1ull) {
-        if (p >= h->nloc)
-          return fail(QH_ERR_NONLOCAL, "expect_pauli: term %llu has X or Y on logical bit %d, held by the shard index (physical bit %d, "
-                      "local bits: %d); exchange first", (unsigned long long)t, b, p, h->nloc);
-        tm.px |= 1ull << p;
-      }
-      if ((zmask[t] >> b) & 1ull) {
-        if (p >= h->nloc) tm.neg ^= (uint32_t)((h->shard >> (p - h->nloc)) & 1ull);
-        else tm.pz |= 1ull << p;
-      }
+    const Placed x = place(h, to_phys(h, xmask[t])), z = place(h, to_phys(h, zmask[t]));
+    if (x.held) {
+      const int b = __builtin_ctzll(to_logical(h, x.held << h->nloc));     // the first of them
+      return fail(QH_ERR_NONLOCAL, "expect_pauli: term %llu has X or Y on logical bit %d, held by the shard index (physical bit %d, "
+                  "local bits: %d); exchange first", (unsigned long long)t, b, h->perm[b], h->nloc);
     }
+    terms[t] = Term{x.local, z.local, t, (uint32_t)__builtin_popcountll(h->shard & z.held) & 1u,
+                    (uint32_t)__builtin_popcountll(xmask[t] & zmask[t]) & 3u};
   }
   // terms that share a physical x mask share a read of the state, kExpectT at a time
   std::stable_sort(terms.begin(), terms.end(), [](const Term &l, const Term &r) { return l.px < r.px; });
@@ -1853,13 +1789,11 @@ int qh_expect_pauli(qh_handle h, uint64_t nterms, const uint64_t *xmask, const u
       if (tm.ny & 1u) a.cim[k] = one; else a.cre[k] = one;
     }
     const int tt = cnt <= 4 ? 4 : qh::kExpectT;
-    if (h->bw == 128) {
-      if (tt == 4) launch_expect<double, 4>(h, pair, (unsigned)nblk, a, slab);
-      else launch_expect<double, qh::kExpectT>(h, pair, (unsigned)nblk, a, slab);
-    } else {
-      if (tt == 4) launch_expect<float, 4>(h, pair, (unsigned)nblk, a, slab);
-      else launch_expect<float, qh::kExpectT>(h, pair, (unsigned)nblk, a, slab);
-    }
+    with_real(h, [&](auto x) {
+      using R = decltype(x);
+      if (tt == 4) launch_expect<R, 4>(h, pair, (unsigned)nblk, a, slab);
+      else launch_expect<R, qh::kExpectT>(h, pair, (unsigned)nblk, a, slab);
+    });
     hipLaunchKernelGGL(qh::k_expect_fold, dim3((unsigned)cnt), dim3(256), 0, h->stream, (const double *)slab, (uint32_t)nblk, tt,
                        pair ? 2.0 : 1.0, dout + first);
     if ((rc = check_launch(h))) return rc;
@@ -1867,8 +1801,7 @@ int qh_expect_pauli(qh_handle h, uint64_t nterms, const uint64_t *xmask, const u
     ++batches;
   }
   std::vector<double> vals(nterms);
-  HIP_TRY(hipMemcpyAsync(vals.data(), dout, (size_t)nterms * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if ((rc = wait_stream(h, h->stream, "reader"))) return rc;
+  if ((rc = read_back(h, vals.data(), dout, (size_t)nterms * sizeof(double)))) return rc;
   for (uint64_t k = 0; k < nterms; ++k) out[terms[k].idx] = vals[k];
   h->stats.kernels_launched += batches;      // reads of the state: one per batch
   h->stats.bytes_swept += batches * ((1ull << h->nloc) * h->amp_bytes());
@@ -1887,9 +1820,8 @@ int qh_reset_stats(qh_handle h) {
 }
 
 int qh_timer_begin(qh_handle h) {
-  if (!h || h->dry) return fail(QH_ERR_ARG, "null/dry");
-  HIP_TRY(hipSetDevice(h->device));
-  int rc = flush_impl(h);
+  if (!h) return fail(QH_ERR_ARG, "null handle");
+  int rc = enter(h);
   if (rc) return rc;
   rc = make_events(h);
   if (rc) return rc;
@@ -1897,10 +1829,9 @@ int qh_timer_begin(qh_handle h) {
   return QH_OK;
 }
 int qh_timer_end(qh_handle h, float *ms) {
-  if (!h || !ms || h->dry) return fail(QH_ERR_ARG, "null/dry");
+  if (!h || !ms) return fail(QH_ERR_ARG, "null handle or out");
   if (!h->ev0) return fail(QH_ERR_ARG, "qh_timer_end without qh_timer_begin");
-  HIP_TRY(hipSetDevice(h->device));
-  int rc = flush_impl(h);
+  int rc = enter(h);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(h->ev1, h->stream));
   if ((rc = wait_event(h, h->ev1, "qh_timer_end"))) return rc;
@@ -1909,9 +1840,8 @@ int qh_timer_end(qh_handle h, float *ms) {
 }
 
 int qh_timer_lap(qh_handle h) {
-  if (!h || h->dry) return fail(QH_ERR_ARG, "null/dry");
-  HIP_TRY(hipSetDevice(h->device));
-  int rc = flush_impl(h);
+  if (!h) return fail(QH_ERR_ARG, "null handle");
+  const int rc = enter(h);
   if (rc) return rc;
   if (h->laps_used == h->laps.size()) {
     hipEvent_t e = nullptr;
@@ -2030,14 +1960,13 @@ namespace {
   } while (0)
 
 int comm_common_init(qh_state_s *h, int nranks, int rank) {
-  if (!h || h->dry) return fail(QH_ERR_ARG, "null/dry handle");
+  if (!h) return fail(QH_ERR_ARG, "null handle");
   if (h->comm) return fail(QH_ERR_ARG, "handle already has a communicator");
   if (nranks < 1 || (nranks & (nranks - 1)) || rank < 0 || rank >= nranks)
     return fail(QH_ERR_ARG, "nranks %d must be a power of two, rank %d inside it", nranks, rank);
   if (nranks > qh::kMaxXferMoves + 1) return fail(QH_ERR_ARG, "at most %d ranks", qh::kMaxXferMoves + 1);
   if (h->bw != 128 && h->bw != 64) return fail(QH_ERR_BAD_DTYPE, "bit width");
-  HIP_TRY(hipSetDevice(h->device));
-  int rc0 = flush_impl(h);
+  int rc0 = enter(h);
   if (rc0) return rc0;
   if (nranks > 1 && h->relayout != 0) {
     // The ranks of a sharded state must hold the same layout whenever they exchange.  They do if all of them
@@ -2075,7 +2004,7 @@ void close_timing(qh::Comm *c) {
 template <typename A>
 void launch_xfer(bool unpack, void *psi, void *stage, uint64_t n, uint64_t start, const qh::XferGeom &g, hipStream_t st) {
   const uint64_t total = n * (uint64_t)g.np;
-  const unsigned grid = (unsigned)std::min<uint64_t>((total + 255) / 256, 1ull << 20);
+  const unsigned grid = grid_for(total, 1ull << 20);
   if (unpack) hipLaunchKernelGGL(qh::k_xunpack<A>, dim3(grid), dim3(256), 0, st, (A *)psi, (const A *)stage, n, start, g);
   else hipLaunchKernelGGL(qh::k_xpack<A>, dim3(grid), dim3(256), 0, st, (const A *)psi, (A *)stage, n, start, g);
 }
@@ -2285,8 +2214,7 @@ int do_exchange(qh_state_s *h, const std::vector<qh::BlockMove> &moves, int base
   auto xfer = [&](bool unpack, void *stage, uint64_t start, uint64_t sv, hipStream_t st) {
     qh::XferGeom g = unpack ? xg_land : xg_send;
     for (size_t m = 0; m < np; ++m) g.off[m] |= sv;
-    if (h->bw == 128) launch_xfer<double2>(unpack, psi, stage, n, start, g, st);
-    else launch_xfer<float2>(unpack, psi, stage, n, start, g, st);
+    with_real(h, [&](auto x) { launch_xfer<typename qh::AmpT<decltype(x)>::type>(unpack, psi, stage, n, start, g, st); });
   };
   if (c->custom) {
     // host-staged transport: synchronous rounds
@@ -2565,14 +2493,11 @@ int qh_comm_allreduce_sum(qh_handle h, double *inout, int count) {
   if (!h || !h->comm || !inout) return fail(QH_ERR_ARG, "null / no communicator");
   if (!h->comm->nccl) return fail(QH_ERR_COMM, "qh_comm_allreduce_sum needs the RCCL transport");
   if (count < 1 || count > kRedBlocks) return fail(QH_ERR_ARG, "count %d", count);
-  HIP_TRY(hipSetDevice(h->device));
-  int rc = flush_impl(h);
+  const int rc = enter(h);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(h->d_red, inout, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
   NCCL_TRY(qh::rccl().AllReduce(h->d_red, h->d_red, (size_t)count, ncclDouble, ncclSum, h->comm->nccl, h->stream));
-  HIP_TRY(hipMemcpyAsync(inout, h->d_red, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if ((rc = wait_stream(h, h->stream, "reader"))) return rc;
-  return QH_OK;
+  return read_back(h, inout, h->d_red, count * sizeof(double));
 }
 
 }  // extern "C"
