@@ -317,6 +317,15 @@ int qh_plan_json(qh_handle h, char *buf, uint64_t cap, uint64_t *needed);
  * without a GPU (tests/plan_interp.py executes it with NumPy).                 */
 int qh_plan_export(qh_handle h, void *buf, uint64_t cap, uint64_t *needed);
 
+/* What the sweep kernels would DISPATCH for the current queue: the plan of qh_plan_export as a flush hands it to
+ * the device (does not launch or clear; planner-only and live handles alike).  Same calling convention.  u32 words:
+ * magic 0x51484831, number of sweeps, then per sweep bit_width, rb, nwave, relayout, n_ops, n_groups, the device
+ * `kind` and `flags` words of every op (kind: OP_* | handler number << 16; the sentinel that ends the list is left
+ * out) and the device `flags` word of every group (handler in bits 8..15, general path bit 2, sign-flip outside
+ * terms bit 4); padded to 8 bytes.  Built by the function the flush builds its upload with
+ * (qcc_amd/csrc/kernels_sweep.hip.h build_device_copy): tests use it to say which island handlers a circuit runs. */
+int qh_plan_handlers(qh_handle h, void *buf, uint64_t cap, uint64_t *needed);
+
 /* ---- literal drop-in on host buffers (what `libxgates` binds) ----------- */
 /* psi: host pointer to 2^nbits complex numbers of width bit_width, updated in
  * place (H2D, kernel, D2H -- PCIe inclusive).  gate: 8 doubles.              */

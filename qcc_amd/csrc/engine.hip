@@ -1947,6 +1947,36 @@ int qh_plan_export(qh_handle h, void *buf, uint64_t cap, uint64_t *needed) {
   return QH_OK;
 }
 
+int qh_plan_handlers(qh_handle h, void *buf, uint64_t cap, uint64_t *needed) {
+  if (!h) return fail(QH_ERR_ARG, "null");
+  if (!qh::sweep_supported(h->nloc, h->bw)) return fail(QH_ERR_ARG, "state too small for sweeps");
+  qh::PlanResult pr;
+  if (int rc = qh::guard_planning(&g_err, [&] { pr = qh::plan_best(h->queue, plan_request(h, relayout_wanted(h))); })) return rc;
+  std::vector<uint32_t> out{0x51484831u, (uint32_t)pr.sweeps.size()};
+  std::vector<qh::SweepOp> ops;
+  std::vector<qh::DGroup> groups;
+  for (auto &sp : pr.sweeps) {
+    // the device copy of the sweep, built by the function a flush builds it with
+    ops.assign(sp.ops.size() + 1, qh::SweepOp{});
+    groups.assign(sp.groups.size(), qh::DGroup{});
+    const uint32_t n_ltab_lds = (uint32_t)(h->bw == 128 ? qh::ltab_lds_count<true>(sp) : qh::ltab_lds_count<false>(sp));
+    qh::build_device_copy(sp, h->bw, n_ltab_lds, ops.data(), groups.data());
+    for (uint32_t v : {(uint32_t)h->bw, (uint32_t)sp.rb, (uint32_t)sp.nwave, (uint32_t)(sp.relayout ? 1 : 0), (uint32_t)sp.ops.size(),
+                       (uint32_t)sp.groups.size()})
+      out.push_back(v);
+    for (size_t k = 0; k < sp.ops.size(); ++k) { out.push_back(ops[k].kind); out.push_back(ops[k].flags); }
+    for (const qh::DGroup &g : groups) out.push_back(g.flags);
+  }
+  if (out.size() & 1) out.push_back(0);
+  const uint64_t bytes = out.size() * 4;
+  if (needed) *needed = bytes;
+  if (buf && cap) {
+    if (cap < bytes) return fail(QH_ERR_ARG, "buffer too small (call with NULL to get the size)");
+    memcpy(buf, out.data(), bytes);
+  }
+  return QH_OK;
+}
+
 }  // extern "C"
 
 // ---- multi-GPU exchange (exchange.hip.h) --------------------------------------------------

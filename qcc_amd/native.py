@@ -89,6 +89,7 @@ SIGNATURES = {
     'qh_timer_laps': (_i32, [_vp, ctypes.POINTER(ctypes.c_float), _i32, ctypes.POINTER(_i32)]),
     'qh_plan_json': (_i32, [_vp, ctypes.c_char_p, _u64, ctypes.POINTER(_u64)]),
     'qh_plan_export': (_i32, [_vp, _vp, _u64, ctypes.POINTER(_u64)]),
+    'qh_plan_handlers': (_i32, [_vp, _vp, _u64, ctypes.POINTER(_u64)]),
     'qh_host_apply1': (_i32, [_vp, _dp, _i32, _i32, _i32]),
     'qh_host_applyc': (_i32, [_vp, _dp, _i32, _i32, _i32, _i32]),
     'qh_host_release': (_i32, []),

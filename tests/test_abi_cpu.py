@@ -91,6 +91,44 @@ def test_shard_semantics_dry(lib):
   lib.qh_destroy(h)
 
 
+def test_plan_handlers_calling_convention_dry(lib):
+  """qh_plan_handlers next to qh_plan_export: size query with NULL, a short buffer refused, nothing launched or cleared,
+  and one (kind, flags) pair per exported op whose low half is the exported kind."""
+  from tests import plan_interp
+  h = ctypes.c_void_p()
+  assert lib.qh_create_dry(10, 128, ctypes.byref(h)) == 0
+  assert lib.qh_set_fusion(h, native.QH_FUSE_SWEEP) == 0
+  had = (ctypes.c_double * 8)(*(np.array([1, 1, 1, -1], dtype=np.complex128) / np.sqrt(2)).view(np.float64))
+  cz = (ctypes.c_double * 8)(1, 0, 0, 0, 0, 0, -1, 0)
+  for q in (0, 3, 9):
+    assert lib.qh_apply1(h, q, had) == 0
+  assert lib.qh_applyc(h, 1, 2, cz) == 0
+  need = ctypes.c_uint64()
+  assert lib.qh_plan_handlers(None, None, 0, ctypes.byref(need)) == native.QH_ERR_ARG
+  assert lib.qh_plan_handlers(h, None, 0, ctypes.byref(need)) == 0 and need.value >= 8 * 4 and need.value % 8 == 0
+  buf = np.zeros(need.value // 4, dtype=np.uint32)
+  assert lib.qh_plan_handlers(h, buf.ctypes.data, need.value - 8, None) == native.QH_ERR_ARG
+  assert lib.qh_plan_handlers(h, buf.ctypes.data, need.value, None) == 0
+  pend = ctypes.c_uint64()
+  assert lib.qh_pending_gates(h, ctypes.byref(pend)) == 0 and pend.value == 4          # neither launched nor cleared
+  sweeps, _ = plan_interp.export_plan(h)
+  assert int(buf[0]) == 0x51484831 and int(buf[1]) == len(sweeps) >= 1
+  pos = 2
+  for sp in sweeps:
+    bw, rb, nwave, relayout, n_ops, n_groups = (int(x) for x in buf[pos:pos + 6])
+    assert (bw, rb, nwave, relayout, n_ops, n_groups) == (128, sp['rb'], sp['nwave'], sp['relayout'], len(sp['ops']), len(sp['groups']))
+    pos += 6
+    for k, op in enumerate(sp['ops']):
+      assert int(buf[pos + 2 * k]) & 0xffff == int(op['kind']) and int(buf[pos + 2 * k]) >> 16 < 192
+    pos += 2 * n_ops + n_groups
+  assert pos in (buf.size, buf.size - 1)
+  lib.qh_destroy(h)
+  small = ctypes.c_void_p()
+  assert lib.qh_create_dry(6, 128, ctypes.byref(small)) == 0
+  assert lib.qh_plan_handlers(small, None, 0, ctypes.byref(need)) == native.QH_ERR_ARG     # no sweeps below 8 qubits
+  lib.qh_destroy(small)
+
+
 def test_bitmap_roundtrip_dry(lib):
   h = ctypes.c_void_p()
   assert lib.qh_create_dry(6, 128, ctypes.byref(h)) == 0
