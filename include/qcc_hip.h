@@ -137,6 +137,20 @@ int qh_apply_bits(qh_handle h, uint64_t ctl_mask, int tgt_bit,
  * index: nothing changes).  A control on a shard bit is dropped where met, and the call is a counted no-op where not. */
 int qh_apply_matrix(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, const double *matrix);
 
+/* Gates selected by a table (kernels_mux.hip.h): one read and one write of the state for any k, 0 <= k <= 16.
+ * gates: 2^k gates of 8 doubles (row-major a b c d, as everywhere).  For every index, s = the value of the selection
+ * bits (bit j of s = LOGICAL bit sel_bits[j], sel_bits[0] least significant); gates[s] is applied to LOGICAL bit tgt_bit.
+ * k = 0 (sel_bits may be NULL) is a plain uncontrolled gate.  Any matrices, unitary or not.  A barrier: what is queued runs
+ * first, and the call works on the layout it finds (no re-layout).  The caller's table is not referenced after the call
+ * returns.  One kernel, counted as one gate; bytes_swept = bytes_algorithmic = the state once read and once written.
+ * A selection bit held by the shard index is fixed per shard: only the entries that agree with the shard index are used.
+ * Errors: QH_ERR_ARG (null pointer, k out of range, dry handle), QH_ERR_BAD_QUBIT, QH_ERR_SAME_QUBIT (a bit twice, the
+ * target among the selectors), QH_ERR_NONLOCAL (the target held by the shard index: nothing changes, nothing is flushed). */
+int qh_apply_mux(qh_handle h, int k, const int32_t *sel_bits, int tgt_bit, const double *gates);
+/* values: 2^k complex numbers (interleaved re,im); a_i *= values[s(i)], s gathered from bits[] the same way (any bit may
+ * be held by the shard index).  k = 0 is qh_scale.  Otherwise as qh_apply_mux.                                        */
+int qh_apply_diag(qh_handle h, int k, const int32_t *bits, const double *values);
+
 /* The whole stream in one call: ops[2k] = control qubit of gate k or QH_NO_CTL (then qh_apply1), ops[2k+1] =
  * target qubit, gates + 8k = its 8 doubles -- exactly `count` qh_apply1/qh_applyc calls (xgates.cc:89-145), without
  * the per-call cost of the host language's FFI (ctypes: ~3 us per gate).  Stops at the first error.          */

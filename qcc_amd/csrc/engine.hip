@@ -23,6 +23,7 @@
 #include "../../include/qcc_hip.h"
 #include "kernels_gate.hip.h"
 #include "kernels_dense.hip.h"
+#include "kernels_mux.hip.h"
 #include "kernels_measure.hip.h"
 #include "kernels_expect.hip.h"
 #include "planner.h"
@@ -85,6 +86,12 @@ struct qh_state_s {
   hipEvent_t mat_ev[kMatSlots] = {};
   bool mat_used[kMatSlots] = {};
   unsigned mat_next = 0;
+  // qh_apply_mux / qh_apply_diag: one pinned staging buffer and one device table, grown on demand (a k = 16 mux table is
+  // 4 MiB: the ring's slots are too small); reused only after the event recorded behind the kernel that read the table
+  void *tab_host = nullptr, *tab_dev = nullptr;
+  size_t tab_cap = 0;
+  hipEvent_t tab_ev = nullptr;
+  bool tab_used = false;
   void *d_meas = nullptr;      // qh_marginal / qh_sample scratch (slab, chunk sums, shot lists), grown on demand
   size_t meas_bytes = 0;
   uint64_t amp_bytes() const { return bw == 128 ? 16 : 8; }
@@ -667,7 +674,7 @@ int select_device(int device) {
 extern "C" {
 
 const char *qh_last_error(void) { return g_err.c_str(); }
-int qh_version(void) { return 108; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
+int qh_version(void) { return 109; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
 
 int qh_device_count(int *count) {
   if (!count) return fail(QH_ERR_ARG, "null");
@@ -802,6 +809,9 @@ int qh_destroy(qh_handle h) {
     for (hipEvent_t e : h->mat_ev) if (e) (void)hipEventDestroy(e);
     if (h->mat_dev) (void)hipFree(h->mat_dev);
     if (h->mat_host) (void)hipHostFree(h->mat_host);
+    if (h->tab_ev) (void)hipEventDestroy(h->tab_ev);
+    if (h->tab_dev) (void)hipFree(h->tab_dev);
+    if (h->tab_host) (void)hipHostFree(h->tab_host);
     if (h->d_meas) (void)hipFree(h->d_meas);
     for (hipEvent_t e : h->laps) (void)hipEventDestroy(e);
     if (h->owns_mem && h->d_psi) (void)hipFree(h->d_psi);
@@ -1539,6 +1549,181 @@ int qh_apply_matrix(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, 
   h->stats.gates_submitted++;
   count_kernel(h, 1ull << (h->nloc - __builtin_popcountll(cm_all)), a.nwork << k);
   return QH_OK;
+}
+
+}  // extern "C"
+
+// ---- table-selected gates: qh_apply_mux, qh_apply_diag (kernels_mux.hip.h) --------------------------------------------
+namespace {
+
+// What a call makes of its k selection bits on this handle: the bits held by the shard index are fixed (`fixed`: their
+// table bits that are 1 on this shard), the others keep their order and number the entries of the restricted table
+// (`tbits`: the table bits they had); `g` gathers the restricted index from a physical amplitude index.
+struct TabPlan {
+  qh::TabGather g{};
+  int kl = 0;
+  uint32_t fixed = 0, tbits = 0;
+  uint64_t local_pos = 0;      // physical positions of the local selection bits
+};
+
+TabPlan plan_table(const qh_state_s *h, int k, const int32_t *bits) {
+  TabPlan t;
+  std::vector<std::pair<int, int>> loc;       // (physical position, bit of the restricted index)
+  for (int j = 0; j < k; ++j) {
+    const Placed b = place_bit(h, bits[j]);
+    if (b.held) {
+      if (h->shard & b.held) t.fixed |= 1u << j;
+    } else {
+      loc.push_back({h->perm[bits[j]], t.kl++});
+      t.tbits |= 1u << j;
+      t.local_pos |= b.local;
+    }
+  }
+  std::sort(loc.begin(), loc.end());
+  for (size_t i = 0; i < loc.size();) {       // a run: adjacent positions that feed adjacent table bits
+    size_t e = i + 1;
+    while (e < loc.size() && loc[e].first == loc[i].first + (int)(e - i) && loc[e].second == loc[i].second + (int)(e - i)) ++e;
+    t.g.run[t.g.n++] = (uint32_t)loc[i].first | ((uint32_t)loc[i].second << 8) | ((uint32_t)(e - i) << 16);
+    i = e;
+  }
+  return t;
+}
+
+// The restricted table (2^kl entries of C complex numbers, picked from the caller's 2^k) in the state's width, into the
+// pinned staging buffer and from there, on the handle's stream, into the device table.  One buffer of each: the
+// previous call's kernel must have read its table before the staging buffer is written again.
+int stage_table(qh_state_s *h, const TabPlan &t, int C, const double *src, const void **dev) {
+  if (!h->tab_ev) HIP_TRY(hipEventCreateWithFlags(&h->tab_ev, hipEventDisableTiming));
+  if (h->tab_used) {
+    const int rc = wait_event(h, h->tab_ev, "qh_apply_mux/diag");
+    if (rc) return rc;
+  }
+  const size_t nent = (size_t)1 << t.kl, elem = h->bw == 128 ? 16 : 8, bytes = nent * C * elem;
+  if (h->tab_cap < bytes) {
+    size_t cap = 64u << 10;
+    while (cap < bytes) cap *= 2;
+    if (h->tab_host) (void)hipHostFree(h->tab_host);
+    if (h->tab_dev) (void)hipFree(h->tab_dev);
+    h->tab_host = h->tab_dev = nullptr;
+    h->tab_cap = 0;
+    HIP_TRY(hipHostMalloc(&h->tab_host, cap, hipHostMallocDefault));
+    HIP_TRY(hipMalloc(&h->tab_dev, cap));
+    h->tab_cap = cap;
+  }
+  for (size_t s = 0; s < nent; ++s) {
+    uint32_t full = t.fixed;                    // entry s of the restricted table = entry `full` of the caller's
+    for (uint32_t m = t.tbits, r = (uint32_t)s; m; m &= m - 1, r >>= 1)
+      if (r & 1u) full |= m & (~m + 1u);
+    const double *e = src + (size_t)full * C * 2;
+    if (h->bw == 128) memcpy((char *)h->tab_host + s * C * 16, e, (size_t)C * 16);
+    else
+      for (int i = 0; i < 2 * C; ++i) ((float *)h->tab_host)[s * C * 2 + i] = (float)e[i];
+  }
+  HIP_TRY(hipMemcpyAsync(h->tab_dev, h->tab_host, bytes, hipMemcpyHostToDevice, h->stream));
+  *dev = h->tab_dev;
+  return QH_OK;
+}
+
+// lane_pos: the index positions that vary with the lane inside one wave row of the kernel that will run
+int pick_tier(const TabPlan &t, uint64_t lane_pos, size_t table_bytes) {
+  if (!(t.local_pos & lane_pos)) return qh::TAB_UNIFORM;
+  return table_bytes <= qh::kTabLdsBytes ? qh::TAB_LDS : qh::TAB_GLOBAL;
+}
+
+// tiles of 64 * U work items, one per wave, four waves per block; LDS blocks stage the table first and grid-stride
+unsigned tab_grid(uint64_t nwork, int U, int tier) {
+  const unsigned g = pick_grid(nwork, 256 * U);
+  return tier == qh::TAB_LDS ? std::min(g, 2048u) : g;
+}
+
+template <typename R, int TIER>
+void launch_tab_tier(qh_state_s *h, int kind, const qh::TabArgs &a, const void *tab, size_t lds) {
+  using A = typename qh::AmpT<R>::type;
+  const size_t sm = TIER == qh::TAB_LDS ? lds : 0;
+  if (kind == 0)
+    hipLaunchKernelGGL((qh::k_mux_pair<R, TIER>), dim3(tab_grid(a.nwork, 4, TIER)), dim3(256), sm, h->stream, (A *)h->d_psi, (const A *)tab, a);
+  else if (kind == 1)
+    hipLaunchKernelGGL((qh::k_mux_line<R, TIER>), dim3(tab_grid(a.nwork, 8, TIER)), dim3(256), sm, h->stream, (A *)h->d_psi, (const A *)tab, a);
+  else
+    hipLaunchKernelGGL((qh::k_diag_tab<R, TIER>), dim3(tab_grid(a.nwork, 16, TIER)), dim3(256), sm, h->stream, (A *)h->d_psi, (const A *)tab, a);
+}
+
+// kind: 0 k_mux_pair, 1 k_mux_line, 2 k_diag_tab
+template <typename R>
+void launch_tab(qh_state_s *h, int kind, int tier, const qh::TabArgs &a, const void *tab, size_t lds) {
+  if (tier == qh::TAB_UNIFORM) launch_tab_tier<R, qh::TAB_UNIFORM>(h, kind, a, tab, lds);
+  else if (tier == qh::TAB_LDS) launch_tab_tier<R, qh::TAB_LDS>(h, kind, a, tab, lds);
+  else launch_tab_tier<R, qh::TAB_GLOBAL>(h, kind, a, tab, lds);
+}
+
+// argument checks shared by the two calls: the target of a mux (has_tgt) must not be among the bits
+int check_tab_bits(const qh_state_s *h, const char *who, int k, const int32_t *bits, bool has_tgt, int extra) {
+  if (k < 0 || k > qh::kMaxMuxBits) return fail(QH_ERR_ARG, "%s: k = %d outside [0,%d]", who, k, qh::kMaxMuxBits);
+  if (k > 0 && !bits) return fail(QH_ERR_ARG, "%s: null bit list", who);
+  uint64_t seen = 0;
+  for (int j = 0; j < k; ++j)
+    if (bits[j] < 0 || bits[j] >= h->nglob) return fail(QH_ERR_BAD_QUBIT, "%s: bit %d out of range [0,%d)", who, bits[j], h->nglob);
+  if (has_tgt && (extra < 0 || extra >= h->nglob)) return fail(QH_ERR_BAD_QUBIT, "%s: target bit %d out of range [0,%d)", who, extra, h->nglob);
+  for (int j = 0; j < k; ++j) {
+    if ((seen >> bits[j]) & 1ull) return fail(QH_ERR_SAME_QUBIT, "%s: bit %d appears twice", who, bits[j]);
+    seen |= 1ull << bits[j];
+  }
+  if (has_tgt && ((seen >> extra) & 1ull)) return fail(QH_ERR_SAME_QUBIT, "%s: target bit %d is among the selection bits", who, extra);
+  return QH_OK;
+}
+
+// the tail of both calls: stage, launch one kernel, record the event, count
+int run_tab(qh_state_s *h, int kind, const TabPlan &t, uint64_t lane_pos, int C, const double *src, qh::TabArgs a) {
+  const size_t bytes = ((size_t)C << t.kl) * h->amp_bytes();
+  const int tier = pick_tier(t, lane_pos, bytes);
+  a.g = t.g;
+  a.nent = 1u << t.kl;
+  const void *dtab = nullptr;
+  int rc = stage_table(h, t, C, src, &dtab);
+  if (rc) return rc;
+  with_real(h, [&](auto x) { launch_tab<decltype(x)>(h, kind, tier, a, dtab, bytes); });
+  if ((rc = check_launch(h))) return rc;
+  HIP_TRY(hipEventRecord(h->tab_ev, h->stream));
+  h->tab_used = true;
+  h->stats.gates_submitted++;
+  count_kernel(h, 1ull << h->nloc, 1ull << h->nloc);
+  return QH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qh_apply_mux(qh_handle h, int k, const int32_t *sel_bits, int tgt_bit, const double *gates) {
+  if (!h || !gates) return fail(QH_ERR_ARG, "apply_mux: null handle or gates");
+  int rc = check_tab_bits(h, "apply_mux", k, sel_bits, true, tgt_bit);
+  if (rc) return rc;
+  // (a logical bit stays local or in the shard index whatever the relayout sweeps do)
+  if (h->perm[tgt_bit] >= h->nloc)
+    return fail(QH_ERR_NONLOCAL, "apply_mux: target bit %d is held by the shard index (physical bit %d, local bits: %d); exchange first",
+                tgt_bit, h->perm[tgt_bit], h->nloc);
+  if ((rc = enter(h))) return rc;          // a barrier: what is queued runs first, on whatever layout it leaves
+  const TabPlan t = plan_table(h, k, sel_bits);
+  qh::TabArgs a{};
+  a.p = h->perm[tgt_bit];
+  if (a.p < 3) {                           // inside the line: one amplitude per lane
+    a.nwork = 1ull << h->nloc;
+    return run_tab(h, 1, t, 0x3full, 4, gates, a);
+  }
+  a.nwork = 1ull << (h->nloc - 1);
+  const uint64_t low = (1ull << a.p) - 1ull;
+  return run_tab(h, 0, t, ((0x3full & ~low) << 1) | (0x3full & low), 4, gates, a);
+}
+
+int qh_apply_diag(qh_handle h, int k, const int32_t *bits, const double *values) {
+  if (!h || !values) return fail(QH_ERR_ARG, "apply_diag: null handle or values");
+  int rc = check_tab_bits(h, "apply_diag", k, bits, false, 0);
+  if (rc) return rc;
+  if ((rc = enter(h))) return rc;
+  const TabPlan t = plan_table(h, k, bits);
+  qh::TabArgs a{};
+  a.nwork = 1ull << h->nloc;
+  return run_tab(h, 2, t, 0x3full, 1, values, a);
 }
 
 }  // extern "C"

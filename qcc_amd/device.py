@@ -206,6 +206,28 @@ class DeviceState:
     native.check(self.lib.qh_apply_matrix(self.h, k, bits.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(ctl_mask),
                                           m.ctypes.data_as(_dp)))
 
+  def apply_mux(self, gates, sel_bits, tgt_bit):
+    """Multiplexed 2x2 (qh_apply_mux): `gates` of shape (2^k, 2, 2); for every index, s = the value of the LOGICAL
+    selection bits (sel_bits[0] the least significant bit of s) and gates[s] is applied to LOGICAL bit tgt_bit.
+    0 <= k <= 16; one read and one write of the state for any k."""
+    sel = np.ascontiguousarray([int(b) for b in sel_bits], dtype=np.int32)
+    k = len(sel)
+    g = np.ascontiguousarray(gates, dtype=np.complex128)
+    if g.shape != (1 << k, 2, 2):
+      raise ValueError(f'apply_mux: gates of shape {g.shape} for {k} selection bits (want ({1 << k}, 2, 2))')
+    native.check(self.lib.qh_apply_mux(self.h, k, sel.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(tgt_bit),
+                                       g.ctypes.data_as(_dp)))
+
+  def apply_diag(self, values, bits):
+    """a_i *= values[s(i)] (qh_apply_diag): 2^k complex values, s gathered from the LOGICAL bits `bits` (bits[0] the
+    least significant bit of s).  0 <= k <= 16."""
+    b = np.ascontiguousarray([int(x) for x in bits], dtype=np.int32)
+    k = len(b)
+    v = np.ascontiguousarray(values, dtype=np.complex128)
+    if v.shape != (1 << k,):
+      raise ValueError(f'apply_diag: values of shape {v.shape} for {k} bits (want ({1 << k},))')
+    native.check(self.lib.qh_apply_diag(self.h, k, b.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), v.ctypes.data_as(_dp)))
+
   def apply_bits_raw(self, ctl_mask, tgt_bit, addr):
     """apply_bits with the gate given as the address of 8 contiguous doubles."""
     rc = self.lib.qh_apply_bits(self.h, ctl_mask, tgt_bit, ctypes.cast(addr, _dp))

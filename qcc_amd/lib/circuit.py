@@ -75,6 +75,7 @@ def _u1_operator(value):
 
 
 _DENSE_MAX_BITS = 6        # qh_apply_matrix: dense operators on up to 6 qubits run on the device
+_TABLE_MAX_BITS = 16       # qh_apply_mux / qh_apply_diag: tables over up to 16 qubits
 _MARGINAL_MAX_BITS = 16    # qh_marginal: registers of up to 16 qubits (2^16 probabilities)
 
 
@@ -598,6 +599,73 @@ class qc:
             mask |= 1 << (n - 1 - c)
         dev.apply_matrix(np.asarray(ops.Operator(op)), [n - 1 - q for q in reversed(qubits)], mask)
         self._gate_done()
+
+    # table-selected gates (extensions with the standing of apply_matrix: eager, one kernel each on the device).  In all
+    # four the FIRST listed qubit is the most significant bit of the table index (np.kron order, as apply_matrix).
+    def _table_device(self, who, method, qubits, nentries, tgt=None):
+        """Checks the qubit lists, drains what is queued and returns (device, logical bits, least significant first)."""
+        qubits = [int(q) for q in qubits]
+        every = qubits + ([int(tgt)] if tgt is not None else [])
+        if len(qubits) > _TABLE_MAX_BITS:
+            raise ValueError(f'{who}: {len(qubits)} selection qubits (at most {_TABLE_MAX_BITS})')
+        if nentries != 1 << len(qubits):
+            raise ValueError(f'{who}: a table of {nentries} entries for {len(qubits)} qubits (want {1 << len(qubits)})')
+        if any(q < 0 or q >= self._nbits for q in every):
+            raise ValueError(f'{who}: qubits {every} out of range for {self._nbits} qubits')
+        if len(set(every)) != len(every):
+            raise ValueError(f'{who}: a qubit appears twice in {every}')
+        dev = self._ensure_device()
+        if not hasattr(dev, method):
+            raise NotImplementedError(f'{who}: {type(dev).__name__} has no {method}')
+        n = self._nbits
+        return dev, [n - 1 - q for q in reversed(qubits)]
+
+    def multiplex(self, gates, sel, tgt):
+        """Uniformly controlled gate: gates[s] (2^k operators of shape (2, 2)) on qubit `tgt`, s the value of the
+        qubits `sel` (sel[0] the most significant bit of s).  One pass over the state for any k <= 16."""
+        g = np.asarray(gates, dtype=np.complex128)
+        if g.ndim != 3 or g.shape[1:] != (2, 2):
+            raise ValueError(f'multiplex: gates of shape {g.shape} (want (2^k, 2, 2))')
+        dev, bits = self._table_device('multiplex', 'apply_mux', sel, g.shape[0], tgt)
+        dev.apply_mux(g, bits, self._nbits - 1 - int(tgt))
+        self._gate_done()
+
+    def diagonal(self, values, qubits):
+        """Multiplies every amplitude by values[s], s the value of `qubits` (qubits[0] the most significant bit)."""
+        v = np.asarray(values, dtype=np.complex128)
+        if v.ndim != 1:
+            raise ValueError(f'diagonal: values of shape {v.shape} (want (2^k,))')
+        dev, bits = self._table_device('diagonal', 'apply_diag', qubits, v.shape[0])
+        dev.apply_diag(v, bits)
+        self._gate_done()
+
+    @staticmethod
+    def _truth_table(f, k):
+        """f as 2^k values 0/1, entry s for the bits of s with xs[0] the most significant: a callable with OracleUf's
+        convention (a list of bits, bits[0] the value of qubit xs[0]; evaluated 2^k times on the host) or a sequence."""
+        if callable(f):
+            return np.array([1 if f(helper.val2bits(s, k)) else 0 for s in range(1 << k)], dtype=np.int64)
+        t = np.asarray(f).reshape(-1)
+        if t.shape[0] != 1 << k or np.any((t != 0) & (t != 1)):
+            raise ValueError(f'oracle: a table of {t.shape[0]} entries for {k} qubits (want {1 << k} values 0/1)')
+        return t.astype(np.int64)
+
+    def oracle(self, f, xs, y):
+        """Bit oracle |x>|y> -> |x>|y xor f(x)> as a multiplexed X / I on qubit y selected by the qubits xs."""
+        xs = list(xs)
+        if len(xs) > _TABLE_MAX_BITS:
+            raise ValueError(f'oracle: {len(xs)} input qubits (at most {_TABLE_MAX_BITS})')
+        t = self._truth_table(f, len(xs))
+        xi = np.stack([np.eye(2), np.array([[0.0, 1.0], [1.0, 0.0]])]).astype(np.complex128)
+        self.multiplex(xi[t], xs, y)
+
+    def phase_oracle(self, f, xs):
+        """The diagonal (-1)^f(x) over the qubits xs."""
+        xs = list(xs)
+        if len(xs) > _TABLE_MAX_BITS:
+            raise ValueError(f'phase_oracle: {len(xs)} input qubits (at most {_TABLE_MAX_BITS})')
+        t = self._truth_table(f, len(xs))
+        self.diagonal(1.0 - 2.0 * t, xs)
 
     # ------------------------------------------------------------------ readers / measurement
     def maxprob(self):

@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB_PATH = os.environ.get('QCC_HIP_LIB') or os.path.join(PKG, 'libqcc_hip.so')  # env: A/B builds only
 SOURCES = [os.path.join(PKG, 'csrc', f) for f in
-           ('engine.hip', 'kernels_gate.hip.h', 'kernels_dense.hip.h', 'kernels_measure.hip.h', 'kernels_expect.hip.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h',
+           ('engine.hip', 'kernels_gate.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_measure.hip.h', 'kernels_expect.hip.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h',
             'sweep_island_rb2.inc', 'sweep_island_rb3.inc', 'sweep_island_rb4.inc',
             'sweep_island_rb5.inc', 'sweep_island_f32_rb2.inc', 'sweep_island_f32_rb3.inc',
             'sweep_island_f32_rb4.inc', 'sweep_island_f32_rb5.inc', 'sweep_island_f32_rb6.inc', 'sweep_handlers.inc',
@@ -59,6 +59,8 @@ SIGNATURES = {
     'qh_applyc': (_i32, [_vp, _i32, _i32, _dp]),
     'qh_apply_bits': (_i32, [_vp, _u64, _i32, _dp]),
     'qh_apply_matrix': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _u64, _dp]),
+    'qh_apply_mux': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _i32, _dp]),
+    'qh_apply_diag': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _dp]),
     'qh_set_fusion': (_i32, [_vp, _i32]),
     'qh_set_relayout': (_i32, [_vp, _i32, ctypes.POINTER(_i32)]),
     'qh_apply_stream': (_i32, [_vp, _u64, ctypes.POINTER(ctypes.c_int32), _dp]),
