@@ -472,10 +472,16 @@ bool layout_is_canonical(const qh_state_s *h) {
 }
 
 // Brings the local index bits back into ascending logical order (one gather pass into the second
-// buffer): for the entry points that hand out or take amplitudes in physical order.
+// buffer): for the entry points that hand out or take amplitudes in physical order.  A handle that keeps no second buffer
+// (no flush has asked for one yet, relayout off, attached or host-mapped memory: qh_remap_swap alone can put its local bits
+// out of order) borrows one for the pass: the result is copied back, so d_psi stays where the caller knows it, and the
+// buffer is freed again.
 int canonicalize(qh_state_s *h) {
   if (h->dry || layout_is_canonical(h)) return QH_OK;
-  if (!h->d_alt) return fail(QH_ERR_ARG, "internal: permuted layout without a second buffer");
+  const bool borrowed = !h->d_alt;
+  if (borrowed && !alloc_second_buffer(h))
+    return fail(QH_ERR_NOMEM, "no room for the second buffer of %llu bytes that bringing a permuted layout back to canonical order needs",
+                (unsigned long long)(h->amp_bytes() << h->nloc));
   std::vector<int> loc;                       // logical bits that live on local positions, ascending
   for (int b = 0; b < h->nglob; ++b) if (h->perm[b] < h->nloc) loc.push_back(b);
   std::vector<int> posn;                      // the local positions they occupy, ascending
@@ -491,8 +497,19 @@ int canonicalize(qh_state_s *h) {
     hipLaunchKernelGGL(qh::k_permute_bits<R>, dim3(grid_for(n, 1ull << 22)), dim3(256), 0, h->stream, (const A *)h->d_psi, (A *)h->d_alt, n, bp);
   });
   int rc = check_launch(h);
+  if (rc == QH_OK && borrowed) {
+    hipError_t e = hipMemcpyAsync(h->d_psi, h->d_alt, (size_t)h->amp_bytes() << h->nloc, hipMemcpyDefault, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) rc = fail(QH_ERR_HIP, hipGetErrorString(e));
+  }
+  if (borrowed) {
+    if (rc) (void)hipStreamSynchronize(h->stream);      // (the gather may still be reading or writing)
+    (void)hipFree(h->d_alt);
+    h->d_alt = nullptr;
+  } else if (rc == QH_OK) {
+    std::swap(h->d_psi, h->d_alt);
+  }
   if (rc) return rc;
-  std::swap(h->d_psi, h->d_alt);
   for (size_t k = 0; k < loc.size(); ++k) h->perm[loc[k]] = posn[k];
   return QH_OK;
 }

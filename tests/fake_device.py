@@ -344,3 +344,190 @@ class NumpyShardEngine:
 
   def reset_stats(self):
     self.n_gates = 0
+
+
+# ---- register readout: NumPy references and stand-ins with marginal / sample / project_bits ---------------------------
+def np_marginal(psi, bits, base=0):
+  """marginal of the logical bits; psi holds indices base .. base + size - 1"""
+  p = np.abs(np.asarray(psi, dtype=np.complex128)) ** 2
+  idx = np.uint64(base) + np.arange(p.size, dtype=np.uint64)
+  j = np.zeros_like(idx)
+  for t, b in enumerate(bits):
+    j |= ((idx >> np.uint64(b)) & np.uint64(1)) << np.uint64(t)
+  return np.bincount(j.astype(np.int64), weights=p, minlength=1 << len(bits))
+
+
+def np_sample(psi, u, base=0):
+  p = np.abs(np.asarray(psi, dtype=np.complex128)) ** 2
+  cdf = np.cumsum(p)
+  assert cdf[-1] > 0
+  i = np.minimum(np.searchsorted(cdf, np.asarray(u) * cdf[-1], side='right'), np.flatnonzero(p)[-1])
+  return (np.uint64(base) + i.astype(np.uint64)).astype(np.uint64)
+
+
+def np_keep(size, mask, value, base=0):
+  idx = np.uint64(base) + np.arange(size, dtype=np.uint64)
+  return (idx & np.uint64(mask)) == np.uint64(value)
+
+
+class MeasureOracle(OracleDevice):
+  """OracleDevice with the three readout methods, in NumPy (logical order = the array's order)."""
+
+  def marginal(self, bits):
+    return np_marginal(self.psi, bits)
+
+  def sample(self, u):
+    return np_sample(self.psi, u)
+
+  def project_bits(self, mask, value):
+    self.psi[~np_keep(self.psi.size, mask, value)] = 0
+
+
+class MeasureShardEngine(NumpyShardEngine):
+  """NumpyShardEngine with the readout methods, shard bits resolved as qh_marginal / qh_sample / qh_project_bits do
+  (tests/test_gpu_shard_readout.py holds the HIP engine to the same answers)."""
+
+  def marginal(self, bits):
+    return np_marginal(self.psi, bits, self.shard << self.nbits)
+
+  def sample(self, u):
+    return np_sample(self.psi, u, self.shard << self.nbits)
+
+  def project_bits(self, mask, value):
+    self.psi[~np_keep(self.psi.size, mask, value, self.shard << self.nbits)] = 0
+
+
+def readout_circuit(nq, seed):
+  from qcc_amd.lib import circuit
+  rng = np.random.default_rng(seed)
+  q = circuit.qc('m')
+  q.reg(nq, 0)
+  for _ in range(3 * nq):
+    a = int(rng.integers(nq))
+    q.ry(a, float(rng.random() * 3))
+    b = int(rng.integers(nq))
+    if b != a:
+      q.cx(a, b)
+    q.rz(int(rng.integers(nq)), float(rng.random() * 3))
+  return q
+
+
+def _shard_qubits(q):
+  """qubits whose logical bit the shard index holds now (the router's map), after the queued gates have been routed"""
+  st = q._ensure_device().st                             # pylint: disable=protected-access
+  return [qb for qb in range(q.nbits) if st.perm[q.nbits - 1 - qb] >= st.nloc]
+
+
+def sharded_readout_worker(rank, n, out_dir, device_factory, layer=False):
+  """One rank of the sharded readout test, inside an initialised process group: qc.probabilities / sample / measure
+  through qcc_amd.sharded.ShardedDevice over whatever engine device_factory builds it on (the NumPy stand-in for the CPU
+  test, the HIP engine on the GPU); what it saw goes to out_dir/r<rank>.npz for check_sharded_readout.  layer=True: the
+  layer's other readers too (prob_bit / project_bit on a held and on a local bit, amplitude, argmax, init_product)."""
+  import os
+  from qcc_amd.lib import backend, tensor
+  tensor.set_tensor_width(128)
+  backend.set_device_factory(device_factory)
+  q = readout_circuit(n, 5)
+  q.h(0)                                                  # dense gates on the top qubits: shard bits get exchanged
+  q.cx(0, n - 1)
+  res = {'psi': np.asarray(q.psi).copy()}
+  sq = _shard_qubits(q)                                   # registers that include qubits held by the shard index
+  local = [qb for qb in range(n) if qb not in sq]
+  regs = {'shard': sq, 'mixed': [local[0], sq[0], local[-1]], 'local': local[:2]}
+  for name, qubits in regs.items():
+    res['q_' + name] = np.array(qubits)
+    res['p_' + name] = q.probabilities(qubits)
+  res['shots'] = q.sample(3000, [0, 2, n - 1], seed=9)
+  res['full'] = q.sample(3000, seed=9)
+  # seed=None: every rank's global stream differs; the ranks still agree (rank 0's draws)
+  np.random.seed(100 + rank)
+  res['shots_none'] = q.sample(2000, [1, n - 1])
+  res['mq'] = np.array(regs['mixed'])
+  res['shard_before_measure'] = np.array(_shard_qubits(q))
+  res['m1'] = np.array(q.measure(regs['mixed']))
+  res['after'] = np.asarray(q.psi).copy()
+  if layer:
+    dev = q._ensure_device()                              # pylint: disable=protected-access
+    st = dev.st
+    hb = [b for b in range(n) if st.perm[b] >= st.nloc][0]       # LOGICAL bits, one held by the shard index, one local
+    lb = [b for b in range(n) if st.perm[b] < st.nloc][n // 2]
+    res['bits'] = np.array([hb, lb])
+    res['prob_bit'] = np.array([dev.prob_bit(b, v) for b in (hb, lb) for v in (0, 1)])
+    res['argmax'] = np.array(dev.argmax())
+    res['amp_idx'] = np.array([0, (1 << n) - 1, int(res['argmax'][0]), 0x2A5A5 & ((1 << n) - 1)])
+    res['amps'] = np.array([dev.amplitude(int(i)) for i in res['amp_idx']])
+    res['perm_held'] = np.array([st.perm[hb], st.nloc])
+    dev.project_bit(lb, 1)
+    res['proj_local'] = np.asarray(dev.download()).copy()
+    dev.project_bit(hb, 0)
+    res['proj_held'] = np.asarray(dev.download()).copy()
+    rng = np.random.default_rng(3)
+    tabs = [rng.standard_normal(1 << k) + 1j * rng.standard_normal(1 << k) for k in (3, 2)]
+    tabs = [t / np.linalg.norm(t) for t in tabs]
+    dev.init_product([(3, tabs[0]), (n - 5, 0b1011), (2, tabs[1])])
+    res['product'] = np.asarray(dev.download()).copy()
+    res['product_want'] = np.kron(np.kron(tabs[0], np.eye(1 << (n - 5))[0b1011]), tabs[1])
+  np.savez(os.path.join(out_dir, f'r{rank}.npz'), **res)
+
+
+def _project(psi, n, qubits, value):
+  idx = np.arange(1 << n)
+  keep = np.ones(1 << n, dtype=bool)
+  for t, qb in enumerate(qubits):
+    keep &= ((idx >> (n - 1 - qb)) & 1) == ((value >> (len(qubits) - 1 - t)) & 1)
+  return np.where(keep, psi, 0)
+
+
+def check_sharded_readout(out_dir, world, n, atol, layer=False):
+  """What the ranks of sharded_readout_worker saw against the single-process NumPy answer."""
+  import os
+  from qcc_amd.lib import backend, circuit, tensor
+  res = [dict(np.load(os.path.join(out_dir, f'r{r}.npz'))) for r in range(world)]
+  for r in res[1:]:
+    for k, v in res[0].items():
+      assert np.array_equal(v, r[k]), k                  # every rank returns the same, seed=None included
+  r0 = res[0]
+  psi = r0['psi']
+  g = world.bit_length() - 1
+  assert len(r0['q_shard']) == g                          # the shard-bit paths of engine and router ran
+  assert set(r0['mq'].tolist()) & set(r0['shard_before_measure'].tolist())
+  tensor.set_tensor_width(128)
+  backend.set_device_factory(MeasureOracle)
+  try:
+    q = circuit.qc('single')
+    q.psi = psi
+    for name in ('shard', 'mixed', 'local'):
+      np.testing.assert_allclose(r0['p_' + name], q.probabilities(r0['q_' + name].tolist()), atol=atol)
+    # the CDF runs in the sharded layout's physical order (rank order, then the router's bit map): the shots follow the
+    # single-process distribution, not its exact sequence
+    p_full = np.abs(psi) ** 2
+    assert np.all(p_full[r0['full'].astype(np.int64)] > 0)
+    freq = np.bincount(r0['full'].astype(np.int64), minlength=1 << n) / 3000
+    assert np.max(np.abs(freq - p_full)) < 0.05
+    reg = (((r0['full'] >> np.uint64(n - 1)) & np.uint64(1)) << np.uint64(2)) | \
+        (((r0['full'] >> np.uint64(n - 3)) & np.uint64(1)) << np.uint64(1)) | (r0['full'] & np.uint64(1))
+    assert reg.tolist() == r0['shots'].tolist()            # the same uniforms: the register is the bits of the full shot
+    pn = q.probabilities([1, n - 1])
+    assert np.all(pn[r0['shots_none'].astype(np.int64)] > 0)
+    mq = r0['mq'].tolist()
+    value, prob = int(r0['m1'][0]), float(r0['m1'][1])
+    assert abs(prob - q.probabilities(mq)[value]) < atol and prob > 0
+    np.testing.assert_allclose(r0['after'], _project(psi, n, mq, value) / np.sqrt(prob), atol=atol)
+  finally:
+    backend.set_device_factory(None)
+    tensor.set_tensor_width(None)
+  if layer:
+    after = r0['after']
+    hb, lb = (int(b) for b in r0['bits'])
+    assert int(r0['perm_held'][0]) >= int(r0['perm_held'][1])
+    idx = np.arange(1 << n)
+    pa = np.abs(after) ** 2
+    want = [float(pa[((idx >> b) & 1) == v].sum()) for b in (hb, lb) for v in (0, 1)]
+    np.testing.assert_allclose(r0['prob_bit'], want, atol=atol)
+    k = int(np.argmax(pa))
+    assert int(r0['argmax'][0]) == k and abs(float(r0['argmax'][1]) - pa[k]) < atol
+    np.testing.assert_allclose(r0['amps'], after[r0['amp_idx'].astype(np.int64)], atol=atol)
+    proj = np.where(((idx >> lb) & 1) == 1, after, 0)
+    assert np.array_equal(r0['proj_local'], proj)           # zeros are zeros, the rest is untouched
+    assert np.array_equal(r0['proj_held'], np.where(((idx >> hb) & 1) == 0, proj, 0))
+    np.testing.assert_allclose(r0['product'], r0['product_want'], atol=atol)

@@ -19,6 +19,7 @@ import pytest
 
 from qcc_amd import device, native, workloads
 from tests.product_oracle import ProductState
+from tests.shard_util import phys_to_logical as _phys_to_logical
 
 pytestmark = pytest.mark.gpu
 
@@ -52,17 +53,6 @@ def _windows(st, rng, count=12, width=2048):
   idx = np.concatenate([np.arange(o, o + width, dtype=np.uint64) for o in offs])
   amp = np.concatenate([st.download(o, width) for o in offs])
   return idx, amp
-
-
-def _phys_to_logical(st, shard, local_idx, nglob):
-  perm = (np.zeros(nglob, dtype=np.int32))
-  import ctypes
-  native.check(st.lib.qh_get_bitmap(st.h, perm.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
-  phys = (np.uint64(shard) << np.uint64(st.nbits)) | local_idx
-  out = np.zeros_like(phys)
-  for b in range(nglob):
-    out |= ((phys >> np.uint64(perm[b])) & np.uint64(1)) << np.uint64(b)
-  return out
 
 
 @pytest.mark.parametrize('shard', [0, 5, 7])

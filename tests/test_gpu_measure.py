@@ -4,7 +4,6 @@ Small registers (n = 4-20, both widths, per-gate and fused runs that leave a per
 physical order, a G-test of a seeded 2^20-shot histogram, qc.probabilities / sample / measure (host-mapped registers
 too), and whole 30-qubit states: a k = 16 marginal of supremacy-30 against a chunked host reduction, the uniform
 marginal of a QFT, GHZ shots, and readers that leave the state as it was."""
-import ctypes
 import math
 
 import numpy as np
@@ -12,23 +11,9 @@ import pytest
 
 from qcc_amd import device, gates, native, workloads
 from qcc_amd.lib import circuit, tensor
+from tests.shard_util import bitmap as _bitmap, check_exact_cdf, logical_of_phys as _logical_of_phys
 
 pytestmark = pytest.mark.gpu
-
-def _bitmap(st):
-  bm = (ctypes.c_int32 * st.nbits)()
-  native.check(st.lib.qh_get_bitmap(st.h, bm))
-  return [int(b) for b in bm]
-
-
-def _logical_of_phys(bm, size):
-  """logical index of every physical index 0..size-1 under the bit map bm (physical bit of each logical bit)"""
-  i = np.arange(size, dtype=np.uint64)
-  out = np.zeros_like(i)
-  for b, p in enumerate(bm):
-    out |= ((i >> np.uint64(p)) & np.uint64(1)) << np.uint64(b)
-  return out
-
 
 def _logical_state(st):
   """the whole (small) state in LOGICAL order, whatever layout the download leaves"""
@@ -114,19 +99,9 @@ def _check_exact_cdf(st, u):
   lstate = _logical_state(st)
   lphys = _logical_of_phys(bm, lstate.size).astype(np.int64)       # logical index of each physical one
   pp = np.abs(lstate[lphys]) ** 2
-  cdf = np.cumsum(pp)
-  total = cdf[-1]
-  x = u * total
-  exp_phys = np.minimum(np.searchsorted(cdf, x, side='right'), np.flatnonzero(pp)[-1])
   phys_of_logical = np.empty(lstate.size, dtype=np.int64)
   phys_of_logical[lphys] = np.arange(lstate.size)
-  g = phys_of_logical[got.astype(np.int64)]
-  assert np.all(pp[g] > 0)                                            # never a zero amplitude
-  bad = g != exp_phys
-  if bad.any():                                                       # ties at a boundary may go to either side
-    lo = np.where(g > 0, cdf[np.maximum(g - 1, 0)], 0.0)
-    ok = (lo[bad] - 1e-12 * total <= x[bad]) & (x[bad] < cdf[g[bad]] + 1e-12 * total)
-    assert ok.all(), (np.flatnonzero(bad)[:5], g[bad][:5], exp_phys[bad][:5])
+  check_exact_cdf(pp, phys_of_logical[got.astype(np.int64)], u)
   return got, lstate
 
 

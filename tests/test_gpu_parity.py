@@ -244,24 +244,32 @@ def test_host_dropin_scratch_lifetime(oracle):
   lib.qh_host_release()
 
 
-def test_readers(oracle):
+@pytest.mark.parametrize('bw', [128, 64])
+def test_readers(oracle, bw):
   n = 14
   rng = np.random.default_rng(4)
-  psi = _rand_state(rng, n)
-  with device.DeviceState(n, 128) as st:
+  dtype = np.complex128 if bw == 128 else np.complex64
+  psi = _rand_state(rng, n, dtype)
+  ref = psi.astype(np.complex128)               # what the handle holds, exactly
+  # complex128: as ever; complex64: the bounds of test_gpu_measure._check_marginal for sums of probabilities (1e-6 relative
+  # + 1e-9) and exact single amplitudes (a product with 2 - 1j rounds once per component: 2^-23 relative, below 5e-6)
+  sum_tol = (lambda want: 1e-12) if bw == 128 else (lambda want: 1e-6 * want + 1e-9)
+  with device.DeviceState(n, bw) as st:
     st.upload(psi)
-    assert abs(st.norm2() - 1.0) < 1e-12
+    assert abs(st.norm2() - float(np.sum(np.abs(ref) ** 2))) < sum_tol(1.0)
+    assert abs(st.norm2() - 1.0) < (1e-12 if bw == 128 else 1e-6)
     idx, p = st.argmax()
-    assert idx == int(np.argmax(np.abs(psi))) and abs(p - np.abs(psi[idx]) ** 2) < 1e-15
+    assert idx == int(np.argmax(np.abs(ref))) and abs(p - np.abs(ref[idx]) ** 2) < 1e-15
     for bit in (0, 5, 13):
-      want = float(np.sum(np.abs(psi[((np.arange(1 << n) >> bit) & 1) == 1]) ** 2))
-      assert abs(st.prob_bit(bit) - want) < 1e-12
+      want = float(np.sum(np.abs(ref[((np.arange(1 << n) >> bit) & 1) == 1]) ** 2))
+      assert abs(st.prob_bit(bit) - want) < sum_tol(want)
+      assert abs(st.prob_bit(bit, 0) - (float(np.sum(np.abs(ref) ** 2)) - want)) < sum_tol(1.0 - want)
     st.project_bit(5, 1)
     proj = psi.copy()
     proj[((np.arange(1 << n) >> 5) & 1) == 0] = 0
     assert np.max(np.abs(st.download() - proj)) == 0
     st.scale(2.0 - 1.0j)
-    assert np.max(np.abs(st.download() - proj * (2.0 - 1.0j))) < 1e-15
+    assert np.max(np.abs(st.download() - proj.astype(np.complex128) * (2.0 - 1.0j))) < (1e-15 if bw == 128 else 5e-6)
     st.init_basis(77)
     got = st.download()
     assert got[77] == 1 and np.count_nonzero(got) == 1

@@ -130,3 +130,36 @@ def test_ranks_with_different_gate_lists_exchange_consistently(oracle, tmp_path,
   assert np.max(np.abs(res['psi'] - want)) < 1e-11
   assert abs(float(res['norm2']) - 1) < 1e-11
   assert int(res['exchanges']) >= 3 and int(res['rounds']) >= 3
+
+
+def _readout_worker(rank, world, port, n, out_dir):
+  os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
+                    LOCAL_RANK='0', QCC_PRELOAD_TORCH='1')
+  import torch  # noqa: F401  (first: one HIP runtime per process)
+  import torch.distributed as dist
+  dist.init_process_group('gloo', rank=rank, world_size=world)
+  from qcc_amd import sharded
+  from tests import fake_device
+  made = []
+
+  def factory(nbits, bw):
+    made.append(sharded.ShardedDevice(nbits, bw, local_rank=0, chunk_amps=1 << 12))
+    return made[-1]
+  fake_device.sharded_readout_worker(rank, n, out_dir, factory, layer=True)
+  assert made and all(type(d.st.eng).__module__ == 'qcc_amd.device' for d in made)      # the HIP engine, not a stand-in
+  assert all(d.st.exchange_path == 'host-staged' and d.st.exchanges >= 1 for d in made)
+  dist.barrier()
+  dist.destroy_process_group()
+
+
+@pytest.mark.parametrize('world', [2, 4])
+def test_sharded_readers_over_hip_engines(tmp_path, world):
+  """The sharded layer's readers over REAL engines (tests/test_measure_cpu.py runs the same worker over a NumPy engine):
+  qc.probabilities over registers of held, mixed and local qubits, seeded and unseeded shots, measure and the collapsed
+  state, then ShardedDevice.prob_bit / project_bit on a held and on a local bit, amplitude, argmax and init_product +
+  download -- all against the single-process NumPy answer."""
+  import torch.multiprocessing as mp
+  from tests import fake_device
+  n = 18
+  mp.spawn(_readout_worker, args=(world, _free_port(), n, str(tmp_path)), nprocs=world, join=True)
+  fake_device.check_sharded_readout(str(tmp_path), world, n, atol=1e-12, layer=True)

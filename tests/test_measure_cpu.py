@@ -12,58 +12,11 @@ import torch.multiprocessing as mp
 from qcc_amd import native
 from qcc_amd.lib import backend, circuit, tensor
 from tests import fake_device
+from tests.fake_device import MeasureOracle, MeasureShardEngine, np_keep, np_marginal, np_sample  # noqa: F401
+from tests.fake_device import readout_circuit as _circuit
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _up = ctypes.POINTER(ctypes.c_uint64)
-
-
-def np_marginal(psi, bits, base=0):
-  """marginal of the logical bits; psi holds indices base .. base + size - 1"""
-  p = np.abs(np.asarray(psi, dtype=np.complex128)) ** 2
-  idx = np.uint64(base) + np.arange(p.size, dtype=np.uint64)
-  j = np.zeros_like(idx)
-  for t, b in enumerate(bits):
-    j |= ((idx >> np.uint64(b)) & np.uint64(1)) << np.uint64(t)
-  return np.bincount(j.astype(np.int64), weights=p, minlength=1 << len(bits))
-
-
-def np_sample(psi, u, base=0):
-  p = np.abs(np.asarray(psi, dtype=np.complex128)) ** 2
-  cdf = np.cumsum(p)
-  assert cdf[-1] > 0
-  i = np.minimum(np.searchsorted(cdf, np.asarray(u) * cdf[-1], side='right'), np.flatnonzero(p)[-1])
-  return (np.uint64(base) + i.astype(np.uint64)).astype(np.uint64)
-
-
-def np_keep(size, mask, value, base=0):
-  idx = np.uint64(base) + np.arange(size, dtype=np.uint64)
-  return (idx & np.uint64(mask)) == np.uint64(value)
-
-
-class MeasureOracle(fake_device.OracleDevice):
-  """OracleDevice with the three readout methods, in NumPy (logical order = the array's order)."""
-
-  def marginal(self, bits):
-    return np_marginal(self.psi, bits)
-
-  def sample(self, u):
-    return np_sample(self.psi, u)
-
-  def project_bits(self, mask, value):
-    self.psi[~np_keep(self.psi.size, mask, value)] = 0
-
-
-class MeasureShardEngine(fake_device.NumpyShardEngine):
-  """NumpyShardEngine with the readout methods, shard bits resolved as qh_marginal / qh_sample / qh_project_bits do."""
-
-  def marginal(self, bits):
-    return np_marginal(self.psi, bits, self.shard << self.nbits)
-
-  def sample(self, u):
-    return np_sample(self.psi, u, self.shard << self.nbits)
-
-  def project_bits(self, mask, value):
-    self.psi[~np_keep(self.psi.size, mask, value, self.shard << self.nbits)] = 0
 
 
 # ---- the C-ABI ---------------------------------------------------------------------------------------------------------
@@ -144,20 +97,6 @@ def cpu_backend():
   yield
   backend.set_device_factory(None)
   tensor.set_tensor_width(None)
-
-
-def _circuit(nq, seed):
-  rng = np.random.default_rng(seed)
-  q = circuit.qc('m')
-  q.reg(nq, 0)
-  for _ in range(3 * nq):
-    a = int(rng.integers(nq))
-    q.ry(a, float(rng.random() * 3))
-    b = int(rng.integers(nq))
-    if b != a:
-      q.cx(a, b)
-    q.rz(int(rng.integers(nq)), float(rng.random() * 3))
-  return q
 
 
 def _ref_probs(psi, qubits):
@@ -277,87 +216,19 @@ def _free_port():
   return p
 
 
-def _shard_qubits(q):
-  """qubits whose logical bit the shard index holds now (the router's map), after the queued gates have been routed"""
-  st = q._ensure_device().st                             # pylint: disable=protected-access
-  return [qb for qb in range(q.nbits) if st.perm[q.nbits - 1 - qb] >= st.nloc]
-
-
 def _sharded_worker(rank, world, port, n, out_dir):
   os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                     LOCAL_RANK=str(rank))
   import torch.distributed as dist
   dist.init_process_group('gloo', rank=rank, world_size=world)
   from qcc_amd import sharded
-  tensor.set_tensor_width(128)
-  backend.set_device_factory(lambda nbits, bw: sharded.ShardedDevice(nbits, bw, engine_factory=MeasureShardEngine,
-                                                                      chunk_amps=16))
-  q = _circuit(n, 5)
-  q.h(0)                                                  # dense gates on the top qubits: shard bits get exchanged
-  q.cx(0, n - 1)
-  res = {'psi': np.asarray(q.psi).copy()}
-  sq = _shard_qubits(q)                                   # registers that include qubits held by the shard index
-  local = [qb for qb in range(n) if qb not in sq]
-  regs = {'shard': sq, 'mixed': [local[0], sq[0], local[-1]], 'local': local[:2]}
-  for name, qubits in regs.items():
-    res['q_' + name] = np.array(qubits)
-    res['p_' + name] = q.probabilities(qubits)
-  res['shots'] = q.sample(3000, [0, 2, n - 1], seed=9)
-  res['full'] = q.sample(3000, seed=9)
-  # seed=None: every rank's global stream differs; the ranks still agree (rank 0's draws)
-  np.random.seed(100 + rank)
-  res['shots_none'] = q.sample(2000, [1, n - 1])
-  res['mq'] = np.array(regs['mixed'])
-  res['shard_before_measure'] = np.array(_shard_qubits(q))
-  res['m1'] = np.array(q.measure(regs['mixed']))
-  res['after'] = np.asarray(q.psi).copy()
-  np.savez(os.path.join(out_dir, f'r{rank}.npz'), **res)
+  fake_device.sharded_readout_worker(
+      rank, n, out_dir, lambda nbits, bw: sharded.ShardedDevice(nbits, bw, engine_factory=MeasureShardEngine, chunk_amps=16))
   dist.barrier()
   dist.destroy_process_group()
-
-
-def _project(psi, n, qubits, value):
-  idx = np.arange(1 << n)
-  keep = np.ones(1 << n, dtype=bool)
-  for t, qb in enumerate(qubits):
-    keep &= ((idx >> (n - 1 - qb)) & 1) == ((value >> (len(qubits) - 1 - t)) & 1)
-  return np.where(keep, psi, 0)
 
 
 @pytest.mark.parametrize('world,n', [(2, 6), (4, 7)])
 def test_sharded_readout_equals_single_process(tmp_path, world, n):
   mp.spawn(_sharded_worker, args=(world, _free_port(), n, str(tmp_path)), nprocs=world, join=True)
-  res = [dict(np.load(tmp_path / f'r{r}.npz')) for r in range(world)]
-  for r in res[1:]:
-    for k, v in res[0].items():
-      assert np.array_equal(v, r[k]), k                  # every rank returns the same, seed=None included
-  r0 = res[0]
-  psi = r0['psi']
-  g = world.bit_length() - 1
-  assert len(r0['q_shard']) == g                          # the shard-bit paths of engine and router ran
-  assert set(r0['mq'].tolist()) & set(r0['shard_before_measure'].tolist())
-  tensor.set_tensor_width(128)
-  backend.set_device_factory(MeasureOracle)
-  try:
-    q = circuit.qc('single')
-    q.psi = psi
-    for name in ('shard', 'mixed', 'local'):
-      np.testing.assert_allclose(r0['p_' + name], q.probabilities(r0['q_' + name].tolist()), atol=1e-13)
-    # the CDF runs in the sharded layout's physical order (rank order, then the router's bit map): the shots follow the
-    # single-process distribution, not its exact sequence
-    p_full = np.abs(psi) ** 2
-    assert np.all(p_full[r0['full'].astype(np.int64)] > 0)
-    freq = np.bincount(r0['full'].astype(np.int64), minlength=1 << n) / 3000
-    assert np.max(np.abs(freq - p_full)) < 0.05
-    reg = (((r0['full'] >> np.uint64(n - 1)) & np.uint64(1)) << np.uint64(2)) | \
-        (((r0['full'] >> np.uint64(n - 3)) & np.uint64(1)) << np.uint64(1)) | (r0['full'] & np.uint64(1))
-    assert reg.tolist() == r0['shots'].tolist()            # the same uniforms: the register is the bits of the full shot
-    pn = q.probabilities([1, n - 1])
-    assert np.all(pn[r0['shots_none'].astype(np.int64)] > 0)
-    mq = r0['mq'].tolist()
-    value, prob = int(r0['m1'][0]), float(r0['m1'][1])
-    assert abs(prob - q.probabilities(mq)[value]) < 1e-13 and prob > 0
-    np.testing.assert_allclose(r0['after'], _project(psi, n, mq, value) / np.sqrt(prob), atol=1e-13)
-  finally:
-    backend.set_device_factory(None)
-    tensor.set_tensor_width(None)
+  fake_device.check_sharded_readout(tmp_path, world, n, atol=1e-13)
