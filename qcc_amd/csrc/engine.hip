@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/qcc_hip.h"
+#include "buffers.hip.h"
 #include "kernels_gate.hip.h"
 #include "kernels_dense.hip.h"
 #include "kernels_mux.hip.h"
@@ -74,26 +75,21 @@ struct qh_state_s {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::vector<hipEvent_t> laps;   // qh_timer_lap: events on the stream, read back by qh_timer_laps
   size_t laps_used = 0;
-  double *d_red = nullptr;     // kRedBlocks doubles
-  uint64_t *d_redi = nullptr;  // kRedBlocks u64
+  // Scratch (buffers.hip.h): released by the members' destructors at `delete h`, after qh_destroy has made the device
+  // current and drained the stream.  A new feature adds its buffer here and nowhere else.
+  qh::DeviceBuffer red, redi;  // kRedBlocks doubles / kRedBlocks u64
   qh::SweepBuffers sweep;      // device/pinned op buffers for fused sweeps
-  uint64_t *d_tmax = nullptr;  // per-unit maxima the last sweep of a flush leaves for qh_argmax (SweepParams::tilemax)
-  uint64_t tmax_cap = 0;       // entries
+  qh::DeviceBuffer tmax;       // per-unit maxima the last sweep of a flush leaves for qh_argmax (SweepParams::tilemax)
   qh::Comm *comm = nullptr;    // multi-GPU exchange (exchange.hip.h)
   // qh_apply_matrix: the caller's matrix is copied into pinned slot i, uploaded on the stream into device slot i, and slot i
   // is reused only after the event recorded behind the kernel that read it has completed
-  void *mat_host = nullptr, *mat_dev = nullptr;
-  hipEvent_t mat_ev[kMatSlots] = {};
-  bool mat_used[kMatSlots] = {};
-  unsigned mat_next = 0;
+  qh::StagedUpload<kMatSlots> mat;
   // qh_apply_mux / qh_apply_diag: one pinned staging buffer and one device table, grown on demand (a k = 16 mux table is
   // 4 MiB: the ring's slots are too small); reused only after the event recorded behind the kernel that read the table
-  void *tab_host = nullptr, *tab_dev = nullptr;
-  size_t tab_cap = 0;
-  hipEvent_t tab_ev = nullptr;
-  bool tab_used = false;
-  void *d_meas = nullptr;      // qh_marginal / qh_sample scratch (slab, chunk sums, shot lists), grown on demand
-  size_t meas_bytes = 0;
+  qh::StagedUpload<1> tab;
+  qh::DeviceBuffer meas;       // the readers' scratch (slabs, chunk sums, shot lists, results), grown on demand
+  double *d_red() const { return red.as<double>(); }
+  uint64_t *d_redi() const { return redi.as<uint64_t>(); }
   uint64_t amp_bytes() const { return bw == 128 ? 16 : 8; }
   uint64_t local_mask() const { return nloc >= 64 ? ~0ull : ((1ull << nloc) - 1ull); }
 };
@@ -125,6 +121,43 @@ uint64_t to_logical(const qh_state_s *h, uint64_t phys) {
 struct Placed { uint64_t local, held; };
 Placed place(const qh_state_s *h, uint64_t phys) { return {phys & h->local_mask(), phys >> h->nloc}; }
 Placed place_bit(const qh_state_s *h, int logical_bit) { return place(h, 1ull << h->perm[logical_bit]); }
+
+// Physical local control bits as the kernels take them: bits 0-1 are never skipped in an index enumeration (the same
+// 64-byte half line), so controls there are a predicate (`lowpred`) and only the others (`cm`) are inserted as ones.
+struct LowSplit { uint32_t lowpred; uint64_t cm; };
+LowSplit split_low(const qh_state_s *h, uint64_t cm_all) {
+  const uint64_t low = (h->nloc > 2) ? 3ull : 0ull;
+  return {(uint32_t)(cm_all & low), cm_all & ~low};
+}
+
+// k logical bits: every one in [0, nglob), then none twice.  *mask = the logical bits listed.
+int check_bit_list(const qh_state_s *h, const char *who, int k, const int32_t *bits, uint64_t *mask) {
+  *mask = 0;
+  for (int j = 0; j < k; ++j)
+    if (bits[j] < 0 || bits[j] >= h->nglob) return fail(QH_ERR_BAD_QUBIT, "%s: bit %d out of range [0,%d)", who, bits[j], h->nglob);
+  for (int j = 0; j < k; ++j) {
+    if ((*mask >> bits[j]) & 1ull) return fail(QH_ERR_SAME_QUBIT, "%s: bit %d appears twice", who, bits[j]);
+    *mask |= 1ull << bits[j];
+  }
+  return QH_OK;
+}
+
+// The listed bits on this shard: the local ones as (physical position, index j in the list), ascending by position, and
+// the j whose bit the shard index holds at 1 (`held_ones`; held at 0: in neither).
+struct SplitBits {
+  std::vector<std::pair<int, int>> local;
+  uint64_t held_ones = 0;
+};
+SplitBits split_bits(const qh_state_s *h, int k, const int32_t *bits) {
+  SplitBits s;
+  for (int j = 0; j < k; ++j) {
+    const Placed b = place_bit(h, bits[j]);
+    if (!b.held) s.local.push_back({h->perm[bits[j]], j});
+    else if (h->shard & b.held) s.held_ones |= 1ull << j;
+  }
+  std::sort(s.local.begin(), s.local.end());
+  return s;
+}
 
 unsigned grid_for(uint64_t n, uint64_t cap) { return (unsigned)std::min<uint64_t>((n + 255) / 256, cap); }   // 256-thread blocks
 
@@ -247,10 +280,9 @@ int launch_single(qh_state_s *h, const qh::GateRec &r) {
     return QH_OK;
   }
   const uint64_t cm_all = ctl.local;
-  // bits 0,1 are never skipped in the enumeration (same 64-byte half line): predicate
-  const uint64_t kLow = (h->nloc > 2) ? 3ull : 0ull;
-  uint32_t lowpred = (uint32_t)(cm_all & kLow);
-  const uint64_t cm = cm_all & ~kLow;
+  const LowSplit low = split_low(h, cm_all);
+  uint32_t lowpred = low.lowpred;
+  const uint64_t cm = low.cm;
   const int nc_all = __builtin_popcountll(cm_all);
   const int nc = __builtin_popcountll(cm);
   if (nc + 1 > qh::kMaxIns) return fail(QH_ERR_ARG, "too many local control bits (%d)", nc);
@@ -286,7 +318,7 @@ int launch_single(qh_state_s *h, const qh::GateRec &r) {
       return QH_OK;  // identity
     }
     if (one_sided) {
-      const bool tgt_low = ((kLow >> r.tgt) & 1ull) != 0;   // target itself inside the half line
+      const bool tgt_low = h->nloc > 2 && r.tgt < 2;        // target itself inside the half line
       if (tgt_low) lowpred |= 1u << r.tgt;
       const uint64_t nwork = 1ull << (h->nloc - nc - (tgt_low ? 0 : 1));
       diag_kernel(nwork, -1, tgt_low ? cm : (cm | (1ull << r.tgt)), 1, 0, g[6], g[7]);
@@ -663,8 +695,8 @@ int make_events(qh_state_s *h) {
 int common_init(qh_state_s *h) {
   for (int b = 0; b < 64; ++b) h->perm[b] = b;
   if (h->dry) return QH_OK;
-  HIP_TRY(hipMalloc(&h->d_red, kRedBlocks * sizeof(double)));
-  HIP_TRY(hipMalloc(&h->d_redi, kRedBlocks * sizeof(uint64_t)));
+  HIP_TRY(h->red.reserve(kRedBlocks * sizeof(double)));
+  HIP_TRY(h->redi.reserve(kRedBlocks * sizeof(uint64_t)));
   return QH_OK;
 }
 
@@ -817,26 +849,15 @@ int qh_destroy(qh_handle h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     (void)qh_comm_destroy(h);
-    qh::free_sweep_buffers(&h->sweep);
-    if (h->d_tmax) (void)hipFree(h->d_tmax);
-    if (h->d_red) (void)hipFree(h->d_red);
-    if (h->d_redi) (void)hipFree(h->d_redi);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
-    for (hipEvent_t e : h->mat_ev) if (e) (void)hipEventDestroy(e);
-    if (h->mat_dev) (void)hipFree(h->mat_dev);
-    if (h->mat_host) (void)hipHostFree(h->mat_host);
-    if (h->tab_ev) (void)hipEventDestroy(h->tab_ev);
-    if (h->tab_dev) (void)hipFree(h->tab_dev);
-    if (h->tab_host) (void)hipHostFree(h->tab_host);
-    if (h->d_meas) (void)hipFree(h->d_meas);
     for (hipEvent_t e : h->laps) (void)hipEventDestroy(e);
     if (h->owns_mem && h->d_psi) (void)hipFree(h->d_psi);
     if (h->d_alt) (void)hipFree(h->d_alt);
     if (h->host_psi) (void)hipHostFree(h->host_psi);
     if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
   }
-  delete h;
+  delete h;      // (the scratch members release themselves here: the device is current, the stream drained)
   return QH_OK;
 }
 
@@ -991,21 +1012,20 @@ int qh_init_product(qh_handle h, int nfactors, const int *nq, const double *cons
     off += 1ull << nq[f];
   }
   HIP_TRY(hipSetDevice(h->device));
-  double2 *d_tab = nullptr;
-  HIP_TRY(hipMalloc((void **)&d_tab, tab.size() * sizeof(double)));
-  hipError_t e = hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+  qh::DeviceBuffer d_tab;
+  HIP_TRY(d_tab.reserve(tab.size() * sizeof(double)));
+  hipError_t e = hipMemcpyAsync(d_tab.ptr, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) {
     const uint64_t n = 1ull << h->nloc;
     const uint64_t idx_high = h->shard << h->nloc;
     with_real(h, [&](auto x) {
       using R = decltype(x);
       hipLaunchKernelGGL(qh::k_init_product<R>, dim3(grid_for(n, 1ull << 22)), dim3(256), 0, h->stream,
-                         (typename qh::AmpT<R>::type *)h->d_psi, n, idx_high, sp, d_tab);
+                         (typename qh::AmpT<R>::type *)h->d_psi, n, idx_high, sp, d_tab.as<double2>());
     });
     e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // `tab` and d_tab are released below
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // `tab` and d_tab are released on return
   }
-  (void)hipFree(d_tab);
   if (e != hipSuccess) return fail(QH_ERR_HIP, hipGetErrorString(e));
   return QH_OK;
 }
@@ -1139,14 +1159,14 @@ int qh_apply_stream(qh_handle h, uint64_t count, const int32_t *ops, const doubl
 
 // sum of |amplitude|^2 over the local indices i with (i & mask) == want
 static int masked_norm2(qh_handle h, uint64_t mask, uint64_t want, double *out) {
-  HIP_TRY(hipMemsetAsync(h->d_red, 0, sizeof(double), h->stream));
+  HIP_TRY(hipMemsetAsync(h->d_red(), 0, sizeof(double), h->stream));
   const uint64_t n = 1ull << h->nloc;
   with_real(h, [&](auto x) {
     using R = decltype(x);
     hipLaunchKernelGGL(qh::k_norm2<R>, dim3(grid_for(n, 4096)), dim3(256), 0, h->stream,
-                       (const typename qh::AmpT<R>::type *)h->d_psi, n, mask, want, h->d_red);
+                       (const typename qh::AmpT<R>::type *)h->d_psi, n, mask, want, h->d_red());
   });
-  return read_back(h, out, h->d_red, sizeof(double));
+  return read_back(h, out, h->d_red(), sizeof(double));
 }
 
 int qh_norm2(qh_handle h, double *out) {
@@ -1312,15 +1332,15 @@ __global__ __launch_bounds__(256) void k_prefix_scan(const A *__restrict__ psi, 
 int argmax_from_tilemax(qh_state_s *h, const qh::TileMaxOut &tm, const LocalBits &lb, uint64_t *logical, double *prob, bool *found) {
   *found = false;
   const unsigned grid = grid_for(tm.nunits, kRedBlocks);
-  hipLaunchKernelGGL(k_tmax_reduce, dim3(grid), dim3(256), 0, h->stream, (const uint64_t *)tm.buf, tm.nunits, h->d_redi);
+  hipLaunchKernelGGL(k_tmax_reduce, dim3(grid), dim3(256), 0, h->stream, (const uint64_t *)tm.buf, tm.nunits, h->d_redi());
   std::vector<uint64_t> part(grid);
-  int rc = read_back(h, part.data(), h->d_redi, grid * sizeof(uint64_t));
+  int rc = read_back(h, part.data(), h->d_redi(), grid * sizeof(uint64_t));
   if (rc) return rc;
   uint64_t top = 0;
   for (uint64_t v : part) top = std::max(top, v);
   double want;
   memcpy(&want, &top, 8);
-  unsigned long long *ids = (unsigned long long *)h->d_redi;      // (kRedBlocks u64: room for 1 + kTmaxIds + the result)
+  unsigned long long *ids = (unsigned long long *)h->d_redi();      // (kRedBlocks u64: room for 1 + kTmaxIds + the result)
   static_assert(kRedBlocks >= 2 + kTmaxIds, "reduction scratch");
   HIP_TRY(hipMemsetAsync(ids, 0, 8, h->stream));
   HIP_TRY(hipMemsetAsync(ids + 1 + kTmaxIds, 0xff, 8, h->stream));
@@ -1373,15 +1393,9 @@ extern "C" int qh_argmax(qh_handle h, uint64_t *phys_index, double *prob) {
       env_int("QH_FUSED_ARGMAX", 1) != 0) {
     const uint64_t need = 1ull << (h->nloc - qh::kLaneBits - 3);       // units of a three-register-bit tile (a sweep without dense gates); plans
                                                                        // with dense gates use five: a flush that wants more entries takes the full pass
-    if (h->tmax_cap < need) {
-      if (h->d_tmax) (void)hipFree(h->d_tmax);
-      h->d_tmax = nullptr;
-      h->tmax_cap = 0;
-      if (hipMalloc((void **)&h->d_tmax, need * 8) == hipSuccess && h->d_tmax) h->tmax_cap = need;
-      else { h->d_tmax = nullptr; (void)hipGetLastError(); }
-    }
-    tm.buf = h->d_tmax;
-    tm.cap = h->tmax_cap;
+    (void)h->tmax.reserve(need * 8);      // (no room: the full pass decides)
+    tm.buf = h->tmax.ptr;
+    tm.cap = h->tmax.cap / 8;
   }
   int rc = flush_impl(h, nullptr, tm.buf ? &tm : nullptr);
   if (rc) return rc;
@@ -1398,13 +1412,13 @@ extern "C" int qh_argmax(qh_handle h, uint64_t *phys_index, double *prob) {
     const unsigned grid = grid_for(n, kRedBlocks);
     with_real(h, [&](auto x) {
       using A = typename qh::AmpT<decltype(x)>::type;
-      if (lb.mapped) hipLaunchKernelGGL((k_argmax_logical<A, true>), dim3(grid), dim3(256), 0, h->stream, (const A *)h->d_psi, n, lb.p2l, h->d_red, h->d_redi);
-      else hipLaunchKernelGGL((k_argmax_logical<A, false>), dim3(grid), dim3(256), 0, h->stream, (const A *)h->d_psi, n, lb.p2l, h->d_red, h->d_redi);
+      if (lb.mapped) hipLaunchKernelGGL((k_argmax_logical<A, true>), dim3(grid), dim3(256), 0, h->stream, (const A *)h->d_psi, n, lb.p2l, h->d_red(), h->d_redi());
+      else hipLaunchKernelGGL((k_argmax_logical<A, false>), dim3(grid), dim3(256), 0, h->stream, (const A *)h->d_psi, n, lb.p2l, h->d_red(), h->d_redi());
     });
     std::vector<double> bp(grid);
     std::vector<uint64_t> bi(grid);
-    HIP_TRY(hipMemcpyAsync(bp.data(), h->d_red, grid * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if ((rc = read_back(h, bi.data(), h->d_redi, grid * sizeof(uint64_t)))) return rc;
+    HIP_TRY(hipMemcpyAsync(bp.data(), h->d_red(), grid * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if ((rc = read_back(h, bi.data(), h->d_redi(), grid * sizeof(uint64_t)))) return rc;
     double best = -1.0;
     uint64_t idx = 0;
     for (unsigned k = 0; k < grid; ++k)
@@ -1450,22 +1464,24 @@ int qh_project_bit(qh_handle h, int logical_bit, int value) {
 
 namespace {
 
+// The next slot of a staged upload, once the kernel that last read it has finished (watched handles poll: wait_event).
+template <int N>
+int acquire(qh_state_s *h, qh::StagedUpload<N> &up, size_t bytes_per_slot, const char *who, char **host, char **dev, unsigned *slot) {
+  if (hipEvent_t e = up.busy()) {
+    const int rc = wait_event(h, e, who);
+    if (rc) return rc;
+  }
+  HIP_TRY(up.acquire(bytes_per_slot, host, dev, slot));
+  return QH_OK;
+}
+
 // Copies the caller's matrix (4^k complex128) into the next staging slot, converted to the state's width, and uploads
 // it on the handle's stream.  *dev = the device copy; *slot = the slot whose event goes behind the kernel.
 int stage_matrix(qh_state_s *h, int k, const double *m, const void **dev, unsigned *slot) {
-  if (!h->mat_host) {
-    HIP_TRY(hipHostMalloc(&h->mat_host, kMatSlots * kMatSlotBytes, hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&h->mat_dev, kMatSlots * kMatSlotBytes));
-    for (hipEvent_t &e : h->mat_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  const unsigned s = h->mat_next++ % kMatSlots;
-  if (h->mat_used[s]) {
-    const int rc = wait_event(h, h->mat_ev[s], "qh_apply_matrix");   // the kernel that last read slot s has finished
-    if (rc) return rc;
-  }
+  char *host = nullptr, *d = nullptr;
+  const int rc = acquire(h, h->mat, kMatSlotBytes, "qh_apply_matrix", &host, &d, slot);
+  if (rc) return rc;
   const size_t n = (size_t)1 << (2 * k);
-  char *host = (char *)h->mat_host + s * kMatSlotBytes;
-  char *d = (char *)h->mat_dev + s * kMatSlotBytes;
   size_t bytes = n * 16;
   if (h->bw == 128) {
     memcpy(host, m, bytes);
@@ -1476,7 +1492,6 @@ int stage_matrix(qh_state_s *h, int k, const double *m, const void **dev, unsign
   }
   HIP_TRY(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, h->stream));
   *dev = d;
-  *slot = s;
   return QH_OK;
 }
 
@@ -1513,16 +1528,11 @@ extern "C" {
 int qh_apply_matrix(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, const double *matrix) {
   if (!h || !bits || !matrix) return fail(QH_ERR_ARG, "apply_matrix: null handle, bits or matrix");
   if (k < 1 || k > qh::kMaxDenseBits) return fail(QH_ERR_ARG, "apply_matrix: k = %d outside [1,%d]", k, qh::kMaxDenseBits);
-  uint64_t tmask = 0;
-  for (int j = 0; j < k; ++j)
-    if (bits[j] < 0 || bits[j] >= h->nglob)
-      return fail(QH_ERR_BAD_QUBIT, "apply_matrix: bit %d out of range [0,%d)", bits[j], h->nglob);
   if (h->nglob < 64 && (ctl_mask >> h->nglob))
     return fail(QH_ERR_BAD_QUBIT, "apply_matrix: control mask 0x%llx has bits >= %d", (unsigned long long)ctl_mask, h->nglob);
-  for (int j = 0; j < k; ++j) {
-    if ((tmask >> bits[j]) & 1ull) return fail(QH_ERR_SAME_QUBIT, "apply_matrix: bit %d appears twice", bits[j]);
-    tmask |= 1ull << bits[j];
-  }
+  uint64_t tmask = 0;
+  int rc = check_bit_list(h, "apply_matrix", k, bits, &tmask);
+  if (rc) return rc;
   if (ctl_mask & tmask)
     return fail(QH_ERR_SAME_QUBIT, "apply_matrix: control and target share bits 0x%llx", (unsigned long long)(ctl_mask & tmask));
   // (a logical bit stays local or in the shard index whatever the relayout sweeps do)
@@ -1534,8 +1544,7 @@ int qh_apply_matrix(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, 
     if (h->perm[bits[j]] >= h->nloc)
       return fail(QH_ERR_NONLOCAL, "apply_matrix: logical bit %d is held by the shard index (physical bit %d, local bits: %d); "
                   "exchange first", bits[j], h->perm[bits[j]], h->nloc);
-  int rc = enter(h);           // a barrier: what is queued runs first, on whatever layout it leaves
-  if (rc) return rc;
+  if ((rc = enter(h))) return rc;          // a barrier: what is queued runs first, on whatever layout it leaves
   const Placed ctl = place(h, to_phys(h, ctl_mask));
   if ((h->shard & ctl.held) != ctl.held) {   // a shard-bit control that is 0 on this shard (met: dropped)
     h->stats.gates_submitted++;
@@ -1543,10 +1552,10 @@ int qh_apply_matrix(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, 
     return QH_OK;
   }
   const uint64_t cm_all = ctl.local;         // physical local control bits
-  const uint64_t kLow = (h->nloc > 2) ? 3ull : 0ull;         // as launch_single: bits 0-1 are a predicate
+  const LowSplit low = split_low(h, cm_all);
+  const uint64_t cm = low.cm;
   qh::DenseArgs a{};
-  a.lowpred = (uint32_t)(cm_all & kLow);
-  const uint64_t cm = cm_all & ~kLow;
+  a.lowpred = low.lowpred;
   uint64_t ptmask = 0;
   for (int j = 0; j < k; ++j) {
     a.t[j] = h->perm[bits[j]];
@@ -1561,8 +1570,7 @@ int qh_apply_matrix(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, 
   if ((rc = stage_matrix(h, k, matrix, &dmat, &slot))) return rc;
   with_real(h, [&](auto x) { launch_dense<decltype(x)>(h, k, a, dmat); });
   if ((rc = check_launch(h))) return rc;
-  HIP_TRY(hipEventRecord(h->mat_ev[slot], h->stream));
-  h->mat_used[slot] = true;
+  HIP_TRY(h->mat.commit(h->stream, slot));
   h->stats.gates_submitted++;
   count_kernel(h, 1ull << (h->nloc - __builtin_popcountll(cm_all)), a.nwork << k);
   return QH_OK;
@@ -1585,18 +1593,15 @@ struct TabPlan {
 
 TabPlan plan_table(const qh_state_s *h, int k, const int32_t *bits) {
   TabPlan t;
-  std::vector<std::pair<int, int>> loc;       // (physical position, bit of the restricted index)
-  for (int j = 0; j < k; ++j) {
-    const Placed b = place_bit(h, bits[j]);
-    if (b.held) {
-      if (h->shard & b.held) t.fixed |= 1u << j;
-    } else {
-      loc.push_back({h->perm[bits[j]], t.kl++});
-      t.tbits |= 1u << j;
-      t.local_pos |= b.local;
-    }
+  const SplitBits sb = split_bits(h, k, bits);
+  t.fixed = (uint32_t)sb.held_ones;
+  t.kl = (int)sb.local.size();
+  for (const auto &pj : sb.local) {
+    t.tbits |= 1u << pj.second;
+    t.local_pos |= 1ull << pj.first;
   }
-  std::sort(loc.begin(), loc.end());
+  std::vector<std::pair<int, int>> loc = sb.local;       // (physical position, bit of the restricted index)
+  for (auto &pj : loc) pj.second = __builtin_popcount(t.tbits & ((1u << pj.second) - 1u));
   for (size_t i = 0; i < loc.size();) {       // a run: adjacent positions that feed adjacent table bits
     size_t e = i + 1;
     while (e < loc.size() && loc[e].first == loc[i].first + (int)(e - i) && loc[e].second == loc[i].second + (int)(e - i)) ++e;
@@ -1610,34 +1615,24 @@ TabPlan plan_table(const qh_state_s *h, int k, const int32_t *bits) {
 // pinned staging buffer and from there, on the handle's stream, into the device table.  One buffer of each: the
 // previous call's kernel must have read its table before the staging buffer is written again.
 int stage_table(qh_state_s *h, const TabPlan &t, int C, const double *src, const void **dev) {
-  if (!h->tab_ev) HIP_TRY(hipEventCreateWithFlags(&h->tab_ev, hipEventDisableTiming));
-  if (h->tab_used) {
-    const int rc = wait_event(h, h->tab_ev, "qh_apply_mux/diag");
-    if (rc) return rc;
-  }
   const size_t nent = (size_t)1 << t.kl, elem = h->bw == 128 ? 16 : 8, bytes = nent * C * elem;
-  if (h->tab_cap < bytes) {
-    size_t cap = 64u << 10;
-    while (cap < bytes) cap *= 2;
-    if (h->tab_host) (void)hipHostFree(h->tab_host);
-    if (h->tab_dev) (void)hipFree(h->tab_dev);
-    h->tab_host = h->tab_dev = nullptr;
-    h->tab_cap = 0;
-    HIP_TRY(hipHostMalloc(&h->tab_host, cap, hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&h->tab_dev, cap));
-    h->tab_cap = cap;
-  }
+  size_t cap = 64u << 10;
+  while (cap < bytes) cap *= 2;
+  char *host = nullptr, *d = nullptr;
+  unsigned slot = 0;
+  const int rc = acquire(h, h->tab, cap, "qh_apply_mux/diag", &host, &d, &slot);
+  if (rc) return rc;
   for (size_t s = 0; s < nent; ++s) {
     uint32_t full = t.fixed;                    // entry s of the restricted table = entry `full` of the caller's
     for (uint32_t m = t.tbits, r = (uint32_t)s; m; m &= m - 1, r >>= 1)
       if (r & 1u) full |= m & (~m + 1u);
     const double *e = src + (size_t)full * C * 2;
-    if (h->bw == 128) memcpy((char *)h->tab_host + s * C * 16, e, (size_t)C * 16);
+    if (h->bw == 128) memcpy(host + s * C * 16, e, (size_t)C * 16);
     else
-      for (int i = 0; i < 2 * C; ++i) ((float *)h->tab_host)[s * C * 2 + i] = (float)e[i];
+      for (int i = 0; i < 2 * C; ++i) ((float *)host)[s * C * 2 + i] = (float)e[i];
   }
-  HIP_TRY(hipMemcpyAsync(h->tab_dev, h->tab_host, bytes, hipMemcpyHostToDevice, h->stream));
-  *dev = h->tab_dev;
+  HIP_TRY(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, h->stream));
+  *dev = d;
   return QH_OK;
 }
 
@@ -1677,14 +1672,10 @@ void launch_tab(qh_state_s *h, int kind, int tier, const qh::TabArgs &a, const v
 int check_tab_bits(const qh_state_s *h, const char *who, int k, const int32_t *bits, bool has_tgt, int extra) {
   if (k < 0 || k > qh::kMaxMuxBits) return fail(QH_ERR_ARG, "%s: k = %d outside [0,%d]", who, k, qh::kMaxMuxBits);
   if (k > 0 && !bits) return fail(QH_ERR_ARG, "%s: null bit list", who);
-  uint64_t seen = 0;
-  for (int j = 0; j < k; ++j)
-    if (bits[j] < 0 || bits[j] >= h->nglob) return fail(QH_ERR_BAD_QUBIT, "%s: bit %d out of range [0,%d)", who, bits[j], h->nglob);
   if (has_tgt && (extra < 0 || extra >= h->nglob)) return fail(QH_ERR_BAD_QUBIT, "%s: target bit %d out of range [0,%d)", who, extra, h->nglob);
-  for (int j = 0; j < k; ++j) {
-    if ((seen >> bits[j]) & 1ull) return fail(QH_ERR_SAME_QUBIT, "%s: bit %d appears twice", who, bits[j]);
-    seen |= 1ull << bits[j];
-  }
+  uint64_t seen = 0;
+  const int rc = check_bit_list(h, who, k, bits, &seen);
+  if (rc) return rc;
   if (has_tgt && ((seen >> extra) & 1ull)) return fail(QH_ERR_SAME_QUBIT, "%s: target bit %d is among the selection bits", who, extra);
   return QH_OK;
 }
@@ -1700,8 +1691,7 @@ int run_tab(qh_state_s *h, int kind, const TabPlan &t, uint64_t lane_pos, int C,
   if (rc) return rc;
   with_real(h, [&](auto x) { launch_tab<decltype(x)>(h, kind, tier, a, dtab, bytes); });
   if ((rc = check_launch(h))) return rc;
-  HIP_TRY(hipEventRecord(h->tab_ev, h->stream));
-  h->tab_used = true;
+  HIP_TRY(h->tab.commit(h->stream, 0));
   h->stats.gates_submitted++;
   count_kernel(h, 1ull << h->nloc, 1ull << h->nloc);
   return QH_OK;
@@ -1750,20 +1740,6 @@ namespace {
 
 constexpr uint64_t kMeasBlocks = 1024;      // k_marginal_bins: blocks to aim for (four 32 KiB-LDS blocks per CU)
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int meas_scratch(qh_state_s *h, size_t bytes, char **out) {
-  if (h->meas_bytes < bytes) {
-    if (h->d_meas) HIP_TRY(hipFree(h->d_meas));
-    h->d_meas = nullptr;
-    h->meas_bytes = 0;
-    HIP_TRY(hipMalloc(&h->d_meas, bytes));
-    h->meas_bytes = bytes;
-  }
-  *out = (char *)h->d_meas;
-  return QH_OK;
-}
-
 int meas_chunk_bits(const qh_state_s *h) { return std::min(h->nloc, qh::kMeasChunkBits); }
 
 }  // namespace
@@ -1774,25 +1750,16 @@ int qh_marginal(qh_handle h, int k, const int32_t *bits, double *out) {
   if (!h || !out || (k > 0 && !bits)) return fail(QH_ERR_ARG, "marginal: null handle, bits or out");
   if (k < 0 || k > qh::kMaxMarginalBits) return fail(QH_ERR_ARG, "marginal: k = %d outside [0,%d]", k, qh::kMaxMarginalBits);
   uint64_t seen = 0;
-  for (int t = 0; t < k; ++t) {
-    if (bits[t] < 0 || bits[t] >= h->nglob) return fail(QH_ERR_BAD_QUBIT, "marginal: bit %d out of range [0,%d)", bits[t], h->nglob);
-    if ((seen >> bits[t]) & 1ull) return fail(QH_ERR_SAME_QUBIT, "marginal: bit %d appears twice", bits[t]);
-    seen |= 1ull << bits[t];
-  }
-  int rc = enter(h);
+  int rc = check_bit_list(h, "marginal", k, bits, &seen);
   if (rc) return rc;
+  if ((rc = enter(h))) return rc;
   const int c = meas_chunk_bits(h);
   qh::MarginalArgs a{};
   qh::FoldArgs f{};
   a.c = c;
-  std::vector<std::pair<int, int>> loc;     // (physical bit, output bit) of the register bits this shard holds locally
-  for (int t = 0; t < k; ++t) {
-    const Placed b = place_bit(h, bits[t]);
-    if (!b.held) loc.push_back({h->perm[bits[t]], t});
-    else if (h->shard & b.held) f.fixed |= 1ull << t;     // fixed on this shard
-  }
-  std::sort(loc.begin(), loc.end());
-  for (const auto &pt : loc) {
+  const SplitBits sb = split_bits(h, k, bits);     // (physical bit, output bit) of the register bits this shard holds locally
+  f.fixed = sb.held_ones;                          // fixed on this shard
+  for (const auto &pt : sb.local) {
     if (pt.first < c) {
       a.inner |= 1u << pt.first;
       f.tin[a.ki++] = (uint8_t)pt.second;
@@ -1809,11 +1776,12 @@ int qh_marginal(qh_handle h, int k, const int32_t *bits, double *out) {
   a.bpo = f.bpo = bpo;
   a.cpb = rest_chunks / bpo;
   const uint64_t nblk = (uint64_t)bpo << a.ko;
-  const size_t slab_bytes = align256((size_t)(nblk << a.ki) * sizeof(double));
   const size_t out_bytes = ((size_t)1 << k) * sizeof(double);
-  char *scr = nullptr;
-  if ((rc = meas_scratch(h, slab_bytes + out_bytes, &scr))) return rc;
-  double *slab = (double *)scr, *dout = (double *)(scr + slab_bytes);
+  qh::ScratchLayout lay;
+  const size_t slab_off = lay.add((size_t)(nblk << a.ki) * sizeof(double)), out_off = lay.add(out_bytes);
+  HIP_TRY(h->meas.reserve(lay.total));
+  char *scr = h->meas.as<char>();
+  double *slab = (double *)(scr + slab_off), *dout = (double *)(scr + out_off);
   HIP_TRY(hipMemsetAsync(dout, 0, out_bytes, h->stream));
   with_real(h, [&](auto x) {
     using R = decltype(x);
@@ -1837,13 +1805,13 @@ int qh_sample(qh_handle h, uint64_t count, const double *u, uint64_t *logical_ou
   const int c = meas_chunk_bits(h);
   const uint64_t nchunks = 1ull << (h->nloc - c);
   const uint64_t maxlist = std::min<uint64_t>(nchunks, count);
-  const size_t sums_b = align256(nchunks * 8), tgt_b = align256(count * 8), ids_b = align256(maxlist * 8),
-               first_b = align256((maxlist + 1) * 8), out_b = align256(count * 8);
-  char *scr = nullptr;
-  if ((rc = meas_scratch(h, sums_b + tgt_b + ids_b + first_b + out_b, &scr))) return rc;
-  double *d_sums = (double *)scr, *d_tgt = (double *)(scr + sums_b);
-  uint64_t *d_ids = (uint64_t *)(scr + sums_b + tgt_b), *d_first = (uint64_t *)(scr + sums_b + tgt_b + ids_b);
-  uint64_t *d_out = (uint64_t *)(scr + sums_b + tgt_b + ids_b + first_b);
+  qh::ScratchLayout lay;
+  const size_t sums_off = lay.add(nchunks * 8), tgt_off = lay.add(count * 8), ids_off = lay.add(maxlist * 8),
+               first_off = lay.add((maxlist + 1) * 8), out_off = lay.add(count * 8);
+  HIP_TRY(h->meas.reserve(lay.total));
+  char *scr = h->meas.as<char>();
+  double *d_sums = (double *)(scr + sums_off), *d_tgt = (double *)(scr + tgt_off);
+  uint64_t *d_ids = (uint64_t *)(scr + ids_off), *d_first = (uint64_t *)(scr + first_off), *d_out = (uint64_t *)(scr + out_off);
   const unsigned g1 = (unsigned)std::min<uint64_t>(nchunks, 2048);
   with_real(h, [&](auto x) {
     using R = decltype(x);
@@ -1962,10 +1930,10 @@ int qh_expect_pauli(qh_handle h, uint64_t nterms, const uint64_t *xmask, const u
   }
   // terms that share a physical x mask share a read of the state, kExpectT at a time
   std::stable_sort(terms.begin(), terms.end(), [](const Term &l, const Term &r) { return l.px < r.px; });
-  const size_t slab_bytes = align256((size_t)kExpectBlocks * qh::kExpectT * sizeof(double));
-  char *scr = nullptr;
-  if ((rc = meas_scratch(h, slab_bytes + (size_t)nterms * sizeof(double), &scr))) return rc;
-  double *slab = (double *)scr, *dout = (double *)(scr + slab_bytes);
+  qh::ScratchLayout lay;
+  const size_t slab_off = lay.add((size_t)kExpectBlocks * qh::kExpectT * sizeof(double)), out_off = lay.add((size_t)nterms * sizeof(double));
+  HIP_TRY(h->meas.reserve(lay.total));
+  double *slab = (double *)(h->meas.as<char>() + slab_off), *dout = (double *)(h->meas.as<char>() + out_off);
   uint64_t batches = 0;
   for (uint64_t first = 0; first < nterms;) {
     uint64_t cnt = 1;
@@ -2277,15 +2245,13 @@ int verify_geometry(qh_state_s *h, uint64_t sig) {
   static const int mode = env_int("QH_EXCHANGE_VERIFY", -1);
   if (mode == 0) return QH_OK;
   if (mode < 0 && std::find(c->verified.begin(), c->verified.end(), sig) != c->verified.end()) return QH_OK;
-  if (!c->d_sig) {
-    HIP_TRY(hipMalloc((void **)&c->d_sig, 4 * sizeof(double)));
-    HIP_TRY(hipHostMalloc((void **)&c->h_sig, 8 * sizeof(double), hipHostMallocDefault));
-  }
-  double *v = c->h_sig, *w = c->h_sig + 4;
+  HIP_TRY(c->d_sig.reserve(4 * sizeof(double)));
+  HIP_TRY(c->h_sig.reserve(8 * sizeof(double)));
+  double *v = c->h_sig.as<double>(), *w = v + 4, *d_sig = c->d_sig.as<double>();
   v[0] = (double)(sig >> 32); v[1] = (double)(sig & 0xffffffffu); v[2] = -v[0]; v[3] = -v[1];
-  HIP_TRY(hipMemcpyAsync(c->d_sig, v, 4 * sizeof(double), hipMemcpyHostToDevice, c->xstream));
-  NCCL_TRY(qh::rccl().AllReduce(c->d_sig, c->d_sig, 4, ncclDouble, ncclMax, c->nccl, c->xstream));
-  HIP_TRY(hipMemcpyAsync(w, c->d_sig, 4 * sizeof(double), hipMemcpyDeviceToHost, c->xstream));
+  HIP_TRY(hipMemcpyAsync(d_sig, v, 4 * sizeof(double), hipMemcpyHostToDevice, c->xstream));
+  NCCL_TRY(qh::rccl().AllReduce(d_sig, d_sig, 4, ncclDouble, ncclMax, c->nccl, c->xstream));
+  HIP_TRY(hipMemcpyAsync(w, d_sig, 4 * sizeof(double), hipMemcpyDeviceToHost, c->xstream));
   const int rc = wait_stream(h, c->xstream, "exchange geometry check (all-reduce of the signature)");
   if (rc) return rc;
   if (w[0] != -w[2] || w[1] != -w[3])
@@ -2431,18 +2397,15 @@ int do_exchange(qh_state_s *h, const std::vector<qh::BlockMove> &moves, int base
   // staging: [2 receive halves][2 send halves (packed only)] of (peers x chunk) amplitudes
   const size_t half = np * n * ab;
   const size_t need_stage = (packed ? 4 : 2) * half;
-  if (c->staging_bytes < need_stage && (packed || !c->custom)) {
-    if (c->staging) {
+  if (c->staging.cap < need_stage && (packed || !c->custom)) {
+    if (c->staging.ptr) {      // (rounds of the previous exchange may still use it)
       HIP_TRY(hipStreamSynchronize(c->cstream));
       HIP_TRY(hipStreamSynchronize(c->pstream));
       HIP_TRY(hipStreamSynchronize(c->xstream));
-      (void)hipFree(c->staging);
-      c->staging = nullptr;
-      c->staging_bytes = 0;
     }
-    HIP_TRY(hipMalloc(&c->staging, need_stage));
-    c->staging_bytes = need_stage;
+    HIP_TRY(c->staging.reserve(need_stage));
   }
+  char *const staging = c->staging.as<char>();
   auto xfer = [&](bool unpack, void *stage, uint64_t start, uint64_t sv, hipStream_t st) {
     qh::XferGeom g = unpack ? xg_land : xg_send;
     for (size_t m = 0; m < np; ++m) g.off[m] |= sv;
@@ -2451,21 +2414,15 @@ int do_exchange(qh_state_s *h, const std::vector<qh::BlockMove> &moves, int base
   if (c->custom) {
     // host-staged transport: synchronous rounds
     const size_t need = np * n * ab;
-    if (c->h_bytes < need) {
-      if (c->h_send) (void)hipHostFree(c->h_send);
-      if (c->h_recv) (void)hipHostFree(c->h_recv);
-      c->h_send = c->h_recv = nullptr;
-      c->h_bytes = 0;
-      HIP_TRY(hipHostMalloc(&c->h_send, need, hipHostMallocDefault));
-      HIP_TRY(hipHostMalloc(&c->h_recv, need, hipHostMallocDefault));
-      c->h_bytes = need;
-    }
+    HIP_TRY(c->h_send.reserve(need));
+    HIP_TRY(c->h_recv.reserve(need));
+    char *const h_send = c->h_send.as<char>(), *const h_recv = c->h_recv.as<char>();
     std::vector<int> peers(np);
     std::vector<void *> sp(np), rp(np);
     for (size_t m = 0; m < np; ++m) {
       peers[m] = moves[m].peer;
-      sp[m] = (char *)c->h_send + m * n * ab;
-      rp[m] = (char *)c->h_recv + m * n * ab;
+      sp[m] = h_send + m * n * ab;
+      rp[m] = h_recv + m * n * ab;
     }
     for (int k = 0; k < K; ++k) {
       const uint64_t sv = slab_vals[k];
@@ -2473,8 +2430,8 @@ int do_exchange(qh_state_s *h, const std::vector<qh::BlockMove> &moves, int base
       if (k == 0) { HIP_TRY(hipEventRecord(c->t0, c->xstream)); }
       for (uint64_t ci = 0; ci < nchunks; ++ci) {
         if (packed) {
-          xfer(false, c->staging, ci << chunk_bits, sv, c->xstream);
-          HIP_TRY(hipMemcpyAsync(c->h_send, c->staging, need, hipMemcpyDeviceToHost, c->xstream));
+          xfer(false, staging, ci << chunk_bits, sv, c->xstream);
+          HIP_TRY(hipMemcpyAsync(h_send, staging, need, hipMemcpyDeviceToHost, c->xstream));
         } else {
           const uint64_t off = qh::deposit_bits(ci << chunk_bits, free_mask) | sv;
           for (size_t m = 0; m < np; ++m)
@@ -2484,8 +2441,8 @@ int do_exchange(qh_state_s *h, const std::vector<qh::BlockMove> &moves, int base
         if (c->custom(c->custom_user, (int)np, peers.data(), sp.data(), rp.data(), n * ab) != 0)
           return fail(QH_ERR_COMM, "host-staged transport: the round callback failed");
         if (packed) {
-          HIP_TRY(hipMemcpyAsync(c->staging, c->h_recv, need, hipMemcpyHostToDevice, c->xstream));
-          xfer(true, c->staging, ci << chunk_bits, sv, c->xstream);
+          HIP_TRY(hipMemcpyAsync(staging, h_recv, need, hipMemcpyHostToDevice, c->xstream));
+          xfer(true, staging, ci << chunk_bits, sv, c->xstream);
         } else {
           const uint64_t off = qh::deposit_bits(ci << chunk_bits, free_mask) | sv;
           for (size_t m = 0; m < np; ++m)
@@ -2517,8 +2474,8 @@ int do_exchange(qh_state_s *h, const std::vector<qh::BlockMove> &moves, int base
       for (uint64_t ci = 0; ci < nchunks; ++ci, ++round) {
         const int par = (int)(round & 1);
         const uint64_t off = qh::deposit_bits(ci << chunk_bits, free_mask) | sv;
-        char *stage = (char *)c->staging + par * half;
-        char *sstage = (char *)c->staging + (2 + par) * half;
+        char *stage = staging + par * half;
+        char *sstage = staging + (2 + par) * half;
         if (packed) {
           if (sent[par]) HIP_TRY(hipStreamWaitEvent(c->pstream, sent[par], 0));
           xfer(false, sstage, ci << chunk_bits, sv, c->pstream);
@@ -2658,15 +2615,10 @@ int qh_comm_destroy(qh_handle h) {
   for (hipEvent_t e : c->pool) (void)hipEventDestroy(e);
   if (c->t0) (void)hipEventDestroy(c->t0);
   if (c->t1) (void)hipEventDestroy(c->t1);
-  if (c->staging) (void)hipFree(c->staging);
-  if (c->d_sig) (void)hipFree(c->d_sig);
-  if (c->h_sig) (void)hipHostFree(c->h_sig);
-  if (c->h_send) (void)hipHostFree(c->h_send);
-  if (c->h_recv) (void)hipHostFree(c->h_recv);
   if (c->xstream) (void)hipStreamDestroy(c->xstream);
   if (c->cstream) (void)hipStreamDestroy(c->cstream);
   if (c->pstream) (void)hipStreamDestroy(c->pstream);
-  delete c;
+  delete c;      // (staging and the pinned buffers go with it: the three streams were drained above)
   h->comm = nullptr;
   return QH_OK;
 }
@@ -2727,9 +2679,9 @@ int qh_comm_allreduce_sum(qh_handle h, double *inout, int count) {
   if (count < 1 || count > kRedBlocks) return fail(QH_ERR_ARG, "count %d", count);
   const int rc = enter(h);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h->d_red, inout, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  NCCL_TRY(qh::rccl().AllReduce(h->d_red, h->d_red, (size_t)count, ncclDouble, ncclSum, h->comm->nccl, h->stream));
-  return read_back(h, inout, h->d_red, count * sizeof(double));
+  HIP_TRY(hipMemcpyAsync(h->d_red(), inout, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  NCCL_TRY(qh::rccl().AllReduce(h->d_red(), h->d_red(), (size_t)count, ncclDouble, ncclSum, h->comm->nccl, h->stream));
+  return read_back(h, inout, h->d_red(), count * sizeof(double));
 }
 
 }  // extern "C"

@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "buffers.hip.h"
 #include "kernels_gate.hip.h"
 
 namespace qh {
@@ -141,10 +142,8 @@ struct Comm {
   hipStream_t xstream = nullptr;     // the links
   hipStream_t cstream = nullptr;     // staging -> home copies / scatter kernels
   hipStream_t pstream = nullptr;     // gather kernels of packed rounds
-  void *staging = nullptr;           // two receive halves (+ two send halves, packed rounds) of (peers x chunk) amplitudes
-  size_t staging_bytes = 0;
-  void *h_send = nullptr, *h_recv = nullptr;   // pinned, custom transport only
-  size_t h_bytes = 0;
+  DeviceBuffer staging;              // two receive halves (+ two send halves, packed rounds) of (peers x chunk) amplitudes
+  PinnedBuffer h_send, h_recv;       // custom transport only
   std::vector<hipEvent_t> pool;      // events of the current exchange (reused by the next)
   size_t pool_used = 0;
   hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -153,7 +152,8 @@ struct Comm {
   qh_xstats stats{};
   qh_xgeom last_geom{};              // how the last exchange was cut (qh_exchange_geometry)
   std::vector<uint64_t> verified;    // geometry signatures the ranks have already compared (RCCL transport)
-  double *d_sig = nullptr, *h_sig = nullptr;   // 4 doubles in HBM / 8 pinned: the signature all-reduce of verify_geometry
+  DeviceBuffer d_sig;                // 4 doubles in HBM / 8 pinned: the signature all-reduce of verify_geometry
+  PinnedBuffer h_sig;
 
   hipEvent_t event() {
     if (pool_used == pool.size()) {

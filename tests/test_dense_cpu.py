@@ -57,6 +57,7 @@ def test_argument_errors_on_dry_handle(dry):
   assert _call(h, [-1, 3]) == native.QH_ERR_BAD_QUBIT
   assert _call(h, [0, 1], ctl_mask=1 << 10) == native.QH_ERR_BAD_QUBIT
   assert _call(h, [3, 3]) == native.QH_ERR_SAME_QUBIT
+  assert _call(h, [3, 3, 10]) == native.QH_ERR_BAD_QUBIT     # both faults: every bit's range is checked first
   assert _call(h, [2, 5], ctl_mask=(1 << 5) | (1 << 7)) == native.QH_ERR_SAME_QUBIT
   # a valid call: dry handles have no state to apply it to
   assert _call(h, [2, 5], ctl_mask=1 << 7) == native.QH_ERR_ARG

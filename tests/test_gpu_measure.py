@@ -12,6 +12,9 @@ import pytest
 from qcc_amd import device, gates, native, workloads
 from qcc_amd.lib import circuit, tensor
 from tests.shard_util import bitmap as _bitmap, check_exact_cdf, logical_of_phys as _logical_of_phys
+from tests.test_dense_cpu import dense_reference
+from tests.test_gpu_expect import _np_expect
+from tests.test_mux_cpu import diag_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -92,16 +95,21 @@ def test_marginal_argument_errors_on_a_real_handle():
     assert st.marginal([0, 1]).tolist() == [0.0, 0.0, 0.0, 1.0]
 
 
-def _check_exact_cdf(st, u):
-  """qh_sample against the inverse CDF of the state in the engine's physical order (bit map before the download)"""
-  bm = _bitmap(st)
-  got = st.sample(u)
-  lstate = _logical_state(st)
+def _check_shots(bm, lstate, got, u):
+  """shots `got` for the uniforms u against the inverse CDF of the state in physical order under the bit map bm"""
   lphys = _logical_of_phys(bm, lstate.size).astype(np.int64)       # logical index of each physical one
   pp = np.abs(lstate[lphys]) ** 2
   phys_of_logical = np.empty(lstate.size, dtype=np.int64)
   phys_of_logical[lphys] = np.arange(lstate.size)
   check_exact_cdf(pp, phys_of_logical[got.astype(np.int64)], u)
+
+
+def _check_exact_cdf(st, u):
+  """qh_sample against the inverse CDF of the state in the engine's physical order (bit map before the download)"""
+  bm = _bitmap(st)
+  got = st.sample(u)
+  lstate = _logical_state(st)
+  _check_shots(bm, lstate, got, u)
   return got, lstate
 
 
@@ -134,6 +142,54 @@ def test_sample_basis_state_and_sparse_states():
     u = np.sort(np.concatenate([np.random.default_rng(1).random(4000), [0.0, 0.25, 0.5, 0.75, np.nextafter(1.0, 0.0)]]))
     got, _ = _check_exact_cdf(st, u)
     assert set(got.tolist()) == {3, 4097, 9000, 16383}
+
+
+@pytest.mark.parametrize('bw', [128, 64])
+def test_readers_share_one_scratch_buffer_on_one_handle(bw):
+  """The readers carve one scratch buffer whose required size goes up and down between calls, and the staged uploads of
+  qh_apply_matrix (a ring) and qh_apply_diag (one slot) interleave: no region aliases another, no slot is overwritten early."""
+  n = 12
+  rng = np.random.default_rng(4000 + bw)
+  full = (1 << n) - 1
+  rnd = lambda: int(rng.integers(0, 1 << n))      # noqa: E731
+  x0, x1 = rnd() | (1 << (n - 1)), rnd() & (full >> 1)          # two distinct x masks; 20 strings on the first: two batches
+  xs = [x0] * 20 + [x1] * 12 + [rnd() for _ in range(8)]
+  zs = [rnd() for _ in range(40)]
+  u_many, u_few = np.sort(rng.random(4096)), np.sort(rng.random(3))
+  b2, b11 = [int(b) for b in rng.permutation(n)[:2]], [int(b) for b in rng.permutation(n)[:11]]
+  with _prepared(n, bw, native.QH_FUSE_SWEEP, seed=200 + bw) as st:
+    bm = _bitmap(st)
+    m2 = st.marginal(b2)
+    s_many = st.sample(u_many)
+    e40 = st.expect_pauli(xs, zs)
+    m11 = st.marginal(b11)
+    s_few = st.sample(u_few)
+    e1 = st.expect_pauli(xs[-1:], zs[-1:])
+    m0 = st.marginal([])
+    assert _bitmap(st) == bm                                    # readers only: the layout they all ran on
+    a = _logical_state(st)
+    p = np.abs(a) ** 2
+    _check_marginal(m2, _np_marginal(p, b2), bw)
+    _check_marginal(m11, _np_marginal(p, b11), bw)
+    assert m0.shape == (1,) and abs(m0[0] - p.sum()) < (1e-12 if bw == 128 else 1e-6)
+    _check_shots(bm, a, s_many, u_many)
+    _check_shots(bm, a, s_few, u_few)
+    want = np.array([_np_expect(a, x, z) for x, z in zip(xs, zs)])
+    assert float(np.max(np.abs(e40 - want))) < 1e-12            # (double accumulation at both widths: tests/test_gpu_expect.py)
+    assert abs(e1[0] - want[-1]) < 1e-12
+    # three matrices (k = 2) and three diagonals (k = 3), interleaved, nothing read in between
+    for _ in range(3):
+      mb, db = [int(b) for b in rng.permutation(n)[:2]], [int(b) for b in rng.permutation(n)[:3]]
+      m, _r = np.linalg.qr(rng.normal(size=(4, 4)) + 1j * rng.normal(size=(4, 4)))
+      v = np.exp(2j * np.pi * rng.random(8))
+      st.apply_matrix(m, mb)
+      st.apply_diag(v, db)
+      a = diag_reference(dense_reference(a, n, m, mb), n, v, db)
+    got = _logical_state(st)
+  if bw == 128:                                                 # (tests/test_gpu_dense.py::_check)
+    assert float(np.max(np.abs(got - a))) < 1e-12
+  else:
+    assert float(np.linalg.norm(got - a) / np.linalg.norm(a)) < 1e-5
 
 
 def test_seeded_histogram_passes_a_g_test():

@@ -55,6 +55,7 @@ def test_marginal_argument_errors(dry):
   assert _marg(dry, [10]) == native.QH_ERR_BAD_QUBIT
   assert _marg(dry, [-1]) == native.QH_ERR_BAD_QUBIT
   assert _marg(dry, [3, 5, 3]) == native.QH_ERR_SAME_QUBIT
+  assert _marg(dry, [3, 3, 10]) == native.QH_ERR_BAD_QUBIT    # both faults: every bit's range is checked first
   assert _marg(dry, [3, 5]) == native.QH_ERR_ARG           # valid, but a dry handle has no state
   assert b'dry' in lib.qh_last_error()
   assert _marg(dry, []) == native.QH_ERR_ARG

@@ -192,6 +192,7 @@ def test_argument_errors_on_dry_handle(dry):
   assert _mux(h, [3, 3], 1) == native.QH_ERR_SAME_QUBIT
   assert _mux(h, [3, 4], 4) == native.QH_ERR_SAME_QUBIT
   assert _diag(h, [5, 1, 5]) == native.QH_ERR_SAME_QUBIT
+  assert _diag(h, [5, 5, 20]) == native.QH_ERR_BAD_QUBIT     # both faults: every bit's range is checked first
   # valid calls, k = 0 and k = 16 included: a planner-only handle has no state to apply them to
   for rc in (_mux(h, [2, 5], 7), _mux(h, [], 3), _mux(h, list(range(16)), 19), _diag(h, [2, 5]), _diag(h, []),
              _diag(h, list(range(4, 20)))):
