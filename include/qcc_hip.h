@@ -296,6 +296,52 @@ int qh_project_bits(qh_handle h, uint64_t mask, uint64_t value);
  * and layout.  nterms = 0 is allowed.  Errors: QH_ERR_ARG (null, dry handle), QH_ERR_BAD_QUBIT (mask bits >= nbits_global). */
 int qh_expect_pauli(qh_handle h, uint64_t nterms, const uint64_t *xmask, const uint64_t *zmask, double *out);
 
+/* ---- two states (kernels_inner.hip.h) ------------------------------------ */
+/* A new handle on src's device holding a copy of src's state: what src has queued runs first, then one device-to-device
+ * copy of the buffer as it lies, with nbits (local and global), width, shard index, fusion level and the bit map as it is
+ * (no canonical order; src's pointer, layout and relayout mode are as before).  The clone always owns HBM memory and its own
+ * stream, also when src is attached or host-mapped; it starts with zeroed stats, nothing queued, relayout mode undecided and
+ * no communicator.  The copy is complete when the call returns.
+ * Errors: QH_ERR_ARG (null, dry handle), QH_ERR_NOMEM (no room: nothing is created; src's STATE is unchanged, but what it
+ * had queued has run, and a flush may re-lay it out).                                                                     */
+int qh_clone(qh_handle src, qh_handle *out);
+/* dst's state := src's, amplitudes and bit map together (restore a snapshot).  What src has queued runs first; what dst has
+ * queued is dropped, as by qh_init_basis.  Waits for dst's outstanding exchange arrivals and stream work, then copies into
+ * dst's CURRENT buffer: the pointer of an attached or host-mapped dst stays valid, dst's relayout mode and second buffer stay
+ * as they are.  The host waits for the copy: after return either handle may be used at once.
+ * Errors: QH_ERR_ARG (null, dry handle, dst == src, another device, different nbits (local or global), width or shard
+ * index): nothing changes.                                                                                              */
+int qh_copy(qh_handle dst, qh_handle src);
+/* out = sum_i conj(a_i) b_i as (re, im) over this shard's amplitudes, matched by LOGICAL index: per shard, not normalised;
+ * qh_inner(a, a, out) is the shard's norm with out[1] == 0.0 exactly.  Runs what both handles have queued; a's stream waits
+ * for b's flushed work (an event), the read runs on a's stream and the host waits for it: on return b is free again.  Reads
+ * only: state, bit map, relayout mode and device pointer of both handles are as before, wherever their local bits sit --
+ * equal layouts are read as two linear streams (16 bytes per lane and load at either width), different ones tile by tile
+ * (qh_inner_tiles below), each state in runs of 16 amplitudes.  Sums in double from the stored amplitudes, in a fixed order: bitwise reproducible for given states and
+ * layouts.  a's qh_stats.kernels_launched grows by 1 (one read of the two states), b's by 0.
+ * Both handles must hold the same logical bits in the shard index, at the same positions, with the same shard index:
+ * otherwise QH_ERR_NONLOCAL (exchange first; out untouched).
+ * Errors: QH_ERR_ARG (null, dry handle, another device, different nbits (local or global) or width).                     */
+int qh_inner(qh_handle a, qh_handle b, double out[2]);
+/* How qh_inner would walk a and b right now (nothing runs, nothing is flushed; planner-only handles too).  Positions are
+ * physical, local.  QH_INNER_TILES: bit k of an in-tile index is position tile_a[k] in a's enumeration and tile_b[k] in
+ * b's (both ascending, both start 0,1,2,3); a's amplitude at in-tile index r pairs with b's at sum_k bit_k(r) << shuffle[k];
+ * bit k of a tile number is position rest_a[k] in a and rest_b[k] in b.  Host arithmetic on the two bit maps only: dry
+ * handles are allowed and the handles' devices are not compared.  Errors: QH_ERR_ARG (null, different nbits (local or
+ * global) or width), QH_ERR_NONLOCAL as qh_inner.                                                                         */
+#define QH_INNER_LINEAR 0       /* same layout: both states front to back                      */
+#define QH_INNER_TILES 1        /* tiles of 2^8 amplitudes, b's crossing through LDS           */
+#define QH_INNER_GATHER 2       /* fewer than 8 local bits: one amplitude at a time            */
+typedef struct {
+  uint32_t path;               /* QH_INNER_*                                                  */
+  uint32_t nrest;              /* tile-number bits: nbits_local - 8                           */
+  uint64_t free_a, free_b;     /* a tile's free bits, in a's and in b's positions             */
+  uint8_t tile_a[8], tile_b[8], shuffle[8];
+  uint8_t rest_a[56], rest_b[56];
+  uint8_t pos_b[64];           /* b's position of the logical bit a keeps at position p       */
+} qh_inner_tiles;
+int qh_inner_plan(qh_handle a, qh_handle b, qh_inner_tiles *out);
+
 /* ---- measurement of the engine itself ----------------------------------- */
 typedef struct {
   uint64_t gates_submitted;   /* qh_apply* calls accepted                      */

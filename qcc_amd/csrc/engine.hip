@@ -27,6 +27,7 @@
 #include "kernels_mux.hip.h"
 #include "kernels_measure.hip.h"
 #include "kernels_expect.hip.h"
+#include "kernels_inner.hip.h"
 #include "planner.h"
 #include "kernels_sweep.hip.h"
 
@@ -73,6 +74,7 @@ struct qh_state_s {
   std::vector<qh::GateRec> queue;
   qh_stats stats{};
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t ev_read = nullptr;   // qh_inner: recorded behind this handle's flushed work when ANOTHER handle's stream reads it
   std::vector<hipEvent_t> laps;   // qh_timer_lap: events on the stream, read back by qh_timer_laps
   size_t laps_used = 0;
   // Scratch (buffers.hip.h): released by the members' destructors at `delete h`, after qh_destroy has made the device
@@ -701,6 +703,7 @@ int common_init(qh_state_s *h) {
 }
 
 int check_args(int nbits, int bit_width) {
+  static_assert(qh::kInnerMaxLocalBits == 40, "kernels_inner.hip.h sizes its tables for the limit below");
   if (nbits < 1 || nbits > 40) return fail(QH_ERR_ARG, "nbits %d out of range [1,40]", nbits);
   if (bit_width != 64 && bit_width != 128)
     return fail(QH_ERR_BAD_DTYPE, "bit_width %d (want 64 or 128)", bit_width);
@@ -723,7 +726,7 @@ int select_device(int device) {
 extern "C" {
 
 const char *qh_last_error(void) { return g_err.c_str(); }
-int qh_version(void) { return 109; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
+int qh_version(void) { return 110; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
 
 int qh_device_count(int *count) {
   if (!count) return fail(QH_ERR_ARG, "null");
@@ -851,6 +854,7 @@ int qh_destroy(qh_handle h) {
     (void)qh_comm_destroy(h);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
+    if (h->ev_read) (void)hipEventDestroy(h->ev_read);
     for (hipEvent_t e : h->laps) (void)hipEventDestroy(e);
     if (h->owns_mem && h->d_psi) (void)hipFree(h->d_psi);
     if (h->d_alt) (void)hipFree(h->d_alt);
@@ -1883,6 +1887,170 @@ int qh_project_bits(qh_handle h, uint64_t mask, uint64_t value) {
                        m.local, v.local);
   });
   return check_launch(h);
+}
+
+}  // extern "C"
+
+// ---- two states: qh_clone, qh_copy, qh_inner (kernels_inner.hip.h) ---------------------------------------------------
+namespace {
+
+constexpr uint64_t kInnerBlocks = 4096;     // blocks at most (one slab row of (re, im) each)
+
+// both handles live, on one device, of one shape
+int check_pair(const qh_state_s *a, const qh_state_s *b, const char *who) {
+  if (!a || !b) return fail(QH_ERR_ARG, "%s: null handle", who);
+  if (a->dry || b->dry) return fail(QH_ERR_ARG, "%s: not on a dry (planner-only) handle", who);
+  if (a->device != b->device) return fail(QH_ERR_ARG, "%s: the handles live on devices %d and %d", who, a->device, b->device);
+  if (a->nloc != b->nloc || a->nglob != b->nglob || a->bw != b->bw)
+    return fail(QH_ERR_ARG, "%s: %d of %d qubits at width %d against %d of %d at width %d", who, a->nloc, a->nglob, a->bw, b->nloc,
+                b->nglob, b->bw);
+  return QH_OK;
+}
+
+int plan_pair(const qh_state_s *a, const qh_state_s *b, const char *who, qh_inner_tiles *out) {
+  if (a->shard != b->shard)
+    return fail(QH_ERR_NONLOCAL, "%s: shard %llu against shard %llu; exchange first", who, (unsigned long long)a->shard,
+                (unsigned long long)b->shard);
+  const int l = qh::plan_inner(a->nloc, a->nglob, a->perm, b->perm, out);
+  if (l >= 0)
+    return fail(QH_ERR_NONLOCAL, "%s: logical bit %d is at physical bit %d of one handle and %d of the other, and the shard index "
+                "holds one of them (local bits: %d); exchange first", who, l, a->perm[l], b->perm[l], a->nloc);
+  return QH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qh_clone(qh_handle src, qh_handle *out) {
+  if (!src || !out) return fail(QH_ERR_ARG, "clone: null handle or out");
+  int rc = enter(src);
+  if (rc) return rc;
+  auto *h = new qh_state_s;
+  h->nloc = src->nloc;
+  h->nglob = src->nglob;
+  h->bw = src->bw;
+  h->device = src->device;
+  h->shard = src->shard;
+  const size_t bytes = (size_t)src->amp_bytes() << src->nloc;
+  hipError_t e = alloc_state_buffer(&h->d_psi, bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    h->d_psi = nullptr;
+    delete h;
+    return fail(QH_ERR_NOMEM, "clone: hipMalloc(%zu bytes) for %d qubits: %s", bytes, src->nloc, hipGetErrorString(e));
+  }
+  h->owns_mem = true;
+  e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+  if (e != hipSuccess) {
+    (void)hipFree(h->d_psi);
+    delete h;
+    return fail(QH_ERR_HIP, "clone: hipStreamCreate: %s", hipGetErrorString(e));
+  }
+  h->owns_stream = true;
+  rc = common_init(h);
+  if (rc == QH_OK) {
+    h->fusion = src->fusion;
+    memcpy(h->perm, src->perm, sizeof h->perm);
+    e = hipMemcpyAsync(h->d_psi, src->d_psi, bytes, hipMemcpyDefault, src->stream);
+    if (e != hipSuccess) rc = fail(QH_ERR_HIP, "clone: hipMemcpyAsync: %s", hipGetErrorString(e));
+    else rc = wait_stream(src, src->stream, "qh_clone");
+  }
+  if (rc) {
+    const std::string why = g_err;
+    qh_destroy(h);
+    g_err = why;
+    return rc;
+  }
+  *out = h;
+  return QH_OK;
+}
+
+int qh_copy(qh_handle dst, qh_handle src) {
+  int rc = check_pair(dst, src, "copy");
+  if (rc) return rc;
+  if (dst == src) return fail(QH_ERR_ARG, "copy: dst == src");
+  if (dst->shard != src->shard)
+    return fail(QH_ERR_ARG, "copy: shard %llu against shard %llu", (unsigned long long)dst->shard, (unsigned long long)src->shard);
+  if ((rc = enter(src))) return rc;
+  // dst is replaced whole: nothing it has queued is worth running and a failed flush is forgotten (as the initialisations)
+  dst->queue.clear();
+  dst->poisoned = false;
+  if (dst->comm) qh::wait_all_arrivals(&dst->comm->arrivals, dst->stream);
+  if ((rc = wait_stream(dst, dst->stream, "qh_copy"))) return rc;
+  HIP_TRY(hipMemcpyAsync(dst->d_psi, src->d_psi, (size_t)src->amp_bytes() << src->nloc, hipMemcpyDefault, src->stream));
+  if ((rc = wait_stream(src, src->stream, "qh_copy"))) return rc;
+  memcpy(dst->perm, src->perm, sizeof dst->perm);
+  return QH_OK;
+}
+
+int qh_inner_plan(qh_handle a, qh_handle b, qh_inner_tiles *out) {
+  if (!a || !b || !out) return fail(QH_ERR_ARG, "inner_plan: null handle or out");
+  if (a->nloc != b->nloc || a->nglob != b->nglob || a->bw != b->bw) return fail(QH_ERR_ARG, "inner_plan: handles of different shapes");
+  qh_inner_tiles t;
+  const int rc = plan_pair(a, b, "inner_plan", &t);
+  if (rc) return rc;
+  *out = t;
+  return QH_OK;
+}
+
+int qh_inner(qh_handle a, qh_handle b, double out[2]) {
+  int rc = check_pair(a, b, "inner");
+  if (rc) return rc;
+  if (!out) return fail(QH_ERR_ARG, "inner: null out");
+  if ((rc = enter(a))) return rc;
+  if (b != a && (rc = enter(b))) return rc;
+  qh_inner_tiles pl;
+  if ((rc = plan_pair(a, b, "inner", &pl))) return rc;
+  qh::ScratchLayout lay;
+  const size_t slab_off = lay.add((size_t)kInnerBlocks * 2 * sizeof(double)), out_off = lay.add(2 * sizeof(double));
+  HIP_TRY(a->meas.reserve(lay.total));
+  double *slab = (double *)(a->meas.as<char>() + slab_off), *dout = (double *)(a->meas.as<char>() + out_off);
+  if (b != a) {      // a's stream reads b: behind everything b's stream has been given
+    if (!b->ev_read) HIP_TRY(hipEventCreateWithFlags(&b->ev_read, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(b->ev_read, b->stream));
+    HIP_TRY(hipStreamWaitEvent(a->stream, b->ev_read, 0));
+  }
+  uint64_t nblk = 1;
+  with_real(a, [&](auto x) {
+    using R = decltype(x);
+    using A = typename qh::AmpT<R>::type;
+    const A *pa = (const A *)a->d_psi, *pb = (const A *)b->d_psi;
+    if (pl.path == QH_INNER_LINEAR) {
+      const int items = a->nloc - qh::InnerItem<R>::kAmpBits;      // log2 of the 16-byte items of a state
+      const int cw = std::min(8 + 3, items);        // 256 threads x kInnerLoads
+      const uint64_t nchunks = 1ull << (items - cw);
+      nblk = std::min(nchunks, kInnerBlocks);
+      hipLaunchKernelGGL(qh::k_inner_linear<R>, dim3((unsigned)nblk), dim3(256), 0, a->stream, pa, pb, cw, (uint32_t)(nchunks / nblk), slab);
+    } else if (pl.path == QH_INNER_TILES) {
+      qh::InnerTileArgs t{};
+      memcpy(t.tile_a, pl.tile_a, 8);
+      memcpy(t.tile_b, pl.tile_b, 8);
+      memcpy(t.shuffle, pl.shuffle, 8);
+      memcpy(t.rest_a, pl.rest_a, sizeof t.rest_a);
+      memcpy(t.rest_b, pl.rest_b, sizeof t.rest_b);
+      t.nrest = (int)pl.nrest;
+      t.cbits = std::min(qh::kInnerChunkBits, t.nrest);
+      const uint64_t nchunks = 1ull << (t.nrest - t.cbits);
+      nblk = std::min(nchunks, kInnerBlocks);
+      t.cpb = (uint32_t)(nchunks / nblk);
+      hipLaunchKernelGGL(qh::k_inner_tiles<R>, dim3((unsigned)nblk), dim3(256), 0, a->stream, pa, pb, t, slab);
+    } else {
+      qh::InnerGatherArgs g{};
+      g.nloc = a->nloc;
+      memcpy(g.pos_b, pl.pos_b, sizeof g.pos_b);
+      hipLaunchKernelGGL(qh::k_inner_gather<R>, dim3(1), dim3(256), 0, a->stream, pa, pb, g, slab);
+    }
+  });
+  hipLaunchKernelGGL(qh::k_expect_fold, dim3(2), dim3(256), 0, a->stream, (const double *)slab, (uint32_t)nblk, 2, 1.0, dout);
+  if ((rc = check_launch(a))) return rc;
+  double vals[2];
+  if ((rc = read_back(a, vals, dout, sizeof vals, "qh_inner"))) return rc;
+  out[0] = vals[0];
+  out[1] = vals[1];
+  a->stats.kernels_launched += 1;      // one read of the two states (the fold is not counted, as in qh_expect_pauli)
+  a->stats.bytes_swept += 2 * ((1ull << a->nloc) * a->amp_bytes());
+  return QH_OK;
 }
 
 }  // extern "C"

@@ -368,6 +368,34 @@ class DeviceState:
                                           out.ctypes.data_as(_dp)))
     return out
 
+  # -- two states ---------------------------------------------------------------
+  def clone(self):
+    """A new DeviceState holding a copy of this one as it lies -- amplitudes, bit map, shard geometry, fusion level --
+    in HBM memory of its own (qh_clone); queued gates run first."""
+    h = ctypes.c_void_p()
+    native.check(self.lib.qh_clone(self.h, ctypes.byref(h)))
+    other = object.__new__(DeviceState)
+    other.lib, other.nbits, other.bit_width, other.dtype = self.lib, self.nbits, self.bit_width, self.dtype
+    other.h, other.nbits_global = h, self.nbits_global
+    return other
+
+  def copy_from(self, other):
+    """This state := other's, amplitudes and bit map (qh_copy); what this state has queued is dropped."""
+    native.check(self.lib.qh_copy(self.h, other.h))
+
+  def inner(self, other):
+    """complex <self|other> = sum_i conj(self_i) other_i by LOGICAL index, over this shard, not normalised (qh_inner:
+    both states are read where they lie, whatever their layouts)."""
+    out = (ctypes.c_double * 2)()
+    native.check(self.lib.qh_inner(self.h, other.h, out))
+    return complex(out[0], out[1])
+
+  def inner_plan(self, other):
+    """How inner(other) would walk the two states right now (qh_inner_plan), as a dict."""
+    t = native.QhInnerTiles()
+    native.check(self.lib.qh_inner_plan(self.h, other.h, ctypes.byref(t)))
+    return t.as_dict()
+
   def project_bits(self, mask, value):
     """Zero every amplitude whose LOGICAL bits under mask differ from value (qh_project_bits); renormalise with scale."""
     native.check(self.lib.qh_project_bits(self.h, int(mask), int(value)))

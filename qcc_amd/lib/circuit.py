@@ -167,6 +167,33 @@ def _alive(ref):
     return circ
 
 
+class Snapshot:
+    """A copy of a circuit's state at one moment (qc.snapshot): a device state of its own in HBM (or, with a device that
+    cannot clone, the amplitudes on the host), the number of qubits and the width.  qc.restore() puts it back,
+    qc.overlap() / qc.fidelity() compare against it.  close() (or leaving a `with` block, or collection) releases it."""
+
+    def __init__(self, nbits, width, dev=None, host=None):
+        self.nbits, self.width = int(nbits), int(width)
+        self._dev, self._host = dev, host
+
+    def close(self):
+        dev, self._dev, self._host = self._dev, None, None
+        if dev is not None:
+            dev.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pylint: disable=broad-except
+            pass
+
+
 class qc:
     """State + gate application + (optional) IR recording."""
 
@@ -875,6 +902,72 @@ class qc:
         c = np.asarray(coeffs, dtype=np.complex128)
         total = complex(np.dot(c, vals)) if len(coeffs) else 0j
         return total if np.any(c.imag != 0) else float(total.real)
+
+    # Two states (extensions; the reference compares states on the host: State.diff, the swap and Hadamard tests).  With a
+    # device that cannot clone / copy_from / inner, the amplitudes go through qc.psi on the host instead.
+    def snapshot(self):
+        """A Snapshot of the state as it is now (qh_clone: queued gates run first, one device-to-device copy)."""
+        dev = self._ensure_device()
+        if hasattr(dev, 'clone'):
+            return Snapshot(self._nbits, self._width(), dev=dev.clone())
+        return Snapshot(self._nbits, self._width(), host=np.array(self.psi, dtype=tensor.tensor_type()).reshape(-1))
+
+    def _same_shape(self, other, what):
+        if not isinstance(other, (qc, Snapshot)):
+            raise ValueError(f'{what}: a qc or a Snapshot, not {type(other).__name__}')
+        width = other.width if isinstance(other, Snapshot) else other._width()      # pylint: disable=protected-access
+        if other.nbits != self._nbits or width != self._width() or self._nbits == 0:
+            raise ValueError(f'{what}: {other.nbits} qubits at width {width} against {self._nbits} at width {self._width()}')
+        if isinstance(other, Snapshot) and other._dev is None and other._host is None:      # pylint: disable=protected-access
+            raise ValueError(f'{what}: the snapshot has been closed')
+
+    def restore(self, snap):
+        """The state := the snapshot's (qh_copy).  Gates still queued, on the host side or in the engine, are dropped."""
+        if not isinstance(snap, Snapshot):
+            raise ValueError(f'restore: a Snapshot, not {type(snap).__name__}')
+        self._same_shape(snap, 'restore')
+        self._q_ops, self._q_gates = [], []
+        dev = self._ensure_device()
+        if snap._dev is not None and hasattr(dev, 'copy_from'):      # pylint: disable=protected-access
+            dev.copy_from(snap._dev)                                   # pylint: disable=protected-access
+        else:
+            host = snap._host if snap._host is not None else snap._dev.download()      # pylint: disable=protected-access
+            dev.upload(np.asarray(host))
+        # neither the product description nor a host copy describes the state any more (as _drain)
+        self._product_flag = False
+        self._host_ok = False
+        if self._aliased():
+            self._dev.sync()
+
+    @staticmethod
+    def _host_amps(other):
+        if isinstance(other, qc):
+            return np.asarray(other.psi).reshape(-1)
+        if other._host is not None:      # pylint: disable=protected-access
+            return other._host           # pylint: disable=protected-access
+        return other._dev.download()     # pylint: disable=protected-access
+
+    def overlap(self, other):
+        """complex <self|other> for another circuit or a Snapshot of the same size and width, on the device (qh_inner:
+        both states are read where they lie).  Not divided by the norms."""
+        self._same_shape(other, 'overlap')
+        dev = self._ensure_device()
+        odev = other._ensure_device() if isinstance(other, qc) else other._dev      # pylint: disable=protected-access
+        if hasattr(dev, 'inner') and odev is not None and hasattr(odev, 'inner'):
+            return complex(dev.inner(odev))
+        return complex(np.vdot(np.asarray(self.psi).reshape(-1), self._host_amps(other)))
+
+    def fidelity(self, other):
+        """|<self|other>|^2 / (|self|^2 |other|^2)."""
+        ov = self.overlap(other)
+        na = self.overlap(self).real
+        if isinstance(other, qc):
+            nb = other.overlap(other).real
+        elif other._dev is not None and hasattr(other._dev, 'inner'):      # pylint: disable=protected-access
+            nb = other._dev.inner(other._dev).real                          # pylint: disable=protected-access
+        else:
+            nb = float(np.vdot(self._host_amps(other), self._host_amps(other)).real)
+        return float(abs(ov) ** 2 / (na * nb))
 
     def pauli_expectation(self, idx):
         p0, _ = self.measure_bit(idx, 0, False)

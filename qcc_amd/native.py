@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB_PATH = os.environ.get('QCC_HIP_LIB') or os.path.join(PKG, 'libqcc_hip.so')  # env: A/B builds only
 SOURCES = [os.path.join(PKG, 'csrc', f) for f in
-           ('engine.hip', 'buffers.hip.h', 'kernels_gate.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_measure.hip.h', 'kernels_expect.hip.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h',
+           ('engine.hip', 'buffers.hip.h', 'kernels_gate.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_measure.hip.h', 'kernels_expect.hip.h', 'kernels_inner.hip.h', 'inner_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h',
             'sweep_island_rb2.inc', 'sweep_island_rb3.inc', 'sweep_island_rb4.inc',
             'sweep_island_rb5.inc', 'sweep_island_f32_rb2.inc', 'sweep_island_f32_rb3.inc',
             'sweep_island_f32_rb4.inc', 'sweep_island_f32_rb5.inc', 'sweep_island_f32_rb6.inc', 'sweep_handlers.inc',
@@ -34,6 +34,20 @@ class QhStats(ctypes.Structure):
 
   def as_dict(self):
     return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+QH_INNER_LINEAR, QH_INNER_TILES, QH_INNER_GATHER = 0, 1, 2
+
+
+class QhInnerTiles(ctypes.Structure):
+  """include/qcc_hip.h qh_inner_tiles: how qh_inner walks two states whose bit maps differ."""
+  _u8 = ctypes.c_uint8
+  _fields_ = [('path', ctypes.c_uint32), ('nrest', ctypes.c_uint32), ('free_a', _u64), ('free_b', _u64),
+              ('tile_a', _u8 * 8), ('tile_b', _u8 * 8), ('shuffle', _u8 * 8), ('rest_a', _u8 * 56), ('rest_b', _u8 * 56),
+              ('pos_b', _u8 * 64)]
+
+  def as_dict(self):
+    return {k: (int(getattr(self, k)) if isinstance(getattr(self, k), int) else list(getattr(self, k))) for k, _ in self._fields_}
 
 
 # name -> (restype, argtypes); every symbol declared in include/qcc_hip.h
@@ -83,6 +97,10 @@ SIGNATURES = {
     'qh_sample': (_i32, [_vp, _u64, _dp, ctypes.POINTER(ctypes.c_uint64)]),
     'qh_project_bits': (_i32, [_vp, _u64, _u64]),
     'qh_expect_pauli': (_i32, [_vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _dp]),
+    'qh_clone': (_i32, [_vp, ctypes.POINTER(_vp)]),
+    'qh_copy': (_i32, [_vp, _vp]),
+    'qh_inner': (_i32, [_vp, _vp, _dp]),
+    'qh_inner_plan': (_i32, [_vp, _vp, ctypes.POINTER(QhInnerTiles)]),
     'qh_get_stats': (_i32, [_vp, ctypes.POINTER(QhStats)]),
     'qh_reset_stats': (_i32, [_vp]),
     'qh_timer_begin': (_i32, [_vp]),
