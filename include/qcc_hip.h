@@ -342,6 +342,34 @@ typedef struct {
 } qh_inner_tiles;
 int qh_inner_plan(qh_handle a, qh_handle b, qh_inner_tiles *out);
 
+/* ---- growing and shrinking a state (kernels_resize.hip.h) ----------------- */
+/* Both calls make a NEW handle and leave src as qh_clone leaves it: what src has queued runs first (exchange arrivals are
+ * waited for); src keeps its amplitudes, bit map, relayout mode and device pointer.  The new handle lives on src's device with
+ * src's width, shard index and fusion level, always owns HBM memory and a stream of its own (also beside an attached or
+ * host-mapped src), starts with zeroed stats, nothing queued, relayout mode undecided and no communicator, and is complete
+ * when the call returns.  src's qh_stats.kernels_launched grows by 1, bytes_algorithmic and bytes_swept by the bytes of src
+ * (read once) plus the bytes of the new state (written once).  Beside a planner-only src the new handle is planner-only: the
+ * new sizes and bit map, no data, weight untouched.
+ * Errors of both: QH_ERR_ARG (null pointer, k outside [1,16], a resulting local size outside [1,40] or global size above
+ * 62), QH_ERR_NOMEM (nothing is created).
+ *
+ * qh_extend: new state = src (x) f in np.kron order.  The k new qubits are the k least significant LOGICAL bits; logical bit
+ * b of src becomes b + k.  f = amps, 2^k complex128 values (interleaved re,im, as in qh_init_product; not referenced after
+ * the call returns), or, where amps is NULL, the basis state |basis> (basis >= 2^k: QH_ERR_ARG).  Nothing of src is re-laid
+ * out: the new bits sit at physical positions nbits_local .. nbits_local + k - 1, every local bit of src keeps its position,
+ * every bit held by the shard index moves up by k: new[(j << nbits_local) | p] = f[j] * src[p], one read of src, 2^k linear
+ * writes (zeros where f[j] is 0).  One complex product per amplitude in the handle's width; entries that are exactly 0 or 1
+ * give 0 or the stored amplitude, equal as numbers.  Shard handles: the new bits are local on every shard.               */
+int qh_extend(qh_handle src, int k, const double *amps, uint64_t basis, qh_handle *out);
+/* qh_release: new state = the slice of src where LOGICAL bit bits[j] has the value of bit j of `value`, for the k distinct bits
+ * listed (value >= 2^k: QH_ERR_ARG; QH_ERR_BAD_QUBIT, QH_ERR_SAME_QUBIT; at least one local qubit must remain).  A listed bit
+ * held by the shard index is QH_ERR_NONLOCAL: nothing is created, weight untouched.  The remaining bits keep their order,
+ * logically and physically, and are renumbered densely: logical l becomes l - (listed bits below l), physical p becomes
+ * p - (released positions below p).  Amplitudes are copied as stored; nothing is rescaled (qh_scale).  weight (may be NULL):
+ * weight[0] = sum |a|^2 of the amplitudes kept, weight[1] = of those dropped, over this shard, not normalised, summed in
+ * double in a fixed order (bitwise reproducible for a given state and layout).  One kernel, one read of src.              */
+int qh_release(qh_handle src, int k, const int32_t *bits, uint64_t value, double weight[2], qh_handle *out);
+
 /* ---- measurement of the engine itself ----------------------------------- */
 typedef struct {
   uint64_t gates_submitted;   /* qh_apply* calls accepted                      */

@@ -28,6 +28,7 @@
 #include "kernels_measure.hip.h"
 #include "kernels_expect.hip.h"
 #include "kernels_inner.hip.h"
+#include "kernels_resize.hip.h"
 #include "planner.h"
 #include "kernels_sweep.hip.h"
 
@@ -726,7 +727,7 @@ int select_device(int device) {
 extern "C" {
 
 const char *qh_last_error(void) { return g_err.c_str(); }
-int qh_version(void) { return 110; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
+int qh_version(void) { return 111; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
 
 int qh_device_count(int *count) {
   if (!count) return fail(QH_ERR_ARG, "null");
@@ -1918,6 +1919,51 @@ int plan_pair(const qh_state_s *a, const qh_state_s *b, const char *who, qh_inne
   return QH_OK;
 }
 
+// A handle that make_sibling made goes away again (what was to fill it failed): rc and its message are kept
+int drop_sibling(qh_state_s *h, int rc) {
+  const std::string why = g_err;
+  qh_destroy(h);
+  g_err = why;
+  return rc;
+}
+
+// A new handle beside src, for qh_clone / qh_extend / qh_release: on src's device, of src's width, shard index and fusion
+// level, with nloc of nglob qubits, HBM memory and a stream of its own, zeroed stats, nothing queued, relayout undecided, no
+// communicator and the identity bit map.  Beside a planner-only src: planner-only, no device call.  QH_ERR_NOMEM: nothing
+// is created.
+int make_sibling(const qh_state_s *src, int nloc, int nglob, const char *who, qh_state_s **out) {
+  auto *h = new qh_state_s;
+  h->nloc = nloc;
+  h->nglob = nglob;
+  h->bw = src->bw;
+  h->device = src->device;
+  h->shard = src->shard;
+  h->dry = src->dry;
+  if (!h->dry) {
+    const size_t bytes = (size_t)h->amp_bytes() << nloc;
+    hipError_t e = alloc_state_buffer(&h->d_psi, bytes);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      h->d_psi = nullptr;
+      delete h;
+      return fail(QH_ERR_NOMEM, "%s: hipMalloc(%zu bytes) for %d qubits: %s", who, bytes, nloc, hipGetErrorString(e));
+    }
+    h->owns_mem = true;
+    e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+      (void)hipFree(h->d_psi);
+      delete h;
+      return fail(QH_ERR_HIP, "%s: hipStreamCreate: %s", who, hipGetErrorString(e));
+    }
+    h->owns_stream = true;
+  }
+  const int rc = common_init(h);
+  if (rc) return drop_sibling(h, rc);
+  h->fusion = src->fusion;
+  *out = h;
+  return QH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1926,42 +1972,13 @@ int qh_clone(qh_handle src, qh_handle *out) {
   if (!src || !out) return fail(QH_ERR_ARG, "clone: null handle or out");
   int rc = enter(src);
   if (rc) return rc;
-  auto *h = new qh_state_s;
-  h->nloc = src->nloc;
-  h->nglob = src->nglob;
-  h->bw = src->bw;
-  h->device = src->device;
-  h->shard = src->shard;
-  const size_t bytes = (size_t)src->amp_bytes() << src->nloc;
-  hipError_t e = alloc_state_buffer(&h->d_psi, bytes);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    h->d_psi = nullptr;
-    delete h;
-    return fail(QH_ERR_NOMEM, "clone: hipMalloc(%zu bytes) for %d qubits: %s", bytes, src->nloc, hipGetErrorString(e));
-  }
-  h->owns_mem = true;
-  e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    (void)hipFree(h->d_psi);
-    delete h;
-    return fail(QH_ERR_HIP, "clone: hipStreamCreate: %s", hipGetErrorString(e));
-  }
-  h->owns_stream = true;
-  rc = common_init(h);
-  if (rc == QH_OK) {
-    h->fusion = src->fusion;
-    memcpy(h->perm, src->perm, sizeof h->perm);
-    e = hipMemcpyAsync(h->d_psi, src->d_psi, bytes, hipMemcpyDefault, src->stream);
-    if (e != hipSuccess) rc = fail(QH_ERR_HIP, "clone: hipMemcpyAsync: %s", hipGetErrorString(e));
-    else rc = wait_stream(src, src->stream, "qh_clone");
-  }
-  if (rc) {
-    const std::string why = g_err;
-    qh_destroy(h);
-    g_err = why;
-    return rc;
-  }
+  qh_state_s *h = nullptr;
+  if ((rc = make_sibling(src, src->nloc, src->nglob, "clone", &h))) return rc;
+  memcpy(h->perm, src->perm, sizeof h->perm);
+  const hipError_t e = hipMemcpyAsync(h->d_psi, src->d_psi, (size_t)src->amp_bytes() << src->nloc, hipMemcpyDefault, src->stream);
+  if (e != hipSuccess) rc = fail(QH_ERR_HIP, "clone: hipMemcpyAsync: %s", hipGetErrorString(e));
+  else rc = wait_stream(src, src->stream, "qh_clone");
+  if (rc) return drop_sibling(h, rc);
   *out = h;
   return QH_OK;
 }
@@ -2050,6 +2067,142 @@ int qh_inner(qh_handle a, qh_handle b, double out[2]) {
   out[1] = vals[1];
   a->stats.kernels_launched += 1;      // one read of the two states (the fold is not counted, as in qh_expect_pauli)
   a->stats.bytes_swept += 2 * ((1ull << a->nloc) * a->amp_bytes());
+  return QH_OK;
+}
+
+}  // extern "C"
+
+// ---- growing and shrinking a state: qh_extend, qh_release (kernels_resize.hip.h, resize_plan.h) ----------------------------
+namespace {
+
+// the checks both calls share, before anything runs
+int check_resize(const qh_state_s *src, const void *out, const char *who, int k, int nloc_new) {
+  if (!src || !out) return fail(QH_ERR_ARG, "%s: null handle or out", who);
+  if (k < 1 || k > qh::kMaxResizeBits) return fail(QH_ERR_ARG, "%s: k = %d outside [1,%d]", who, k, qh::kMaxResizeBits);
+  if (nloc_new < 1 || nloc_new > 40) return fail(QH_ERR_ARG, "%s: %d local qubits would become %d, outside [1,40]", who, src->nloc, nloc_new);
+  if (src->nglob + (nloc_new - src->nloc) > qh::kResizeMaxGlobalBits)
+    return fail(QH_ERR_ARG, "%s: %d global qubits would become more than %d", who, src->nglob, qh::kResizeMaxGlobalBits);
+  return QH_OK;
+}
+
+// one kernel has read src once and written the new state once
+void count_resize(qh_state_s *src, const qh_state_s *h) {
+  const uint64_t amps = (1ull << src->nloc) + (1ull << h->nloc);      // (both terms are even: every handle has a local bit)
+  count_kernel(src, amps / 2, amps / 2);
+}
+
+}  // namespace
+
+extern "C" {
+
+int qh_extend(qh_handle src, int k, const double *amps, uint64_t basis, qh_handle *out) {
+  int rc = check_resize(src, out, "extend", k, src ? src->nloc + k : 0);
+  if (rc) return rc;
+  if (!amps && basis >= (1ull << k)) return fail(QH_ERR_ARG, "extend: basis state %llu of %d qubits", (unsigned long long)basis, k);
+  if ((rc = flush_impl(src))) return rc;          // (planner-only handles too: the bit map is the one the queue leaves)
+  qh_state_s *h = nullptr;
+  if ((rc = make_sibling(src, src->nloc + k, src->nglob + k, "extend", &h))) return rc;
+  qh::plan_extend(src->nloc, src->nglob, src->perm, k, h->perm);
+  if (src->dry) {
+    *out = h;
+    return QH_OK;
+  }
+  TabPlan t;                                      // the whole table, in order, through the staged upload of the table gates
+  t.kl = k;
+  t.tbits = (1u << k) - 1u;
+  std::vector<double> unit;
+  if (!amps) {
+    unit.assign((size_t)2 << k, 0.0);
+    unit[2 * basis] = 1.0;
+    amps = unit.data();
+  }
+  const void *dtab = nullptr;
+  if ((rc = stage_table(src, t, 1, amps, &dtab))) return drop_sibling(h, rc);
+  with_real(src, [&](auto x) {
+    using R = decltype(x);
+    using A = typename qh::AmpT<R>::type;
+    qh::ExtendArgs a{};
+    a.ib = src->nloc - qh::InnerItem<R>::kAmpBits;
+    a.cw = std::min(qh::kResizeChunkBits, a.ib);
+    a.nj = 1u << k;
+    a.nchunks = 1ull << (a.ib - a.cw);
+    const uint32_t gx = (uint32_t)std::min<uint64_t>(a.nchunks, qh::kResizeBlocks);
+    // the slabs one trip of a block covers (more than one where src is smaller than a chunk), shared out over enough block
+    // rows to fill the machine
+    const uint32_t jstep = 1u << (qh::kResizeChunkBits - a.cw), units = (a.nj + jstep - 1) / jstep;
+    uint32_t gy = std::min(units, std::max(1u, qh::kResizeBlocks / gx));
+    a.jper = (units + gy - 1) / gy * jstep;
+    gy = (a.nj + a.jper - 1) / a.jper;
+    hipLaunchKernelGGL(qh::k_extend<R>, dim3(gx, gy), dim3(256), 0, src->stream, (const A *)src->d_psi, (A *)h->d_psi, (const A *)dtab, a);
+  });
+  rc = check_launch(src);
+  if (rc == QH_OK && src->tab.commit(src->stream, 0) != hipSuccess) rc = fail(QH_ERR_HIP, "extend: hipEventRecord failed");
+  if (rc == QH_OK) rc = wait_stream(src, src->stream, "qh_extend");
+  if (rc) return drop_sibling(h, rc);
+  count_resize(src, h);
+  *out = h;
+  return QH_OK;
+}
+
+int qh_release(qh_handle src, int k, const int32_t *bits, uint64_t value, double weight[2], qh_handle *out) {
+  int rc = check_resize(src, out, "release", k, src ? src->nloc - k : 0);
+  if (rc) return rc;
+  if (!bits) return fail(QH_ERR_ARG, "release: null bit list");
+  if (value >= (1ull << k)) return fail(QH_ERR_ARG, "release: value %llu of %d bits", (unsigned long long)value, k);
+  uint64_t seen = 0;
+  if ((rc = check_bit_list(src, "release", k, bits, &seen))) return rc;
+  // (a logical bit stays local or in the shard index whatever the relayout sweeps do)
+  for (int j = 0; j < k; ++j)
+    if (place_bit(src, bits[j]).held)
+      return fail(QH_ERR_NONLOCAL, "release: bit %d is held by the shard index (physical bit %d, local bits: %d); exchange first", bits[j],
+                  src->perm[bits[j]], src->nloc);
+  if ((rc = flush_impl(src))) return rc;
+  qh::ReleasePlan pl;
+  qh::plan_release(src->nloc, src->nglob, src->perm, k, bits, value, &pl);
+  qh_state_s *h = nullptr;
+  if ((rc = make_sibling(src, src->nloc - k, src->nglob - k, "release", &h))) return rc;
+  memcpy(h->perm, pl.perm, sizeof h->perm);
+  if (src->dry) {
+    *out = h;
+    return QH_OK;
+  }
+  qh::ReleaseArgs a{};
+  a.drop = pl.drop;
+  a.want = pl.want;
+  a.nseg = pl.nseg;
+  for (int s = 0; s < pl.nseg; ++s) {
+    a.mask[s] = pl.mask[s];
+    a.shift[s] = pl.shift[s];
+  }
+  const int ib = src->nloc - (src->bw == 128 ? 0 : 1);      // log2 of the 16-byte items of src
+  a.cw = std::min(qh::kResizeChunkBits, ib);
+  a.nchunks = 1ull << (ib - a.cw);
+  const uint32_t nblk = (uint32_t)std::min<uint64_t>(a.nchunks, qh::kResizeBlocks);
+  qh::ScratchLayout lay;
+  const size_t slab_off = lay.add((size_t)nblk * 2 * sizeof(double)), out_off = lay.add(2 * sizeof(double));
+  if (src->meas.reserve(lay.total) != hipSuccess) return drop_sibling(h, fail(QH_ERR_NOMEM, "release: no room for %zu bytes of scratch", lay.total));
+  double *slab = (double *)(src->meas.as<char>() + slab_off), *dout = (double *)(src->meas.as<char>() + out_off);
+  with_real(src, [&](auto x) {
+    using R = decltype(x);
+    using A = typename qh::AmpT<R>::type;
+    const A *from = (const A *)src->d_psi;
+    A *to = (A *)h->d_psi;
+    if (qh::InnerItem<R>::kAmpBits && (pl.drop & 1ull))      // a complex64 item loses one of its halves
+      hipLaunchKernelGGL((qh::k_release<R, true>), dim3(nblk), dim3(256), 0, src->stream, from, to, a, slab);
+    else
+      hipLaunchKernelGGL((qh::k_release<R, false>), dim3(nblk), dim3(256), 0, src->stream, from, to, a, slab);
+  });
+  hipLaunchKernelGGL(qh::k_expect_fold, dim3(2), dim3(256), 0, src->stream, (const double *)slab, nblk, 2, 1.0, dout);
+  double vals[2];
+  rc = check_launch(src);
+  if (rc == QH_OK) rc = read_back(src, vals, dout, sizeof vals, "qh_release");
+  if (rc) return drop_sibling(h, rc);
+  if (weight) {
+    weight[0] = vals[0];
+    weight[1] = vals[1];
+  }
+  count_resize(src, h);
+  *out = h;
   return QH_OK;
 }
 

@@ -379,6 +379,45 @@ class DeviceState:
     other.h, other.nbits_global = h, self.nbits_global
     return other
 
+  def _sibling(self, call, nbits_delta):
+    """Wraps the handle a qh_extend / qh_release call makes (call(out) -> status), the way clone() wraps its own; on
+    QH_ERR_NOMEM the parked device states are dropped and the call is tried once more, as in __init__."""
+    h = ctypes.c_void_p()
+    rc = call(ctypes.byref(h))
+    if rc == native.QH_ERR_NOMEM:
+      from qcc_amd.lib import backend  # pylint: disable=import-outside-toplevel
+      backend.drop_device_pool()
+      rc = call(ctypes.byref(h))
+    native.check(rc)
+    other = object.__new__(DeviceState)
+    other.lib, other.bit_width, other.dtype, other.h = self.lib, self.bit_width, self.dtype, h
+    other.nbits, other.nbits_global = self.nbits + nbits_delta, self.nbits_global + nbits_delta
+    return other
+
+  def extend(self, nqubits, amps=None, basis=0):
+    """A new DeviceState holding self (x) f (np.kron order: the nqubits new qubits are the least significant logical bits),
+    built on the device (qh_extend); f = amps (2^nqubits amplitudes) or, where amps is None, the basis state |basis>.
+    1 <= nqubits <= 16.  This state is left as clone() leaves it."""
+    k = int(nqubits)
+    tab = None
+    if amps is not None:
+      tab = np.ascontiguousarray(amps, dtype=np.complex128).reshape(-1)
+      if not 1 <= k <= 16 or tab.size != 1 << k:
+        raise ValueError(f'extend: {tab.size} amplitudes for {k} qubits')
+    ptr = tab.ctypes.data_as(_dp) if tab is not None else None
+    return self._sibling(lambda out: self.lib.qh_extend(self.h, k, ptr, int(basis), out), k)
+
+  def release(self, bits, value=0):
+    """(new DeviceState, kept, dropped): the slice of this state where LOGICAL bit bits[j] equals bit j of value, as a state
+    of len(bits) fewer qubits (qh_release: the remaining bits keep their order and are renumbered from 0), with the sums of
+    |a|^2 of the amplitudes kept and dropped (per shard, not normalised).  Nothing is rescaled.  This state is left as
+    clone() leaves it."""
+    b = np.ascontiguousarray([int(x) for x in bits], dtype=np.int32)
+    w = (ctypes.c_double * 2)()
+    bp = b.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    new = self._sibling(lambda out: self.lib.qh_release(self.h, int(b.size), bp, int(value), w, out), -int(b.size))
+    return new, float(w[0]), float(w[1])
+
   def copy_from(self, other):
     """This state := other's, amplitudes and bit map (qh_copy); what this state has queued is dropped."""
     native.check(self.lib.qh_copy(self.h, other.h))

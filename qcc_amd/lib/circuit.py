@@ -77,6 +77,7 @@ def _u1_operator(value):
 _DENSE_MAX_BITS = 6        # qh_apply_matrix: dense operators on up to 6 qubits run on the device
 _TABLE_MAX_BITS = 16       # qh_apply_mux / qh_apply_diag: tables over up to 16 qubits
 _MARGINAL_MAX_BITS = 16    # qh_marginal: registers of up to 16 qubits (2^16 probabilities)
+_EXTEND_MAX_BITS = 16      # qh_extend / qh_release: up to 16 qubits added or given back per call
 
 
 def _dense_bits(op):
@@ -382,6 +383,22 @@ class qc:
         if self._is_product:
             idx = getattr(new_state, 'basis_index', None)
             self._append_factor(nqubits, idx if idx is not None else np.array(tensor.host_current(new_state), dtype=np.complex128))
+            return
+        dev = self._dev
+        if (self._dev_ok and dev is not None and not self._alias and hasattr(dev, 'extend') and 1 <= nqubits <= _EXTEND_MAX_BITS
+                and dev.nbits == self._nbits and dev.bit_width == self._width()):
+            # a live state in HBM: the product is built there (qh_extend), in a buffer of its own; the old one goes back
+            idx = getattr(new_state, 'basis_index', None)
+            if idx is not None:
+                grown = dev.extend(nqubits, basis=int(idx))
+            else:
+                grown = dev.extend(nqubits, amps=np.array(tensor.host_current(new_state), dtype=np.complex128).reshape(-1))
+            self._dev = grown
+            backend.release_device_state(dev)
+            self._nbits += nqubits
+            self.global_reg += nqubits
+            self._host, self._host_ok = None, False
+            self._factors = []
             return
         cur = self.psi if self._nbits else state.State(1.0)
         self.psi = cur * new_state
@@ -840,6 +857,58 @@ class qc:
             dev.scale(1.0 / math.sqrt(prob))
             self._gate_done()
         return value, prob
+
+    def release(self, qubits, value=0, *, tol=1e-9, normalize=False):
+        """Give the qubits `qubits` back: the state becomes its slice at register value `value` (an int in register order,
+        qubits[0] most significant, as measure() returns it -- `v, _ = qc.measure(qs); qc.release(qs, v)` -- or a sequence of
+        bits), a state of len(qubits) fewer qubits, on the device (qh_release).  Returns (kept, dropped): the sums of |a|^2
+        of the amplitudes kept and dropped.  The remaining qubits keep their order and are renumbered from 0: Reg objects
+        handed out earlier are stale.  If tol is not None and dropped > tol * (kept + dropped) -- the qubits were not in
+        |value> -- ValueError is raised and the state is as before; tol=None is post-selection.  normalize=True scales the
+        result by 1/sqrt(kept).  Not recorded in the IR, like measure.  With a device that cannot release (and in aliased
+        mode) the same result comes from qc.psi on the host."""
+        qubits = self._register(qubits, 'release')
+        n, k = self._nbits, len(qubits)
+        if k < 1 or k >= n:
+            raise ValueError(f'release: {k} of {n} qubits (at least one is released, at least one remains)')
+        if not isinstance(value, (int, np.integer)):
+            bits = [int(b) for b in value]
+            if len(bits) != k or any(b not in (0, 1) for b in bits):
+                raise ValueError(f'release: value {value!r} is not {k} bits')
+            value = helper.bits2val(bits)
+        value = int(value)
+        if value < 0 or value >> k:
+            raise ValueError(f'release: value {value} of {k} qubits')
+        dev = self._ensure_device()
+        on_device = hasattr(dev, 'release') and k <= _EXTEND_MAX_BITS and not self._alias
+        if on_device:
+            small, kept, dropped = dev.release([n - 1 - q for q in reversed(qubits)], value)
+        else:
+            amps = np.asarray(self.psi).reshape(-1)
+            keep = self._register_values(np.arange(amps.size, dtype=np.uint64), qubits) == np.uint64(value)
+            w = np.abs(amps.astype(np.complex128)) ** 2
+            kept, dropped = float(w[keep].sum()), float(w[~keep].sum())
+        if tol is not None and dropped > tol * (kept + dropped):
+            if on_device:
+                small.close()
+            raise ValueError(f'release: qubits {qubits} are not in |{value}>: weight {dropped:.3e} of {kept + dropped:.3e} would be dropped')
+        if normalize and not kept > 0:
+            if on_device:
+                small.close()
+            raise ValueError('release: nothing is kept, nothing to normalise')
+        if on_device:
+            self._dev = small
+            backend.release_device_state(dev)
+            self._nbits = n - k
+            self._host, self._host_ok = None, False
+            self._factors = []
+            self._product_flag = False
+            if normalize:
+                small.scale(1.0 / math.sqrt(kept))
+        else:
+            self.psi = amps[keep] / math.sqrt(kept) if normalize else amps[keep]
+        self.global_reg -= k
+        return kept, dropped
 
     def _pauli_masks(self, paulis):
         """(x, z) masks over LOGICAL bits of one Pauli string: a str over IXYZ of length nbits (character q = qubit q)
