@@ -341,6 +341,26 @@ typedef struct {
   uint8_t pos_b[64];           /* b's position of the logical bit a keeps at position p       */
 } qh_inner_tiles;
 int qh_inner_plan(qh_handle a, qh_handle b, qh_inner_tiles *out);
+/* dst := alpha*dst + beta*src, amplitude by amplitude, matched by LOGICAL index.  alpha, beta: (re, im).  Written in place
+ * into dst's current buffer in dst's current layout: bit map, relayout mode, second buffer and device pointer of dst are as
+ * before (attached and host-mapped handles too); src is read only.  What both handles have queued runs first (dst's queue is
+ * flushed, not dropped; dst's exchange arrivals are waited for); dst's stream waits for src's flushed work (an event), the
+ * kernel runs on dst's stream and the host waits for it: on return either handle may be used at once.
+ * The two states are walked as qh_inner_plan(dst, src) says: equal layouts as linear streams of 16 bytes per lane, different
+ * ones tile by tile with src's values crossing through LDS, fewer than 8 local bits as a gather.
+ * Each component of a new amplitude is formed in double from the stored amplitudes and rounded once to the handle's width;
+ * a coefficient component that is exactly 0 contributes 0 whatever the amplitude holds, so coefficients made of 0, 1 and -1
+ * give d + s, d - s, s ... equal as numbers to the sums formed at the handle's width (the sign of a zero may differ).
+ * alpha == 0 exactly: dst's old values are not read (NaN or Inf in them does not propagate; two streams).  beta == 0 exactly:
+ * src is not read, whatever its layout.  Both 0: one stream of zeros.  alpha == 1 and beta == 0: no kernel.
+ * norm2 (may be NULL): sum |a|^2 of dst's NEW amplitudes as stored, over this shard, in double, in a fixed order without
+ * atomics: the same states, layouts and coefficients give the same bits.  Without a kernel it is qh_inner(dst, dst)'s sum.
+ * dst's qh_stats: kernels_launched + 1 (+ 0 without a kernel), bytes_swept and bytes_algorithmic + (streams touched: the
+ * write, dst's read unless alpha == 0, src's read unless beta == 0) x the bytes of the state.  src's stats are unchanged.
+ * Errors, nothing runs and nothing changes: QH_ERR_ARG (null handle or coefficient pointer, dry handle, dst == src -- use
+ * qh_scale --, another device, different nbits (local or global) or width); QH_ERR_NONLOCAL as qh_inner (another shard index,
+ * or a logical bit one handle keeps in the shard index and the other elsewhere; exchange first).                          */
+int qh_axpby(qh_handle dst, const double alpha[2], qh_handle src, const double beta[2], double *norm2);
 
 /* ---- growing and shrinking a state (kernels_resize.hip.h) ----------------- */
 /* Both calls make a NEW handle and leave src as qh_clone leaves it: what src has queued runs first (exchange arrivals are

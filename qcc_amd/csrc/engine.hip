@@ -28,6 +28,7 @@
 #include "kernels_measure.hip.h"
 #include "kernels_expect.hip.h"
 #include "kernels_inner.hip.h"
+#include "kernels_axpby.hip.h"
 #include "kernels_resize.hip.h"
 #include "planner.h"
 #include "kernels_sweep.hip.h"
@@ -727,7 +728,7 @@ int select_device(int device) {
 extern "C" {
 
 const char *qh_last_error(void) { return g_err.c_str(); }
-int qh_version(void) { return 111; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
+int qh_version(void) { return 112; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
 
 int qh_device_count(int *count) {
   if (!count) return fail(QH_ERR_ARG, "null");
@@ -1892,7 +1893,7 @@ int qh_project_bits(qh_handle h, uint64_t mask, uint64_t value) {
 
 }  // extern "C"
 
-// ---- two states: qh_clone, qh_copy, qh_inner (kernels_inner.hip.h) ---------------------------------------------------
+// ---- two states: qh_clone, qh_copy, qh_inner, qh_axpby (kernels_inner.hip.h, kernels_axpby.hip.h) ---------------------
 namespace {
 
 constexpr uint64_t kInnerBlocks = 4096;     // blocks at most (one slab row of (re, im) each)
@@ -1964,6 +1965,74 @@ int make_sibling(const qh_state_s *src, int nloc, int nglob, const char *who, qh
   return QH_OK;
 }
 
+// The launch geometry the two-state kernels share (k_inner_*, k_axpby_*).  Linear walk over 2^items 16-byte items: chunks of
+// 256 threads x kInnerLoads items, a whole number of chunks per block.
+struct LinearGeom { int cw; uint32_t cpb; uint64_t nblk; };
+LinearGeom linear_geom(int items) {
+  const int cw = std::min(8 + 3, items);
+  const uint64_t nchunks = 1ull << (items - cw), nblk = std::min(nchunks, kInnerBlocks);
+  return {cw, (uint32_t)(nchunks / nblk), nblk};
+}
+qh::InnerTileArgs tile_args(const qh_inner_tiles &pl, uint64_t *nblk) {
+  qh::InnerTileArgs t{};
+  memcpy(t.tile_a, pl.tile_a, 8);
+  memcpy(t.tile_b, pl.tile_b, 8);
+  memcpy(t.shuffle, pl.shuffle, 8);
+  memcpy(t.rest_a, pl.rest_a, sizeof t.rest_a);
+  memcpy(t.rest_b, pl.rest_b, sizeof t.rest_b);
+  t.nrest = (int)pl.nrest;
+  t.cbits = std::min(qh::kInnerChunkBits, t.nrest);
+  const uint64_t nchunks = 1ull << (t.nrest - t.cbits);
+  *nblk = std::min(nchunks, kInnerBlocks);
+  t.cpb = (uint32_t)(nchunks / *nblk);
+  return t;
+}
+qh::InnerGatherArgs gather_args(int nloc, const qh_inner_tiles &pl) {
+  qh::InnerGatherArgs g{};
+  g.nloc = nloc;
+  memcpy(g.pos_b, pl.pos_b, sizeof g.pos_b);
+  return g;
+}
+
+// b's stream has been given work that a's stream is about to read (or must not overtake): an event between them
+int order_after(qh_state_s *a, qh_state_s *b) {
+  if (!b->ev_read) HIP_TRY(hipEventCreateWithFlags(&b->ev_read, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(b->ev_read, b->stream));
+  HIP_TRY(hipStreamWaitEvent(a->stream, b->ev_read, 0));
+  return QH_OK;
+}
+
+// <a|b> into vals, on a's stream, behind what b's stream has been given; both flushed, pl = their plan.  The host waits.
+// No stats: the callers count.
+int run_inner(qh_state_s *a, qh_state_s *b, const qh_inner_tiles &pl, double vals[2]) {
+  int rc;
+  qh::ScratchLayout lay;
+  const size_t slab_off = lay.add((size_t)kInnerBlocks * 2 * sizeof(double)), out_off = lay.add(2 * sizeof(double));
+  HIP_TRY(a->meas.reserve(lay.total));
+  double *slab = (double *)(a->meas.as<char>() + slab_off), *dout = (double *)(a->meas.as<char>() + out_off);
+  if (b != a && (rc = order_after(a, b))) return rc;      // a's stream reads b: behind everything b's stream has been given
+  uint64_t nblk = 1;
+  with_real(a, [&](auto x) {
+    using R = decltype(x);
+    using A = typename qh::AmpT<R>::type;
+    const A *pa = (const A *)a->d_psi, *pb = (const A *)b->d_psi;
+    if (pl.path == QH_INNER_LINEAR) {
+      const LinearGeom g = linear_geom(a->nloc - qh::InnerItem<R>::kAmpBits);
+      nblk = g.nblk;
+      hipLaunchKernelGGL(qh::k_inner_linear<R>, dim3((unsigned)nblk), dim3(256), 0, a->stream, pa, pb, g.cw, g.cpb, slab);
+    } else if (pl.path == QH_INNER_TILES) {
+      const qh::InnerTileArgs t = tile_args(pl, &nblk);
+      hipLaunchKernelGGL(qh::k_inner_tiles<R>, dim3((unsigned)nblk), dim3(256), 0, a->stream, pa, pb, t, slab);
+    } else {
+      const qh::InnerGatherArgs g = gather_args(a->nloc, pl);
+      hipLaunchKernelGGL(qh::k_inner_gather<R>, dim3(1), dim3(256), 0, a->stream, pa, pb, g, slab);
+    }
+  });
+  hipLaunchKernelGGL(qh::k_expect_fold, dim3(2), dim3(256), 0, a->stream, (const double *)slab, (uint32_t)nblk, 2, 1.0, dout);
+  if ((rc = check_launch(a))) return rc;
+  return read_back(a, vals, dout, 2 * sizeof(double), "qh_inner");
+}
+
 }  // namespace
 
 extern "C" {
@@ -2019,54 +2088,80 @@ int qh_inner(qh_handle a, qh_handle b, double out[2]) {
   if (b != a && (rc = enter(b))) return rc;
   qh_inner_tiles pl;
   if ((rc = plan_pair(a, b, "inner", &pl))) return rc;
-  qh::ScratchLayout lay;
-  const size_t slab_off = lay.add((size_t)kInnerBlocks * 2 * sizeof(double)), out_off = lay.add(2 * sizeof(double));
-  HIP_TRY(a->meas.reserve(lay.total));
-  double *slab = (double *)(a->meas.as<char>() + slab_off), *dout = (double *)(a->meas.as<char>() + out_off);
-  if (b != a) {      // a's stream reads b: behind everything b's stream has been given
-    if (!b->ev_read) HIP_TRY(hipEventCreateWithFlags(&b->ev_read, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(b->ev_read, b->stream));
-    HIP_TRY(hipStreamWaitEvent(a->stream, b->ev_read, 0));
-  }
-  uint64_t nblk = 1;
-  with_real(a, [&](auto x) {
-    using R = decltype(x);
-    using A = typename qh::AmpT<R>::type;
-    const A *pa = (const A *)a->d_psi, *pb = (const A *)b->d_psi;
-    if (pl.path == QH_INNER_LINEAR) {
-      const int items = a->nloc - qh::InnerItem<R>::kAmpBits;      // log2 of the 16-byte items of a state
-      const int cw = std::min(8 + 3, items);        // 256 threads x kInnerLoads
-      const uint64_t nchunks = 1ull << (items - cw);
-      nblk = std::min(nchunks, kInnerBlocks);
-      hipLaunchKernelGGL(qh::k_inner_linear<R>, dim3((unsigned)nblk), dim3(256), 0, a->stream, pa, pb, cw, (uint32_t)(nchunks / nblk), slab);
-    } else if (pl.path == QH_INNER_TILES) {
-      qh::InnerTileArgs t{};
-      memcpy(t.tile_a, pl.tile_a, 8);
-      memcpy(t.tile_b, pl.tile_b, 8);
-      memcpy(t.shuffle, pl.shuffle, 8);
-      memcpy(t.rest_a, pl.rest_a, sizeof t.rest_a);
-      memcpy(t.rest_b, pl.rest_b, sizeof t.rest_b);
-      t.nrest = (int)pl.nrest;
-      t.cbits = std::min(qh::kInnerChunkBits, t.nrest);
-      const uint64_t nchunks = 1ull << (t.nrest - t.cbits);
-      nblk = std::min(nchunks, kInnerBlocks);
-      t.cpb = (uint32_t)(nchunks / nblk);
-      hipLaunchKernelGGL(qh::k_inner_tiles<R>, dim3((unsigned)nblk), dim3(256), 0, a->stream, pa, pb, t, slab);
-    } else {
-      qh::InnerGatherArgs g{};
-      g.nloc = a->nloc;
-      memcpy(g.pos_b, pl.pos_b, sizeof g.pos_b);
-      hipLaunchKernelGGL(qh::k_inner_gather<R>, dim3(1), dim3(256), 0, a->stream, pa, pb, g, slab);
-    }
-  });
-  hipLaunchKernelGGL(qh::k_expect_fold, dim3(2), dim3(256), 0, a->stream, (const double *)slab, (uint32_t)nblk, 2, 1.0, dout);
-  if ((rc = check_launch(a))) return rc;
   double vals[2];
-  if ((rc = read_back(a, vals, dout, sizeof vals, "qh_inner"))) return rc;
+  if ((rc = run_inner(a, b, pl, vals))) return rc;
   out[0] = vals[0];
   out[1] = vals[1];
   a->stats.kernels_launched += 1;      // one read of the two states (the fold is not counted, as in qh_expect_pauli)
   a->stats.bytes_swept += 2 * ((1ull << a->nloc) * a->amp_bytes());
+  return QH_OK;
+}
+
+int qh_axpby(qh_handle dst, const double alpha[2], qh_handle src, const double beta[2], double *norm2) {
+  int rc = check_pair(dst, src, "axpby");
+  if (rc) return rc;
+  if (!alpha || !beta) return fail(QH_ERR_ARG, "axpby: null coefficient");
+  if (dst == src) return fail(QH_ERR_ARG, "axpby: dst == src (use qh_scale)");
+  qh_inner_tiles pl;
+  // which bits the shard index holds is not something a flush changes: refused before anything runs
+  if ((rc = plan_pair(dst, src, "axpby", &pl))) return rc;
+  if ((rc = enter(dst))) return rc;      // (queued gates run, exchange arrivals are waited for on dst's stream)
+  if ((rc = enter(src))) return rc;
+  if ((rc = plan_pair(dst, src, "axpby", &pl))) return rc;      // the layouts the flushes left
+  const bool rd = alpha[0] != 0.0 || alpha[1] != 0.0, rs = beta[0] != 0.0 || beta[1] != 0.0;
+  if (!rs && alpha[0] == 1.0 && alpha[1] == 0.0) {      // dst as it is: no kernel; the norm from the readers' fixed-order sum
+    if (!norm2) return QH_OK;
+    double vals[2];
+    if ((rc = plan_pair(dst, dst, "axpby", &pl)) || (rc = run_inner(dst, dst, pl, vals))) return rc;
+    *norm2 = vals[0];
+    return QH_OK;
+  }
+  double *slab = nullptr, *dout = nullptr;
+  if (norm2) {
+    qh::ScratchLayout lay;
+    const size_t slab_off = lay.add((size_t)kInnerBlocks * 2 * sizeof(double)), out_off = lay.add(2 * sizeof(double));
+    HIP_TRY(dst->meas.reserve(lay.total));
+    slab = (double *)(dst->meas.as<char>() + slab_off);
+    dout = (double *)(dst->meas.as<char>() + out_off);
+  }
+  if (rs && (rc = order_after(dst, src))) return rc;      // dst's stream reads src: behind everything src's stream has been given
+  const qh::AxpbyCoef c{alpha[0], alpha[1], beta[0], beta[1], norm2 ? 1 : 0};
+  uint64_t nblk = 1;
+  with_real(dst, [&](auto x) {
+    using R = decltype(x);
+    using A = typename qh::AmpT<R>::type;
+    A *pd = (A *)dst->d_psi;
+    const A *ps = (const A *)src->d_psi;
+    const dim3 thr(256);
+    if (!rs || pl.path == QH_INNER_LINEAR) {      // (src not read: the layouts do not matter)
+      const LinearGeom g = linear_geom(dst->nloc - qh::InnerItem<R>::kAmpBits);
+      nblk = g.nblk;
+      const dim3 grid((unsigned)nblk);
+      if (rd && rs) hipLaunchKernelGGL((qh::k_axpby_linear<R, true, true>), grid, thr, 0, dst->stream, pd, ps, c, g.cw, g.cpb, slab);
+      else if (rs) hipLaunchKernelGGL((qh::k_axpby_linear<R, false, true>), grid, thr, 0, dst->stream, pd, ps, c, g.cw, g.cpb, slab);
+      else if (rd) hipLaunchKernelGGL((qh::k_axpby_linear<R, true, false>), grid, thr, 0, dst->stream, pd, ps, c, g.cw, g.cpb, slab);
+      else hipLaunchKernelGGL((qh::k_axpby_linear<R, false, false>), grid, thr, 0, dst->stream, pd, ps, c, g.cw, g.cpb, slab);
+    } else if (pl.path == QH_INNER_TILES) {
+      const qh::InnerTileArgs t = tile_args(pl, &nblk);
+      const dim3 grid((unsigned)nblk);
+      if (rd) hipLaunchKernelGGL((qh::k_axpby_tiles<R, true>), grid, thr, 0, dst->stream, pd, ps, c, t, slab);
+      else hipLaunchKernelGGL((qh::k_axpby_tiles<R, false>), grid, thr, 0, dst->stream, pd, ps, c, t, slab);
+    } else {
+      const qh::InnerGatherArgs g = gather_args(dst->nloc, pl);
+      if (rd) hipLaunchKernelGGL((qh::k_axpby_gather<R, true>), dim3(1), thr, 0, dst->stream, pd, ps, c, g, slab);
+      else hipLaunchKernelGGL((qh::k_axpby_gather<R, false>), dim3(1), thr, 0, dst->stream, pd, ps, c, g, slab);
+    }
+  });
+  if (norm2) hipLaunchKernelGGL(qh::k_expect_fold, dim3(1), dim3(256), 0, dst->stream, (const double *)slab, (uint32_t)nblk, 2, 1.0, dout);
+  if ((rc = check_launch(dst))) return rc;
+  // the host waits: on return src may be changed and dst read at once
+  if (norm2) rc = read_back(dst, norm2, dout, sizeof(double), "qh_axpby");
+  else rc = wait_stream(dst, dst->stream, "qh_axpby");
+  if (rc) return rc;
+  const uint64_t streams = 1 + (rd ? 1 : 0) + (rs ? 1 : 0), bytes = streams * ((1ull << dst->nloc) * dst->amp_bytes());
+  dst->stats.kernels_launched += 1;      // (the fold is not counted, as in qh_inner)
+  dst->stats.bytes_swept += bytes;
+  dst->stats.bytes_algorithmic += bytes;
   return QH_OK;
 }
 

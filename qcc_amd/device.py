@@ -429,6 +429,16 @@ class DeviceState:
     native.check(self.lib.qh_inner(self.h, other.h, out))
     return complex(out[0], out[1])
 
+  def axpby(self, alpha, other, beta, norm=False):
+    """self := alpha * self + beta * other by LOGICAL index, in place, in this state's layout (qh_axpby: both states are
+    read where they lie; other is read only).  norm=True returns sum |a|^2 of the new amplitudes over this shard (a float,
+    summed in a fixed order on the device), otherwise None."""
+    a, b = complex(alpha), complex(beta)
+    out = ctypes.c_double() if norm else None
+    native.check(self.lib.qh_axpby(self.h, (ctypes.c_double * 2)(a.real, a.imag), other.h, (ctypes.c_double * 2)(b.real, b.imag),
+                                   ctypes.byref(out) if norm else None))
+    return out.value if norm else None
+
   def inner_plan(self, other):
     """How inner(other) would walk the two states right now (qh_inner_plan), as a dict."""
     t = native.QhInnerTiles()

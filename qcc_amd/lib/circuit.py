@@ -1038,6 +1038,59 @@ class qc:
             nb = float(np.vdot(self._host_amps(other), self._host_amps(other)).real)
         return float(abs(ov) ** 2 / (na * nb))
 
+    def combine(self, other, alpha=1.0, beta=1.0, *, normalize=False):
+        """self := alpha * self + beta * other for another circuit or a Snapshot of the same size and width, on the device
+        (qh_axpby: in place, both states read where they lie; other is unchanged).  Gates queued on either side run first.
+        Returns the norm^2 of the result, before any normalisation; normalize=True follows with scale(1 / sqrt(norm^2)) and
+        raises ValueError where the result is 0 (the state is then that result).  Not recorded in the IR, like restore."""
+        self._same_shape(other, 'combine')
+        if other is self:
+            raise ValueError('combine: other is this circuit (scale it instead)')
+        alpha, beta = complex(alpha), complex(beta)
+        dev = self._ensure_device()
+        odev = other._ensure_device() if isinstance(other, qc) else other._dev      # pylint: disable=protected-access
+        if hasattr(dev, 'axpby') and odev is not None and hasattr(odev, 'axpby'):
+            norm2 = float(dev.axpby(alpha, odev, beta, norm=True))
+            # neither the product description nor a host copy describes the state any more (as restore)
+            self._product_flag = False
+            self._host_ok = False
+            if self._aliased():
+                self._dev.sync()
+            if normalize:
+                if not norm2 > 0:
+                    raise ValueError('combine: the result is 0, nothing to normalise')
+                dev.scale(1.0 / math.sqrt(norm2))
+                self._gate_done()
+            return norm2
+        amps = np.asarray(self.psi).reshape(-1)
+        new = (alpha * amps.astype(np.complex128) + beta * np.asarray(self._host_amps(other)).reshape(-1).astype(np.complex128)).astype(amps.dtype)
+        norm2 = float(np.vdot(new.astype(np.complex128), new.astype(np.complex128)).real)      # of the values as stored, in double
+        if normalize and not norm2 > 0:
+            self.psi = new
+            raise ValueError('combine: the result is 0, nothing to normalise')
+        self.psi = new / math.sqrt(norm2) if normalize else new
+        return norm2
+
+    def project_out(self, other):
+        """Remove other's component from this state (one Gram-Schmidt step): c = <other|self> / <other|other>,
+        self -= c * other; returns c.  ValueError where <other|other> is 0."""
+        self._same_shape(other, 'project_out')
+        if other is self:
+            raise ValueError('project_out: other is this circuit')
+        if isinstance(other, qc):
+            ov, nn = other.overlap(self), other.overlap(other).real
+        else:
+            ov = complex(np.conj(self.overlap(other)))
+            if other._dev is not None and hasattr(other._dev, 'inner'):      # pylint: disable=protected-access
+                nn = other._dev.inner(other._dev).real                          # pylint: disable=protected-access
+            else:
+                nn = float(np.vdot(self._host_amps(other), self._host_amps(other)).real)
+        if not nn > 0:
+            raise ValueError('project_out: <other|other> is 0')
+        c = ov / nn
+        self.combine(other, 1.0, -c)
+        return c
+
     def pauli_expectation(self, idx):
         p0, _ = self.measure_bit(idx, 0, False)
         return p0 - (1 - p0)
