@@ -295,6 +295,41 @@ int qh_project_bits(qh_handle h, uint64_t mask, uint64_t value);
  * held by the shard index is QH_ERR_NONLOCAL (nothing computed, out untouched).  Bitwise reproducible for a given state
  * and layout.  nterms = 0 is allowed.  Errors: QH_ERR_ARG (null, dry handle), QH_ERR_BAD_QUBIT (mask bits >= nbits_global). */
 int qh_expect_pauli(qh_handle h, uint64_t nterms, const uint64_t *xmask, const uint64_t *zmask, double *out);
+/* Sparse readout (kernels_select.hip.h): a short list of (logical index, amplitude) entries instead of a reduction.  All
+ * three calls are per shard, run what is queued first and read only (state, bit map, relayout mode and device pointer are
+ * as before); they work at either width (complex64 amplitudes are widened to double, unrounded), in whatever layout the
+ * last flush left, on attached and host-mapped handles, from 1 local bit up.  index is the GLOBAL LOGICAL index, the bits
+ * the shard index holds included.  A probability is fma(im, im, re * re) in double, as qh_argmax computes it.  Dry handles:
+ * QH_ERR_ARG.                                                                                                            */
+typedef struct { uint64_t index; double re, im; } qh_entry;
+#define QH_SELECT_MAX (1u << 20)
+#define QH_TOPK_MAX 4096
+/* Every amplitude of the shard with probability >= threshold.  *count = their exact number, whatever cap is; *weight (may
+ * be NULL) = the sum of their probabilities, in double, in a fixed order without float atomics: bitwise reproducible for a
+ * given state and layout.  If *count <= cap, out[0..*count) holds them in ascending index, amplitudes bit for bit as
+ * stored; otherwise out is not written and the call is still QH_OK (raise the threshold or the cap).  cap == 0 with
+ * out == NULL is the count-only form; threshold == 0 selects everything.  One read of the state: a stream compaction with
+ * one returning 64-bit atomic add per wave and chunk that has hits (none once the count has passed cap);
+ * qh_stats.kernels_launched grows by 1, bytes_swept and bytes_algorithmic by the bytes of the state.
+ * Errors, nothing written: QH_ERR_ARG (null handle or count, threshold negative or NaN, cap > QH_SELECT_MAX, out == NULL
+ * with cap > 0).                                                                                                         */
+int qh_select(qh_handle h, double threshold, uint64_t cap, qh_entry *out, uint64_t *count, double *weight);
+/* The k entries of largest probability, most probable first, ties by ascending index -- at the cut too: the smallest
+ * indices get in.  Entries of probability 0 are never returned: *count = min(k, nonzero amplitudes of the shard).
+ * qh_topk(h, 1, ...) names the amplitude qh_argmax names.  A radix select on the bit pattern of the probability: one
+ * histogram read of the top key bits, then one compaction read from the lower edge of the bin that holds the k-th entry (a
+ * peaked state: kernels_launched + 2).  One compaction hands the host at most max(4 k, QH_TOPK_MAX) candidates; a boundary
+ * bin that holds more is histogrammed again on its next 12 key bits (at most 6 histogram reads: then the bin is one value),
+ * and one value with that many ties -- a flat state, or the near-flat output of a QFT -- is finished by scanning ranges of
+ * the LOGICAL index space for it (each scan counts as a kernel; bytes_swept grows by what it read).  Exact.  k == 0 is
+ * allowed; NaN amplitudes: unspecified.
+ * Errors: QH_ERR_ARG (null, k > QH_TOPK_MAX).                                                                             */
+int qh_topk(qh_handle h, uint64_t k, qh_entry *out, uint64_t *count);
+/* out[2j], out[2j+1] = the amplitude at global LOGICAL index logical[j]; exactly (0, 0) where another shard holds it, so
+ * the sum over ranks is the answer.  *nlocal (may be NULL) = how many of the entries this shard holds.  One gather kernel
+ * and one copy back, no read of the state (kernels_launched is unchanged).  Duplicates and count == 0 are allowed.
+ * Errors, nothing written: QH_ERR_ARG (null, count > 2^24, an index >= 2^nbits_global).                                   */
+int qh_amplitudes(qh_handle h, uint64_t count, const uint64_t *logical, double *out, uint64_t *nlocal);
 
 /* ---- two states (kernels_inner.hip.h) ------------------------------------ */
 /* A new handle on src's device holding a copy of src's state: what src has queued runs first, then one device-to-device

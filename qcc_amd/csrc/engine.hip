@@ -26,6 +26,8 @@
 #include "kernels_dense.hip.h"
 #include "kernels_mux.hip.h"
 #include "kernels_measure.hip.h"
+#include "kernels_select.hip.h"
+#include "select_plan.h"
 #include "kernels_expect.hip.h"
 #include "kernels_inner.hip.h"
 #include "kernels_axpby.hip.h"
@@ -728,7 +730,7 @@ int select_device(int device) {
 extern "C" {
 
 const char *qh_last_error(void) { return g_err.c_str(); }
-int qh_version(void) { return 112; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
+int qh_version(void) { return 113; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
 
 int qh_device_count(int *count) {
   if (!count) return fail(QH_ERR_ARG, "null");
@@ -1889,6 +1891,240 @@ int qh_project_bits(qh_handle h, uint64_t mask, uint64_t value) {
                        m.local, v.local);
   });
   return check_launch(h);
+}
+
+}  // extern "C"
+
+// ---- sparse readout: qh_select, qh_topk, qh_amplitudes (kernels_select.hip.h, select_plan.h) --------------------------
+namespace {
+
+constexpr uint64_t kSelectBlocks = 2048;            // blocks at most (one weight partial each)
+// qh_topk: candidates one compaction pass may hand to the host for sorting: four times k, at least QH_TOPK_MAX.  A boundary
+// bin that holds more is refined on the next key bits (one more read) instead of shipping and sorting entries that cannot
+// make the cut; the headroom over k keeps a large k on a generic state from refining down to single values before
+// above + in_bin happens to land in [k, cap].
+inline uint64_t topk_candidates(uint64_t k) { return std::max<uint64_t>(4 * k, QH_TOPK_MAX); }
+constexpr uint64_t kTieCap = 2 * QH_TOPK_MAX;       // entries one tie scan may append
+constexpr uint64_t kTieFloor = QH_TOPK_MAX;         // a range this short cannot overflow kTieCap
+constexpr uint64_t kKeyMax = 0x7fffffffffffffffull;
+static_assert(sizeof(qh_entry) == sizeof(qh::SelEntry) && offsetof(qh_entry, re) == offsetof(qh::SelEntry, re), "qh_entry layout");
+
+void count_state_read(qh_state_s *h, uint64_t amps) {
+  h->stats.kernels_launched++;
+  h->stats.bytes_swept += amps * h->amp_bytes();
+  h->stats.bytes_algorithmic += amps * h->amp_bytes();
+}
+
+double entry_prob(const qh_entry &e) { return std::fma(e.im, e.im, e.re * e.re); }     // (the device's sel_prob, bit for bit)
+
+// One compaction pass: the entries with klo <= key <= khi.  *count: how many there are; *weight (optional): the sum of
+// their probabilities; out (optional, cap entries): written, in the order the waves arrived, iff *count <= cap.
+int select_pass(qh_state_s *h, uint64_t klo, uint64_t khi, uint64_t cap, qh_entry *out, uint64_t *count, double *weight) {
+  const int c = meas_chunk_bits(h);
+  const uint64_t nchunks = 1ull << (h->nloc - c);
+  const unsigned grid = (unsigned)std::min<uint64_t>(nchunks, kSelectBlocks);
+  qh::ScratchLayout lay;
+  const size_t cnt_off = lay.add(8), w_off = lay.add(grid * sizeof(double)), ent_off = lay.add(cap * sizeof(qh::SelEntry));
+  HIP_TRY(h->meas.reserve(lay.total));
+  char *scr = h->meas.as<char>();
+  unsigned long long *d_cnt = (unsigned long long *)(scr + cnt_off);
+  double *d_w = (double *)(scr + w_off);
+  qh::SelEntry *d_ent = cap ? (qh::SelEntry *)(scr + ent_off) : nullptr;
+  HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, h->stream));
+  const qh::MeasMap mm = local_bits(h).meas;
+  with_real(h, [&](auto x) {
+    using R = decltype(x);
+    hipLaunchKernelGGL(qh::k_select<R>, dim3(grid), dim3(256), 0, h->stream, (const typename qh::AmpT<R>::type *)h->d_psi, c, nchunks, klo,
+                       khi, mm, d_cnt, d_ent, cap, d_w);
+  });
+  int rc = check_launch(h);
+  if (rc) return rc;
+  count_state_read(h, 1ull << h->nloc);
+  std::vector<double> wp(grid);
+  unsigned long long cnt = 0;
+  HIP_TRY(hipMemcpyAsync(wp.data(), d_w, grid * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if ((rc = read_back(h, &cnt, d_cnt, 8, "select"))) return rc;
+  *count = cnt;
+  if (weight) {
+    double w = 0.0;
+    for (unsigned b = 0; b < grid; ++b) w += wp[b];
+    *weight = w;
+  }
+  if (out && cnt && cnt <= cap) return read_back(h, out, d_ent, cnt * sizeof(qh::SelEntry), "select");
+  return QH_OK;
+}
+
+// One histogram pass of the radix select (select_plan.h): hist[b] for the 2^sel_bits(level) bins under pl.prefix
+int key_hist_pass(qh_state_s *h, const qh::SelPlan &pl, std::vector<uint64_t> *hist) {
+  const int c = meas_chunk_bits(h), bits = qh::sel_bits(pl.level), shift = qh::sel_shift(pl.level);
+  const uint64_t nchunks = 1ull << (h->nloc - c);
+  const unsigned grid = (unsigned)std::min<uint64_t>(nchunks, kSelectBlocks);
+  const size_t bytes = sizeof(uint64_t) << bits;
+  HIP_TRY(h->meas.reserve(bytes));
+  unsigned long long *d_hist = h->meas.as<unsigned long long>();
+  HIP_TRY(hipMemsetAsync(d_hist, 0, bytes, h->stream));
+  with_real(h, [&](auto x) {
+    using R = decltype(x);
+    hipLaunchKernelGGL(qh::k_key_hist<R>, dim3(grid), dim3(256), 0, h->stream, (const typename qh::AmpT<R>::type *)h->d_psi, c, nchunks,
+                       pl.prefix, shift, bits, d_hist);
+  });
+  const int rc = check_launch(h);
+  if (rc) return rc;
+  count_state_read(h, 1ull << h->nloc);
+  hist->assign((size_t)1 << bits, 0);
+  return read_back(h, hist->data(), d_hist, bytes, "topk");
+}
+
+// `need` entries whose key is `want`, the smallest LOGICAL indices first, appended to out: growing ranges of the shard's
+// amplitudes in logical order are gathered through the logical -> physical map until enough are found (as
+// argmax_from_tilemax finishes a flat state).  `total` of the shard's amplitudes have that key.
+int tie_scan(qh_state_s *h, uint64_t want, uint64_t need, uint64_t total, std::vector<qh_entry> *out) {
+  qh::TieMap tm{};
+  for (int b = 0; b < h->nglob; ++b) {
+    const Placed at = place_bit(h, b);
+    if (at.held) {
+      if (h->shard & at.held) tm.shard_logical |= 1ull << b;
+      continue;
+    }
+    tm.phys[tm.n] = (uint8_t)h->perm[b];
+    tm.log[tm.n++] = (uint8_t)b;
+  }
+  qh::ScratchLayout lay;
+  const size_t cnt_off = lay.add(8), ent_off = lay.add(kTieCap * sizeof(qh::SelEntry));
+  HIP_TRY(h->meas.reserve(lay.total));
+  unsigned long long *d_cnt = (unsigned long long *)(h->meas.as<char>() + cnt_off);
+  qh::SelEntry *d_ent = (qh::SelEntry *)(h->meas.as<char>() + ent_off);
+  const uint64_t n = 1ull << h->nloc;
+  uint64_t len = qh::sel_tie_first_len(n, total, need, kTieFloor), r0 = 0, found = 0;
+  std::vector<qh_entry> got;
+  while (found < need && r0 < n) {
+    const uint64_t r1 = std::min(n, r0 + len);
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, h->stream));
+    with_real(h, [&](auto x) {
+      using A = typename qh::AmpT<decltype(x)>::type;
+      hipLaunchKernelGGL(qh::k_tie_scan<A>, dim3(grid_for(r1 - r0, kRedBlocks)), dim3(256), 0, h->stream, (const A *)h->d_psi, r0, r1, want,
+                         tm, d_cnt, d_ent, kTieCap);
+    });
+    int rc = check_launch(h);
+    if (rc) return rc;
+    count_state_read(h, r1 - r0);
+    unsigned long long cnt = 0;
+    if ((rc = read_back(h, &cnt, d_cnt, 8, "topk"))) return rc;
+    if (cnt > kTieCap) {      // denser here than on average: a shorter range (one of kTieFloor amplitudes cannot overflow)
+      len = std::max(len / 16, kTieFloor);
+      continue;
+    }
+    got.resize(cnt);
+    if (cnt && (rc = read_back(h, got.data(), d_ent, cnt * sizeof(qh::SelEntry), "topk"))) return rc;
+    std::sort(got.begin(), got.end(), [](const qh_entry &a, const qh_entry &b) { return a.index < b.index; });
+    for (uint64_t j = 0; j < cnt && found < need; ++j, ++found) out->push_back(got[j]);
+    r0 = r1;
+    len = std::min(n, len * 4);
+  }
+  return QH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qh_select(qh_handle h, double threshold, uint64_t cap, qh_entry *out, uint64_t *count, double *weight) {
+  if (!h || !count) return fail(QH_ERR_ARG, "select: null handle or count");
+  if (!(threshold >= 0.0)) return fail(QH_ERR_ARG, "select: threshold %g is negative or not a number", threshold);
+  if (cap > QH_SELECT_MAX) return fail(QH_ERR_ARG, "select: cap %llu above QH_SELECT_MAX", (unsigned long long)cap);
+  if (cap && !out) return fail(QH_ERR_ARG, "select: cap %llu without out", (unsigned long long)cap);
+  int rc = enter(h);
+  if (rc) return rc;
+  const double t = threshold + 0.0;      // (-0.0 -> +0.0)
+  uint64_t klo, cnt = 0;
+  memcpy(&klo, &t, 8);
+  double w = 0.0;
+  if ((rc = select_pass(h, klo, qh::kSelKeyInf, cap, out, &cnt, &w))) return rc;
+  if (cnt <= cap) std::sort(out, out + cnt, [](const qh_entry &a, const qh_entry &b) { return a.index < b.index; });
+  *count = cnt;
+  if (weight) *weight = w;
+  return QH_OK;
+}
+
+int qh_topk(qh_handle h, uint64_t k, qh_entry *out, uint64_t *count) {
+  if (!h || !count || (k && !out)) return fail(QH_ERR_ARG, "topk: null handle, out or count");
+  if (k > QH_TOPK_MAX) return fail(QH_ERR_ARG, "topk: k = %llu above QH_TOPK_MAX", (unsigned long long)k);
+  int rc = enter(h);
+  if (rc) return rc;
+  if (k == 0) {
+    *count = 0;
+    return QH_OK;
+  }
+  qh::SelPlan pl = qh::sel_begin(k, topk_candidates(k));
+  std::vector<uint64_t> hist;
+  qh::SelStep st{};
+  do {
+    if ((rc = key_hist_pass(h, pl, &hist))) return rc;
+    st = qh::sel_step(pl, hist.data());
+  } while (st.next == qh::kSelRefine);
+  if (st.next == qh::kSelEmpty) {
+    *count = 0;
+    return QH_OK;
+  }
+  // the candidates above the cut: keys >= key_lo, or, in front of a tie scan, the keys above the tied value
+  std::vector<qh_entry> ent(st.candidates);
+  if (st.candidates) {
+    uint64_t cnt = 0;
+    const uint64_t klo = st.next == qh::kSelTies ? st.key_lo + 1 : st.key_lo;
+    if ((rc = select_pass(h, klo, kKeyMax, st.candidates, ent.data(), &cnt, nullptr))) return rc;
+    if (cnt != st.candidates)
+      return fail(QH_ERR_HIP, "topk: %llu candidates where the histogram counted %llu (the state changed under the call?)",
+                  (unsigned long long)cnt, (unsigned long long)st.candidates);
+    std::sort(ent.begin(), ent.end(), [](const qh_entry &a, const qh_entry &b) {
+      const double pa = entry_prob(a), pb = entry_prob(b);
+      return pa > pb || (pa == pb && a.index < b.index);
+    });
+  }
+  if (st.next == qh::kSelTies && (rc = tie_scan(h, st.key_lo, st.ties_needed, st.ties_total, &ent))) return rc;
+  const uint64_t m = std::min<uint64_t>(k, ent.size());
+  if (m) memcpy(out, ent.data(), m * sizeof(qh_entry));
+  *count = m;
+  return QH_OK;
+}
+
+int qh_amplitudes(qh_handle h, uint64_t count, const uint64_t *logical, double *out, uint64_t *nlocal) {
+  if (!h || (count && (!logical || !out))) return fail(QH_ERR_ARG, "amplitudes: null handle, indices or out");
+  if (count > (1ull << 24)) return fail(QH_ERR_ARG, "amplitudes: %llu indices (at most 2^24 a call)", (unsigned long long)count);
+  if (h->nglob < 64)
+    for (uint64_t j = 0; j < count; ++j)
+      if (logical[j] >> h->nglob)
+        return fail(QH_ERR_ARG, "amplitudes: index %llu (entry %llu) out of range", (unsigned long long)logical[j], (unsigned long long)j);
+  int rc = enter(h);
+  if (rc) return rc;
+  qh::GatherMap gm{};
+  gm.nglob = h->nglob;
+  for (int b = 0; b < h->nglob; ++b) {
+    const Placed at = place_bit(h, b);
+    gm.l2p[b] = at.held ? 0xff : (uint8_t)h->perm[b];
+    if (at.held) {
+      gm.held |= 1ull << b;
+      if (h->shard & at.held) gm.held_ones |= 1ull << b;
+    }
+  }
+  uint64_t mine = 0;
+  for (uint64_t j = 0; j < count; ++j) mine += (logical[j] & gm.held) == gm.held_ones;
+  if (count) {
+    qh::ScratchLayout lay;
+    const size_t idx_off = lay.add(count * 8), out_off = lay.add(count * 16);
+    HIP_TRY(h->meas.reserve(lay.total));
+    uint64_t *d_idx = (uint64_t *)(h->meas.as<char>() + idx_off);
+    double2 *d_out = (double2 *)(h->meas.as<char>() + out_off);
+    HIP_TRY(hipMemcpyAsync(d_idx, logical, count * 8, hipMemcpyHostToDevice, h->stream));
+    with_real(h, [&](auto x) {
+      using A = typename qh::AmpT<decltype(x)>::type;
+      hipLaunchKernelGGL(qh::k_gather_amps<A>, dim3(grid_for(count, kRedBlocks)), dim3(256), 0, h->stream, (const A *)h->d_psi,
+                         (const uint64_t *)d_idx, count, gm, d_out);
+    });
+    if ((rc = check_launch(h))) return rc;
+    if ((rc = read_back(h, out, d_out, count * 16, "amplitudes"))) return rc;
+  }
+  if (nlocal) *nlocal = mine;
+  return QH_OK;
 }
 
 }  // extern "C"

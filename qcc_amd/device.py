@@ -368,6 +368,47 @@ class DeviceState:
                                           out.ctypes.data_as(_dp)))
     return out
 
+  # -- sparse readout ------------------------------------------------------------
+  @staticmethod
+  def _entries(buf, count):
+    """(idx uint64, amp complex128) of the first `count` qh_entry records of a ctypes array."""
+    if not count:
+      return np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.complex128)
+    rec = np.frombuffer(buf, dtype=np.dtype([('index', np.uint64), ('re', np.float64), ('im', np.float64)]), count=count)
+    amp = np.empty(count, dtype=np.complex128)      # (component by component: re + 1j * im would lose the sign of a zero)
+    amp.real, amp.imag = rec['re'], rec['im']
+    return rec['index'].copy(), amp
+
+  def select(self, threshold, cap=1 << 16):
+    """(idx uint64, amp complex128, count, weight): the amplitudes of this shard with probability >= threshold, by ascending
+    GLOBAL LOGICAL index, their exact number and the sum of their probabilities (qh_select: one read of the state).  More
+    than cap of them: the arrays are empty, count and weight still hold.  cap = 0 counts only."""
+    cap = int(cap)
+    buf = (native.QhEntry * cap)() if cap else None
+    n, w = ctypes.c_uint64(), ctypes.c_double()
+    native.check(self.lib.qh_select(self.h, float(threshold), cap, buf, ctypes.byref(n), ctypes.byref(w)))
+    idx, amp = self._entries(buf, n.value if n.value <= cap else 0)
+    return idx, amp, int(n.value), float(w.value)
+
+  def topk(self, k):
+    """(idx uint64, amp complex128): the k most probable amplitudes of this shard, most probable first, ties by ascending
+    GLOBAL LOGICAL index; never one of probability 0, so fewer than k where the support is smaller (qh_topk)."""
+    k = int(k)
+    buf = (native.QhEntry * k)() if k else None
+    n = ctypes.c_uint64()
+    native.check(self.lib.qh_topk(self.h, k, buf, ctypes.byref(n)))
+    return self._entries(buf, n.value)
+
+  def amplitudes(self, indices, nlocal=False):
+    """complex128 array: the amplitudes at the GLOBAL LOGICAL indices given, exact zeros where another shard holds them
+    (qh_amplitudes: one gather, one copy back).  nlocal=True: (array, how many this shard holds)."""
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    out = np.zeros(idx.size, dtype=np.complex128)
+    n = ctypes.c_uint64()
+    native.check(self.lib.qh_amplitudes(self.h, int(idx.size), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                        out.ctypes.data_as(_dp), ctypes.byref(n)))
+    return (out, int(n.value)) if nlocal else out
+
   # -- two states ---------------------------------------------------------------
   def clone(self):
     """A new DeviceState holding a copy of this one as it lies -- amplitudes, bit map, shard geometry, fusion level --

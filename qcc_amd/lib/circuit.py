@@ -148,6 +148,17 @@ class _LazyPsi(np.lib.mixins.NDArrayOperatorsMixin):
     def __getattr__(self, name):
         return getattr(self._get(), name)
 
+    def dump(self, desc=None, prob_only=True):
+        """State.dump without the snapshot: while nobody has looked yet and the owner's state lives on a device that can
+        select, the rows come from there (the state as it is NOW).  prob_only=False prints every basis state and is refused
+        above 2^16 of them."""
+        if self._snap is None:
+            dev = self._owner._sparse_device()      # pylint: disable=protected-access
+            if dev is not None:
+                self._owner._dump_state(dev, desc, prob_only)      # pylint: disable=protected-access
+                return
+        self._get().dump(desc, prob_only)
+
     def __getitem__(self, key):
         return self._get()[key]
 
@@ -735,6 +746,102 @@ class qc:
     def norm2(self):
         return self._ensure_device().norm2()
 
+    # Sparse readout (extensions): short lists of (bits, amplitude, probability) straight from the device (qh_select,
+    # qh_topk, qh_amplitudes) -- nothing is downloaded, so they work at sizes where qc.psi raises.  Devices without
+    # select / topk / amplitudes, states still a product on the host and alias mode read qc.psi with NumPy instead.
+    def _sparse_device(self):
+        if self._q_ops:
+            self._drain()
+        dev = self._dev
+        if (self._dev_ok and not self._aliased() and hasattr(dev, 'select') and hasattr(dev, 'topk')
+                and hasattr(dev, 'amplitudes')):
+            return dev
+        return None
+
+    @staticmethod
+    def _select_checked(dev, threshold, limit, what):
+        idx, amp, count, weight = dev.select(threshold, limit)
+        if count > limit:
+            raise ValueError(f'{what}: {count} basis states have probability >= {threshold:g} (total weight {weight:.6g}), '
+                             f'more than limit = {limit}; raise the threshold or the limit')
+        return np.asarray(idx, dtype=np.uint64), np.asarray(amp, dtype=np.complex128)
+
+    def _triples(self, idx, amp):
+        n = self._nbits
+        return [(helper.val2bits(i, n), complex(a), float((a.conjugate() * a).real)) for i, a in zip(idx.tolist(), amp.tolist())]
+
+    def support(self, threshold=1e-5, limit=1 << 16):
+        """[(bits, amplitude, probability)] of every basis state with probability >= threshold, in index order.  More than
+        `limit` of them: ValueError that names their number and total weight."""
+        limit = int(limit)
+        dev = self._sparse_device()
+        if dev is not None:
+            return self._triples(*self._select_checked(dev, float(threshold), limit, 'support'))
+        a = np.asarray(self.psi, dtype=np.complex128).reshape(-1)
+        p = a.real * a.real + a.imag * a.imag
+        idx = np.flatnonzero(p >= threshold)
+        if idx.size > limit:
+            raise ValueError(f'support: {idx.size} basis states have probability >= {threshold:g} (total weight '
+                             f'{float(p[idx].sum()):.6g}), more than limit = {limit}; raise the threshold or the limit')
+        return self._triples(idx, a[idx])
+
+    def top(self, k):
+        """The k most probable basis states as [(bits, amplitude, probability)], most probable first, ties by ascending
+        index; never one of probability 0."""
+        k = int(k)
+        if k < 0:
+            raise ValueError(f'top: k = {k}')
+        dev = self._sparse_device()
+        if dev is not None:
+            idx, amp = dev.topk(k)
+            return self._triples(np.asarray(idx, dtype=np.uint64), np.asarray(amp, dtype=np.complex128))
+        a = np.asarray(self.psi, dtype=np.complex128).reshape(-1)
+        p = a.real * a.real + a.imag * a.imag
+        order = np.lexsort((np.arange(p.size), -p))[:k]
+        order = order[p[order] > 0]
+        return self._triples(order, a[order])
+
+    def _indices(self, states):
+        n = self._nbits
+        out = []
+        for s in states:
+            i = int(s) if isinstance(s, (int, np.integer)) else helper.bits2val(s)
+            if i < 0 or i >> n:
+                raise ValueError(f'basis state {s} out of range for {n} qubits')
+            out.append(i)
+        return np.array(out, dtype=np.uint64)
+
+    def ampls(self, states):
+        """complex128 array: the amplitudes of the basis states given as bit tuples (as qc.ampl takes them) or integer
+        indices, fetched in one device call."""
+        idx = self._indices(states)
+        dev = self._sparse_device()
+        if dev is not None:
+            return np.asarray(dev.amplitudes(idx), dtype=np.complex128)
+        return np.asarray(self.psi, dtype=np.complex128).reshape(-1)[idx.astype(np.int64)]
+
+    def probs(self, states):
+        """float64 array: the probabilities of those basis states."""
+        a = self.ampls(states)
+        return a.real * a.real + a.imag * a.imag
+
+    def _dump_state(self, dev, desc, prob_only, limit=1 << 16):
+        """What State.dump(desc, prob_only) prints, from a device selection: the same header, rows, formats and order."""
+        n = self._nbits
+        if not prob_only and (1 << n) > limit:
+            raise ValueError(f'dump: prob_only=False would print 2^{n} basis states, more than limit = {limit}')
+        # a little under State.dump's threshold, which is then applied to each row exactly as State.dump applies it (at
+        # the state's own width)
+        idx, amp = self._select_checked(dev, 0.99 * state.DUMP_MIN_PROB if prob_only else 0.0, limit, 'dump')
+        rows = []
+        for i, a in zip(idx.tolist(), amp.astype(tensor.tensor_type())):
+            if prob_only and np.real(a.conj() * a) < state.DUMP_MIN_PROB:
+                continue
+            rows.append(state.dump_row(n, i, a))
+        if desc:
+            print(state.dump_header(n, desc))
+        print(*rows, sep='\n')
+
     def measure_bit(self, idx, tostate=0, collapse=True):
         """P(qubit idx == tostate); with collapse, project and renormalise in place.
 
@@ -1222,7 +1329,11 @@ class qc:
             print(f'Circuit: {self.name}, Gates: {len(self.ir.gates)}, QBits: {self.nbits}')
         print(self.ir, end='')
         if pstate:
-            self.psi.dump('Current state')
+            dev = self._sparse_device() if self._nbits else None
+            if dev is not None:
+                self._dump_state(dev, 'Current state', True)
+            else:
+                self.psi.dump('Current state')
 
     def sync(self):
         """Wait for all queued device work (for timing)."""

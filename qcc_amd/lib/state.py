@@ -281,6 +281,24 @@ def _remove_hooks():
         _hooks_on = False
 
 
+DUMP_MIN_PROB = 10e-6      # State.dump skips basis states below this probability
+
+
+def dump_header(nbits, desc):
+    """The first line of State.dump: the qubit numbers over the bit columns, and the description."""
+    return '|' + ''.join(str(i % 10) for i in range(nbits)) + f"> '{desc}'"
+
+
+def dump_row(nbits, index, a):
+    """One row of State.dump: basis state `index` of nbits qubits, whose amplitude is a (a scalar of the state's dtype).
+    Shared with the printers that get their rows from the device (qc.dump) instead of walking a host copy."""
+    digits = int(math.log10(2 ** nbits)) + 1
+    s = format(index, f'0{nbits}b')
+    p = np.real(a.conj() * a)
+    return (f'|{s}> (|{index:{digits}d}>):  ampl: {a:+.2f} '
+            f'prob: {p:.2f} Phase: {math.degrees(cmath.phase(a)):5.1f}')
+
+
 class State(tensor.Tensor):
     """Amplitudes of an n-qubit pure state, qubit 0 = most significant index bit."""
 
@@ -400,17 +418,14 @@ class State(tensor.Tensor):
     def dump(self, desc=None, prob_only=True):
         """Print the basis states with non-negligible probability."""
         n = self.nbits
-        digits = int(math.log10(2 ** n)) + 1
         if desc:
-            print('|' + ''.join(str(i % 10) for i in range(n)) + f"> '{desc}'")
+            print(dump_header(n, desc))
         rows = []
         for bits in helper.bitprod(n):
             p = self.prob(*bits)
-            if prob_only and p < 10e-6:
+            if prob_only and p < DUMP_MIN_PROB:
                 continue
-            s = ''.join(str(b) for b in bits)
-            rows.append(f'|{s}> (|{int(s, 2):{digits}d}>):  ampl: {self.ampl(*bits):+.2f} '
-                        f'prob: {p:.2f} Phase: {self.phase(*bits):5.1f}')
+            rows.append(dump_row(n, helper.bits2val(bits), self.ampl(*bits)))
         rows.sort()
         print(*rows, sep='\n')
 

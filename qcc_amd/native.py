@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB_PATH = os.environ.get('QCC_HIP_LIB') or os.path.join(PKG, 'libqcc_hip.so')  # env: A/B builds only
 SOURCES = [os.path.join(PKG, 'csrc', f) for f in
-           ('engine.hip', 'buffers.hip.h', 'kernels_gate.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_measure.hip.h', 'kernels_expect.hip.h', 'kernels_inner.hip.h', 'kernels_axpby.hip.h', 'inner_plan.h', 'kernels_resize.hip.h', 'resize_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h',
+           ('engine.hip', 'buffers.hip.h', 'kernels_gate.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_measure.hip.h', 'kernels_select.hip.h', 'select_plan.h', 'kernels_expect.hip.h', 'kernels_inner.hip.h', 'kernels_axpby.hip.h', 'inner_plan.h', 'kernels_resize.hip.h', 'resize_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h',
             'sweep_island_rb2.inc', 'sweep_island_rb3.inc', 'sweep_island_rb4.inc',
             'sweep_island_rb5.inc', 'sweep_island_f32_rb2.inc', 'sweep_island_f32_rb3.inc',
             'sweep_island_f32_rb4.inc', 'sweep_island_f32_rb5.inc', 'sweep_island_f32_rb6.inc', 'sweep_handlers.inc',
@@ -48,6 +48,14 @@ class QhInnerTiles(ctypes.Structure):
 
   def as_dict(self):
     return {k: (int(getattr(self, k)) if isinstance(getattr(self, k), int) else list(getattr(self, k))) for k, _ in self._fields_}
+
+
+QH_SELECT_MAX, QH_TOPK_MAX = 1 << 20, 4096
+
+
+class QhEntry(ctypes.Structure):
+  """include/qcc_hip.h qh_entry: one (global logical index, amplitude) of qh_select / qh_topk."""
+  _fields_ = [('index', _u64), ('re', ctypes.c_double), ('im', ctypes.c_double)]
 
 
 # name -> (restype, argtypes); every symbol declared in include/qcc_hip.h
@@ -97,6 +105,9 @@ SIGNATURES = {
     'qh_sample': (_i32, [_vp, _u64, _dp, ctypes.POINTER(ctypes.c_uint64)]),
     'qh_project_bits': (_i32, [_vp, _u64, _u64]),
     'qh_expect_pauli': (_i32, [_vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _dp]),
+    'qh_select': (_i32, [_vp, ctypes.c_double, _u64, ctypes.POINTER(QhEntry), ctypes.POINTER(_u64), _dp]),
+    'qh_topk': (_i32, [_vp, _u64, ctypes.POINTER(QhEntry), ctypes.POINTER(_u64)]),
+    'qh_amplitudes': (_i32, [_vp, _u64, ctypes.POINTER(_u64), _dp, ctypes.POINTER(_u64)]),
     'qh_clone': (_i32, [_vp, ctypes.POINTER(_vp)]),
     'qh_copy': (_i32, [_vp, _vp]),
     'qh_inner': (_i32, [_vp, _vp, _dp]),

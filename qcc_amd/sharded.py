@@ -112,6 +112,59 @@ def predict_step_ms(nbits, world, *, sweeps=None, exchanges=None, bit_width=128,
                           f'amplitudes (measured); packed rounds at {PACK_GBPS / 1e3:g} TB/s; {overlap_efficiency:g} of 2 x 7/8 sweeps hidden')}
 
 
+def _fma_exact(re, im):
+  """fma(im, im, re * re) of two Python floats by exact rational arithmetic (the slow path of fma_probs)."""
+  from fractions import Fraction  # pylint: disable=import-outside-toplevel
+  return float(Fraction(im) * Fraction(im) + Fraction(re * re))
+
+
+def fma_probs(amps):
+  """float64 array: the probability of each complex128 amplitude as the engine's readers compute it, fma(im, im, re * re):
+  re * re rounded once, then im * im + that rounded once.  ShardedDevice.topk merges per-rank lists on the host and must
+  order them, ties included, exactly as one engine would have; qh_entry carries no probability, so it is recomputed here.
+
+  Exact and vectorised.  With x = re, y = im in double:
+    h = fl(x * x)                                      the engine's first rounding;
+    y * y = ph + pl exactly                            Dekker's product: y = yh + yl by Veltkamp's split with 2^27 + 1 (26
+                                                       bits each), ph = fl(y * y), pl = ((yh*yh - ph) + 2*yh*yl) + yl*yl, every
+                                                       operation of which is exact while y * y neither overflows nor loses
+                                                       bits to underflow (|y| in [1e-140, 1e150] here);
+    ph + h = s1 + e1, e1 + pl = t + te, s1 + t = r + err      three error-free sums (Knuth's two-sum), so that the number
+                                                       the engine rounds, y*y + h, equals r + err + te exactly, with
+                                                       r = fl(s1 + t), |err| <= ulp(r)/2 and |te| <= ulp(t)/2 <= 2^-53 ulp(r).
+  r is the correctly rounded value of r + err alone.  Adding te can change the rounding only if r + err lies within |te| of
+  a rounding boundary of r: a midpoint between r and a neighbour, i.e. |err| within |te| of ulp(r)/2 -- or of ulp(r)/4,
+  which is the midpoint on the lower side when r is a power of two and the spacing below it is half the spacing above
+  (np.spacing gives the one above).  Entries with te != 0 and |err| within 2|te| of either band are redone in rational
+  arithmetic; since te is 2^-53 of an ulp, that is about one entry in 10^15.  te == 0: r is exact rounding of the exact sum.
+  Amplitudes that are not finite, or whose squares leave the range where the product is error-free, go the slow way too."""
+  a = np.asarray(amps, dtype=np.complex128).reshape(-1)
+  x, y = np.ascontiguousarray(a.real), np.ascontiguousarray(a.imag)
+  with np.errstate(all='ignore'):
+    h = x * x
+    ph = y * y
+    c = 134217729.0 * y                     # 2^27 + 1
+    yh = c - (c - y)
+    yl = y - yh
+    pl = ((yh * yh - ph) + 2.0 * yh * yl) + yl * yl
+
+    def two_sum(u, v):
+      s_ = u + v
+      b = s_ - u
+      return s_, (u - (s_ - b)) + (v - b)
+    s1, e1 = two_sum(ph, h)
+    t, te = two_sum(e1, pl)
+    r, err = two_sum(s1, t)
+    sp = np.spacing(np.abs(r))
+    edge = (te != 0) & ((np.abs(np.abs(err) - 0.5 * sp) <= 2 * np.abs(te)) | (np.abs(np.abs(err) - 0.25 * sp) <= 2 * np.abs(te)))
+    ay, ax = np.abs(y), np.abs(x)
+    odd = ~(np.isfinite(x) & np.isfinite(y)) | (ay > 1e150) | (ax > 1e150) | ((ay < 1e-140) & (ay > 0)) | ((ax < 1e-140) & (ax > 0))
+  for j in np.flatnonzero(edge | odd).tolist():
+    re, im = float(x[j]), float(y[j])
+    r[j] = _fma_exact(re, im) if (re - re == 0.0 and im - im == 0.0) else im * im + re * re
+  return r
+
+
 class MemoryPlanError(RuntimeError):
   """A rank's shard + staging does not fit its free device memory (raised on EVERY rank, before anything is allocated)."""
 
@@ -807,6 +860,90 @@ class ShardedDevice:
         lo |= ((got >> np.uint64(p)) & np.uint64(1)) << np.uint64(b)
       out[mine] = lo.astype(np.float64)                         # (indices < 2^53: exact in a double)
     return self._all_sum_array(out).astype(np.uint64)
+
+  # -- sparse readout: the engine's indices are this layer's PHYSICAL ones -----------------------------------------------
+  def _map_indices(self, idx, to_logical):
+    """uint64 array of global indices through the router's bit map (physical -> logical, or back)."""
+    idx = np.asarray(idx, dtype=np.uint64)
+    out = np.zeros_like(idx)
+    for b, p in enumerate(self.st.perm):
+      src, dst = (p, b) if to_logical else (b, p)
+      out |= ((idx >> np.uint64(src)) & np.uint64(1)) << np.uint64(dst)
+    return out
+
+  def _all_entries(self, idx, amp):
+    """Every rank's (physical index, amplitude) entries on every rank, in rank order, as (logical idx, amp, counts): each
+    rank fills its own slots of one summed array (indices < 2^53 are exact in a double; a value plus zeros is exact)."""
+    st = self.st
+    counts = np.zeros(st.world)
+    counts[st.rank] = idx.size
+    counts = self._all_sum_array(counts).astype(np.int64)
+    off = int(counts[:st.rank].sum())
+    buf = np.zeros(3 * int(counts.sum()))
+    buf[3 * off: 3 * (off + idx.size)] = np.stack([idx.astype(np.float64), amp.real, amp.imag], axis=1).reshape(-1)
+    buf = self._all_sum_array(buf).reshape(-1, 3)
+    return self._map_indices(buf[:, 0].astype(np.uint64), True), buf[:, 1] + 1j * buf[:, 2], counts
+
+  def select(self, threshold, cap=1 << 16):
+    """DeviceState.select over all ranks: (idx, amp, count, weight) by ascending LOGICAL index, counts and weights summed;
+    the arrays are empty when more than cap qualify.  Collective; the same on every rank."""
+    idx, amp, count, weight = self.st.eng.select(threshold, cap)
+    count, weight = self._all_sum([count, weight])
+    count = int(count)
+    if count > int(cap):         # (every rank sees the same total: all take this branch)
+      return np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.complex128), count, weight
+    idx, amp, _ = self._all_entries(idx, amp)
+    order = np.argsort(idx, kind='stable')
+    return idx[order], amp[order], count, weight
+
+  def amplitudes(self, indices):
+    """The amplitudes at the LOGICAL indices given (DeviceState.amplitudes on every rank: exact zeros for what another
+    rank holds, then a sum over the ranks)."""
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    if idx.size and int(idx.max()) >> self.st.nbits:
+      raise ValueError(f'amplitudes: an index at or above 2^{self.st.nbits}')
+    a = np.asarray(self.st.eng.amplitudes(self._map_indices(idx, False)), dtype=np.complex128)
+    flat = self._all_sum_array(np.concatenate([a.real, a.imag]))
+    return flat[:idx.size] + 1j * flat[idx.size:]
+
+  TIE_SELECT_CAP = 1 << 16      # topk: tied entries at the cut are fetched whole up to this many, by prefixes above
+
+  def topk(self, k):
+    """DeviceState.topk over all ranks: (idx, amp), most probable first, ties by ascending LOGICAL index.  Every rank's k
+    best are merged.  A rank breaks ties at ITS cut by the engine's index order, which is this layer's physical one: where
+    a rank's list is full and ends on the merged cut's probability, the tied entries are fetched again in logical order --
+    all of them through select() if they are few, else by reading growing prefixes of the logical index range
+    (amplitudes()) until enough are found, which is how a flat state ends up with indices 0 .. k-1."""
+    k = int(k)
+    idx, amp, counts = self._all_entries(*self.st.eng.topk(k))
+    p = fma_probs(amp)
+    order = np.lexsort((idx, -p))
+    idx, amp, p_sorted = idx[order], amp[order], p[order]
+    if idx.size <= k or k == 0:
+      return idx[:k], amp[:k]
+    v = p_sorted[k - 1]
+    ends = np.cumsum(counts)
+    if not any(c == k and p[e - 1] >= v for c, e in zip(counts, ends)):      # no rank cut a tie with the merged cut
+      return idx[:k], amp[:k]
+    above = int(np.count_nonzero(p_sorted > v))
+    need = k - above
+    tidx, tamp, tcount, _ = self.select(float(v), self.TIE_SELECT_CAP)
+    if tcount <= self.TIE_SELECT_CAP:
+      tie = fma_probs(tamp) == v
+      tidx, tamp = tidx[tie][:need], tamp[tie][:need]
+    else:
+      found_i, found_a, lo, length, n = [], [], 0, max(4096, 4 * need), 1 << self.st.nbits
+      while sum(x.size for x in found_i) < need and lo < n:
+        rng = np.arange(lo, min(n, lo + length), dtype=np.uint64)
+        a = self.amplitudes(rng)
+        near = np.flatnonzero(np.abs(a.real * a.real + a.imag * a.imag - v) <= 8 * np.spacing(v))
+        hit = near[fma_probs(a[near]) == v]
+        found_i.append(rng[hit])
+        found_a.append(a[hit])
+        lo += length
+        length = min(4 * length, 1 << 22)
+      tidx, tamp = np.concatenate(found_i)[:need], np.concatenate(found_a)[:need]
+    return np.concatenate([idx[:above], tidx]), np.concatenate([amp[:above], tamp])
 
   def project_bits(self, mask, value):
     st = self.st
