@@ -2811,12 +2811,18 @@ namespace {
       return fail(QH_ERR_COMM, "%s: %s (%s:%d)", #expr, qh::rccl().GetErrorString(r_), __FILE__, __LINE__); \
   } while (0)
 
-int comm_common_init(qh_state_s *h, int nranks, int rank) {
-  if (!h) return fail(QH_ERR_ARG, "null handle");
-  if (h->comm) return fail(QH_ERR_ARG, "handle already has a communicator");
+// what every transport asks of (nranks, rank)
+int check_ranks(int nranks, int rank) {
   if (nranks < 1 || (nranks & (nranks - 1)) || rank < 0 || rank >= nranks)
     return fail(QH_ERR_ARG, "nranks %d must be a power of two, rank %d inside it", nranks, rank);
   if (nranks > qh::kMaxXferMoves + 1) return fail(QH_ERR_ARG, "at most %d ranks", qh::kMaxXferMoves + 1);
+  return QH_OK;
+}
+
+int comm_common_init(qh_state_s *h, int nranks, int rank) {
+  if (!h) return fail(QH_ERR_ARG, "null handle");
+  if (h->comm) return fail(QH_ERR_ARG, "handle already has a communicator");
+  if (int rc = check_ranks(nranks, rank)) return rc;
   if (h->bw != 128 && h->bw != 64) return fail(QH_ERR_BAD_DTYPE, "bit width");
   int rc0 = enter(h);
   if (rc0) return rc0;
@@ -2917,11 +2923,9 @@ int verify_geometry(qh_state_s *h, uint64_t sig) {
 }
 
 // What must be equal on every rank besides the geometry itself: the planner's switches and the build.
-uint64_t env_build_hash() {
+uint64_t env_build_hash(const qh::ExchangeSwitches &xsw) {
   std::string s = qh::PlanSwitches::from_env().key();
-  // (the EFFECTIVE values: an unset switch and one set to its default are the same plan)
-  s += std::to_string(env_int("QH_EXCHANGE_SLAB_BITS", 3)) + ";" + std::to_string(env_int("QH_EXCHANGE_PACK", -1)) + ";" +
-       std::to_string(env_int("QH_RELAYOUT", 1) != 0) + ";";
+  s += xsw.key() + std::to_string(env_int("QH_RELAYOUT", 1) != 0) + ";";
   // the build: the library's version and the layouts the planner and the kernels share -- NOT the time of compilation (two
   // nodes that build the same sources in-tree must be able to exchange)
   s += "v" + std::to_string(qh_version()) + ":" + std::to_string(sizeof(qh::SweepArgs)) + ":" + std::to_string(sizeof(qh::SweepOp)) +
@@ -2931,16 +2935,145 @@ uint64_t env_build_hash() {
   return hsh;
 }
 
+// The gather (or scatter) kernel of packed round ci of slab k: every move's amplitudes to (from) `stage`, peer after peer.
+void launch_packed_round(qh_state_s *h, const qh::ExchangePlan &pl, const std::vector<qh::BlockMove> &moves, bool unpack, void *stage,
+                         int k, uint64_t ci, hipStream_t st) {
+  qh::XferGeom g{};
+  g.ins.n = pl.nins;
+  for (int i = 0; i < pl.nins; ++i) g.ins.pos[i] = pl.ins_pos[i];
+  g.np = pl.np;
+  for (int m = 0; m < pl.np; ++m) g.off[m] = pl.packed_offset(k, unpack ? moves[m].land : moves[m].blk);
+  with_real(h, [&](auto x) {
+    launch_xfer<typename qh::AmpT<decltype(x)>::type>(unpack, h->d_psi, stage, pl.chunk_amps(), pl.round_start(ci), g, st);
+  });
+}
+
+// The rounds of the host-staged transport: synchronous, all on the exchange stream.  slab_done[k]: slab k is written.
+int run_rounds_host_staged(qh_state_s *h, const qh::ExchangePlan &pl, const std::vector<qh::BlockMove> &moves,
+                           const std::vector<hipEvent_t> &slab_done) {
+  qh::Comm *c = h->comm;
+  char *const psi = (char *)h->d_psi, *const staging = c->staging.as<char>();
+  const size_t np = moves.size(), need = pl.half_bytes;
+  const uint64_t ab = pl.amp_bytes, nb = pl.chunk_bytes();
+  HIP_TRY(c->h_send.reserve(need));
+  HIP_TRY(c->h_recv.reserve(need));
+  char *const h_send = c->h_send.as<char>(), *const h_recv = c->h_recv.as<char>();
+  std::vector<int> peers(np);
+  std::vector<void *> sp(np), rp(np);
+  for (size_t m = 0; m < np; ++m) {
+    peers[m] = moves[m].peer;
+    sp[m] = h_send + m * nb;
+    rp[m] = h_recv + m * nb;
+  }
+  for (int k = 0; k < pl.slabs(); ++k) {
+    HIP_TRY(hipEventSynchronize(slab_done[k]));
+    if (k == 0) { HIP_TRY(hipEventRecord(c->t0, c->xstream)); }
+    for (uint64_t ci = 0; ci < pl.rounds_per_slab; ++ci) {
+      const uint64_t off = pl.round_offset(k, ci);
+      if (pl.packed) {
+        launch_packed_round(h, pl, moves, false, staging, k, ci, c->xstream);
+        HIP_TRY(hipMemcpyAsync(h_send, staging, need, hipMemcpyDeviceToHost, c->xstream));
+      } else {
+        for (size_t m = 0; m < np; ++m)
+          HIP_TRY(hipMemcpyAsync(sp[m], psi + (off | pl.block_offset(moves[m].blk)) * ab, nb, hipMemcpyDeviceToHost, c->xstream));
+      }
+      HIP_TRY(hipStreamSynchronize(c->xstream));
+      if (c->custom(c->custom_user, (int)np, peers.data(), sp.data(), rp.data(), nb) != 0)
+        return fail(QH_ERR_COMM, "host-staged transport: the round callback failed");
+      if (pl.packed) {
+        HIP_TRY(hipMemcpyAsync(staging, h_recv, need, hipMemcpyHostToDevice, c->xstream));
+        launch_packed_round(h, pl, moves, true, staging, k, ci, c->xstream);
+      } else {
+        for (size_t m = 0; m < np; ++m)
+          HIP_TRY(hipMemcpyAsync(psi + (off | pl.block_offset(moves[m].land)) * ab, rp[m], nb, hipMemcpyHostToDevice, c->xstream));
+      }
+      HIP_TRY(hipStreamSynchronize(c->xstream));
+      c->stats.rounds++;
+    }
+    hipEvent_t ev = c->event();
+    if (!ev) return fail(QH_ERR_HIP, "hipEventCreate failed");
+    HIP_TRY(hipEventRecord(ev, c->xstream));
+    c->arrivals.push_back(qh::Arrival{pl.slab_mask, pl.slab_vals[k], ev});
+  }
+  HIP_TRY(hipEventRecord(c->t1, c->xstream));
+  return QH_OK;
+}
+
+// The rounds of the RCCL transport: grouped send/recv per round on xstream, landing (copies / scatter kernel) on cstream,
+// packing on pstream; the two halves of the staging area alternate from round to round.
+int run_rounds_rccl(qh_state_s *h, const qh::ExchangePlan &pl, const std::vector<qh::BlockMove> &moves,
+                    const std::vector<hipEvent_t> &slab_done) {
+  qh::Comm *c = h->comm;
+  if (!c->nccl) return fail(QH_ERR_COMM, "no communicator (qh_comm_init)");
+  char *const psi = (char *)h->d_psi, *const staging = c->staging.as<char>();
+  const size_t np = moves.size(), half = pl.half_bytes;
+  const uint64_t ab = pl.amp_bytes, nb = pl.chunk_bytes();
+  const bool packed = pl.packed;
+  const ncclDataType_t dt = h->bw == 128 ? ncclDouble : ncclFloat;
+  const size_t cnt = (size_t)pl.chunk_amps() * 2;
+  auto &R = qh::rccl();
+  hipEvent_t copied[2] = {nullptr, nullptr};   // receive half free again
+  hipEvent_t sent[2] = {nullptr, nullptr};     // send half free again (packed)
+  uint64_t round = 0;
+  for (int k = 0; k < pl.slabs(); ++k) {
+    HIP_TRY(hipStreamWaitEvent(packed ? c->pstream : c->xstream, slab_done[k], 0));
+    if (k == 0) { HIP_TRY(hipEventRecord(c->t0, packed ? c->pstream : c->xstream)); }
+    hipEvent_t last_copy = nullptr;
+    for (uint64_t ci = 0; ci < pl.rounds_per_slab; ++ci, ++round) {
+      const int par = (int)(round & 1);
+      const uint64_t off = pl.round_offset(k, ci);
+      char *stage = staging + par * half;
+      char *sstage = staging + (2 + par) * half;
+      if (packed) {
+        if (sent[par]) HIP_TRY(hipStreamWaitEvent(c->pstream, sent[par], 0));
+        launch_packed_round(h, pl, moves, false, sstage, k, ci, c->pstream);
+        hipEvent_t pk = c->event();
+        if (!pk) return fail(QH_ERR_HIP, "hipEventCreate failed");
+        HIP_TRY(hipEventRecord(pk, c->pstream));
+        HIP_TRY(hipStreamWaitEvent(c->xstream, pk, 0));
+      }
+      if (copied[par]) HIP_TRY(hipStreamWaitEvent(c->xstream, copied[par], 0));   // this half is free again
+      NCCL_TRY(R.GroupStart());
+      for (size_t m = 0; m < np; ++m) {
+        const void *src = packed ? (const void *)(sstage + m * nb) : (const void *)(psi + (off | pl.block_offset(moves[m].blk)) * ab);
+        NCCL_TRY(R.Send(src, cnt, dt, moves[m].peer, c->nccl, c->xstream));
+        NCCL_TRY(R.Recv(stage + m * nb, cnt, dt, moves[m].peer, c->nccl, c->xstream));
+      }
+      NCCL_TRY(R.GroupEnd());
+      hipEvent_t landed = c->event();
+      if (!landed) return fail(QH_ERR_HIP, "hipEventCreate failed");
+      HIP_TRY(hipEventRecord(landed, c->xstream));
+      sent[par] = landed;
+      HIP_TRY(hipStreamWaitEvent(c->cstream, landed, 0));
+      if (packed) {
+        launch_packed_round(h, pl, moves, true, stage, k, ci, c->cstream);
+      } else {
+        for (size_t m = 0; m < np; ++m)
+          HIP_TRY(hipMemcpyAsync(psi + (off | pl.block_offset(moves[m].land)) * ab, stage + m * nb, nb, hipMemcpyDeviceToDevice,
+                                 c->cstream));
+      }
+      hipEvent_t cp = c->event();
+      if (!cp) return fail(QH_ERR_HIP, "hipEventCreate failed");
+      HIP_TRY(hipEventRecord(cp, c->cstream));
+      copied[par] = cp;
+      last_copy = cp;
+      c->stats.rounds++;
+    }
+    c->arrivals.push_back(qh::Arrival{pl.slab_mask, pl.slab_vals[k], last_copy});
+  }
+  HIP_TRY(hipEventRecord(c->t1, c->cstream));
+  return QH_OK;
+}
+
 // The exchange proper.  `moves`: block value blk of the g LOGICAL local bits [base, base+g) goes to `peer`,
 // whose data lands in block value `land`.  Logical = the bit numbers the caller uses (canonical positions);
 // where those bits live now is the handle's business (relayout sweeps move them).
 int do_exchange(qh_state_s *h, const std::vector<qh::BlockMove> &moves, int base, int gbits, uint64_t chunk_amps) {
   qh::Comm *c = h->comm;
-  const int nloc = h->nloc;
-  const uint64_t ab = h->amp_bytes();
-  if (base < 0 || base + gbits > h->nglob || gbits > 8) return fail(QH_ERR_BAD_QUBIT, "exchange bits [%d,%d)", base, base + gbits);
+  if (base < 0 || base + gbits > h->nglob || gbits > qh::kMaxExchangeBits)
+    return fail(QH_ERR_BAD_QUBIT, "exchange bits [%d,%d)", base, base + gbits);
   for (int k = 0; k < gbits; ++k)
-    if (h->perm[base + k] >= nloc) return fail(QH_ERR_BAD_QUBIT, "exchange bit %d is not a local bit of this shard", base + k);
+    if (h->perm[base + k] >= h->nloc) return fail(QH_ERR_BAD_QUBIT, "exchange bit %d is not a local bit of this shard", base + k);
   if (moves.size() > (size_t)qh::kMaxXferMoves) return fail(QH_ERR_ARG, "too many peers");
   if (h->poisoned) return fail(QH_ERR_HIP, "the state of this handle is undefined (an earlier sweep or exchange failed); re-initialise it");
   const bool dry = h->dry;
@@ -2948,232 +3081,58 @@ int do_exchange(qh_state_s *h, const std::vector<qh::BlockMove> &moves, int base
     HIP_TRY(hipSetDevice(h->device));
     close_timing(c);
   }
+  const qh::ExchangeSwitches xsw = qh::ExchangeSwitches::from_env();
   // 1. the queued gates, the last sweep cut into slabs
   qh::SlabIO io;
   io.split_last = true;
   for (int k = 0; k < gbits; ++k) io.avoid |= 1ull << h->perm[base + k];   // (layout before the flush; run_fused follows the moves)
-  io.want_bits = std::max(0, std::min(env_int("QH_EXCHANGE_SLAB_BITS", qh::kMaxSlabBits), qh::kMaxSlabBits));   // (UnitPerm::slab_pos)
+  io.want_bits = xsw.slab_bits;
   c->pool_used = 0;   // (arrivals of the previous exchange are waited for by this flush)
   const uint64_t sweeps0 = h->stats.sweeps;
   int rc = flush_impl(h, &io);
   if (rc) return rc;
-  // 2. where the blocks' bits live now
-  int pos[8];
-  uint64_t blockbits = 0;
-  for (int k = 0; k < gbits; ++k) { pos[k] = h->perm[base + k]; blockbits |= 1ull << pos[k]; }
-  auto blk_off = [&](int v) {
-    uint64_t o = 0;
-    for (int k = 0; k < gbits; ++k) if ((v >> k) & 1) o |= 1ull << pos[k];
-    return o;
-  };
-  uint64_t slab_mask = io.slab_mask;
-  std::vector<uint64_t> slab_vals = io.slab_vals;
-  if (io.slab_done.empty()) {
-    slab_mask = 0;
-    if (io.want_bits > 0)   // nothing was queued (or the last sweep could not be cut): slabs still let the NEXT sweep start early
-      slab_mask = qh::pick_slab_bits(nloc, blockbits | 7ull, std::min(io.want_bits, std::max(0, nloc - gbits - 10)), 6);
-    slab_vals.clear();
-    for (int k = 0; k < (1 << qh::popc(slab_mask)); ++k) slab_vals.push_back(qh::deposit_bits((uint64_t)k, slab_mask));
-  }
-  const int K = (int)slab_vals.size();
-  hipEvent_t all_done = nullptr;
-  if (dry) {
-    io.slab_done.assign(K, nullptr);
-  } else if (io.slab_done.empty() || std::find(io.slab_done.begin(), io.slab_done.end(), nullptr) != io.slab_done.end()) {
-    all_done = c->event();
+  // 2. how the exchange is cut, in the layout the flush left (exchange_plan.h)
+  int pos[qh::kMaxExchangeBits];
+  for (int k = 0; k < gbits; ++k) pos[k] = h->perm[base + k];
+  const bool flush_cut = !io.slab_done.empty();
+  const qh::ExchangePlan pl = qh::plan_exchange(h->nloc, pos, gbits, chunk_amps, (int)moves.size(), h->amp_bytes(), xsw, io.slab_mask,
+                                                flush_cut ? &io.slab_vals : nullptr);
+  if (!dry && (!flush_cut || std::find(io.slab_done.begin(), io.slab_done.end(), nullptr) != io.slab_done.end())) {
+    hipEvent_t all_done = c->event();
     if (!all_done) return fail(QH_ERR_HIP, "hipEventCreate failed");
     HIP_TRY(hipEventRecord(all_done, h->stream));
-    io.slab_done.assign(K, all_done);
+    io.slab_done.assign(pl.slabs(), all_done);
   }
-  // 3. geometry of the rounds.  Two ways to move a round: DIRECT -- the blocks are contiguous runs of the shard,
-  // sent from where they lie and copied home from the staging area -- when the low free bits give runs of a
-  // whole chunk (or 16 MiB); PACKED -- a gather kernel packs each peer's amplitudes of the round into the staging area, a
-  // scatter kernel puts the received ones in place -- whatever the layout (after relayout sweeps the blocks'
-  // bits may sit anywhere above the 128-byte line).
-  const uint64_t free_mask = h->local_mask() & ~blockbits & ~slab_mask;
-  const int nfree = qh::popc(free_mask);
-  const int run_bits = (~free_mask) ? __builtin_ctzll(~free_mask) : 64;
-  if (!chunk_amps) chunk_amps = 1ull << 22;
-  int want_bits = 0;
-  while ((2ull << want_bits) <= chunk_amps && want_bits + 1 <= nfree) want_bits++;
-  const int force = env_int("QH_EXCHANGE_PACK", -1);      // tests: 1 = always packed, 0 = never
-  const bool packed = force >= 0 ? force != 0 : run_bits < std::min(want_bits, 20);   // direct: whole chunks, or runs of >= 16 MiB
-  const int chunk_bits = packed ? want_bits : std::min(want_bits, run_bits);
-  const uint64_t n = 1ull << chunk_bits;                       // amplitudes per peer and round
-  const uint64_t nchunks = 1ull << (nfree - chunk_bits);
-  const size_t np = moves.size();
-  if (np == 0) return QH_OK;
-  {
-    uint64_t sig = 0x9e3779b97f4a7c15ull;
-    auto mix = [&](uint64_t v) { sig ^= v + 0x9e3779b97f4a7c15ull + (sig << 6) + (sig >> 2); };
-    for (int b = 0; b < h->nglob; ++b) mix((uint64_t)h->perm[b]);
-    mix(slab_mask); mix((uint64_t)chunk_bits); mix(nchunks); mix(packed); mix((uint64_t)K); mix(blockbits); mix((uint64_t)base); mix((uint64_t)gbits);
-    for (uint64_t v : slab_vals) mix(v);
-    mix((uint64_t)np); mix((uint64_t)h->bw); mix(env_build_hash());
-    qh_xgeom &G = c->last_geom;
-    G.signature = sig;
-    G.slab_mask = slab_mask;
-    G.block_bits = blockbits;
-    G.rounds_per_slab = nchunks;
-    G.staging_bytes = (uint64_t)(packed ? 4 : 2) * np * n * ab;
-    G.slabs = (uint32_t)K;
-    G.chunk_bits = (uint32_t)chunk_bits;
-    G.packed = packed ? 1 : 0;
-    G.peers = (uint32_t)np;
-    G.sweeps_before = (uint32_t)(h->stats.sweeps - sweeps0);
-    G.last_sweep_split = io.split_done ? 1 : 0;
-    if (dry) {     // planner-only handle: the decisions are on record, the next flush sees the arrivals it would see
-      for (int k = 0; k < K; ++k) c->arrivals.push_back(qh::Arrival{slab_mask, slab_vals[k], nullptr});
-      c->stats.exchanges++;
-      c->stats.slabs += K;
-      c->stats.rounds += (uint64_t)K * nchunks;
-      c->stats.rounds_packed += packed ? (uint64_t)K * nchunks : 0;
-      c->stats.bytes_sent += (uint64_t)np * (1ull << (nloc - gbits)) * ab;
-      return QH_OK;
-    }
+  if (moves.empty()) return QH_OK;
+  const uint64_t sig = qh::exchange_signature(pl, h->perm, h->nglob, base, h->bw, env_build_hash(xsw));
+  c->last_geom = qh::exchange_record(pl, sig, (uint32_t)(h->stats.sweeps - sweeps0), io.split_done);
+  if (dry) {
+    // 3. planner-only handle: the decisions are on record, the next flush sees the arrivals it would see
+    for (uint64_t sv : pl.slab_vals) c->arrivals.push_back(qh::Arrival{pl.slab_mask, sv, nullptr});
+    c->stats.rounds += (uint64_t)pl.slabs() * pl.rounds_per_slab;
+  } else {
+    // 3. the rounds
     rc = verify_geometry(h, sig);
     if (rc) return rc;
-  }
-  char *psi = (char *)h->d_psi;
-  qh::XferGeom xg_send{}, xg_land{};
-  if (packed) {
-    qh::BitIns ins{};
-    for (int b = 0; b < nloc; ++b) if (!((free_mask >> b) & 1ull)) {
-      if (ins.n == qh::kMaxIns) return fail(QH_ERR_ARG, "exchange: more than %d block + slab bits", qh::kMaxIns);
-      ins.pos[ins.n++] = b;
-    }
-    xg_send.ins = xg_land.ins = ins;
-    xg_send.np = xg_land.np = (int)np;
-    for (size_t m = 0; m < np; ++m) { xg_send.off[m] = blk_off(moves[m].blk); xg_land.off[m] = blk_off(moves[m].land); }
-  }
-  // staging: [2 receive halves][2 send halves (packed only)] of (peers x chunk) amplitudes
-  const size_t half = np * n * ab;
-  const size_t need_stage = (packed ? 4 : 2) * half;
-  if (c->staging.cap < need_stage && (packed || !c->custom)) {
-    if (c->staging.ptr) {      // (rounds of the previous exchange may still use it)
-      HIP_TRY(hipStreamSynchronize(c->cstream));
-      HIP_TRY(hipStreamSynchronize(c->pstream));
-      HIP_TRY(hipStreamSynchronize(c->xstream));
-    }
-    HIP_TRY(c->staging.reserve(need_stage));
-  }
-  char *const staging = c->staging.as<char>();
-  auto xfer = [&](bool unpack, void *stage, uint64_t start, uint64_t sv, hipStream_t st) {
-    qh::XferGeom g = unpack ? xg_land : xg_send;
-    for (size_t m = 0; m < np; ++m) g.off[m] |= sv;
-    with_real(h, [&](auto x) { launch_xfer<typename qh::AmpT<decltype(x)>::type>(unpack, psi, stage, n, start, g, st); });
-  };
-  if (c->custom) {
-    // host-staged transport: synchronous rounds
-    const size_t need = np * n * ab;
-    HIP_TRY(c->h_send.reserve(need));
-    HIP_TRY(c->h_recv.reserve(need));
-    char *const h_send = c->h_send.as<char>(), *const h_recv = c->h_recv.as<char>();
-    std::vector<int> peers(np);
-    std::vector<void *> sp(np), rp(np);
-    for (size_t m = 0; m < np; ++m) {
-      peers[m] = moves[m].peer;
-      sp[m] = h_send + m * n * ab;
-      rp[m] = h_recv + m * n * ab;
-    }
-    for (int k = 0; k < K; ++k) {
-      const uint64_t sv = slab_vals[k];
-      HIP_TRY(hipEventSynchronize(io.slab_done[k]));
-      if (k == 0) { HIP_TRY(hipEventRecord(c->t0, c->xstream)); }
-      for (uint64_t ci = 0; ci < nchunks; ++ci) {
-        if (packed) {
-          xfer(false, staging, ci << chunk_bits, sv, c->xstream);
-          HIP_TRY(hipMemcpyAsync(h_send, staging, need, hipMemcpyDeviceToHost, c->xstream));
-        } else {
-          const uint64_t off = qh::deposit_bits(ci << chunk_bits, free_mask) | sv;
-          for (size_t m = 0; m < np; ++m)
-            HIP_TRY(hipMemcpyAsync(sp[m], psi + (off | blk_off(moves[m].blk)) * ab, n * ab, hipMemcpyDeviceToHost, c->xstream));
-        }
+    if (pl.packed && pl.nins > qh::kMaxIns) return fail(QH_ERR_ARG, "exchange: more than %d block + slab bits", qh::kMaxIns);
+    if (c->staging.cap < pl.staging_bytes && (pl.packed || !c->custom)) {   // (direct host-staged rounds copy shard <-> pinned memory)
+      if (c->staging.ptr) {      // (rounds of the previous exchange may still use it)
+        HIP_TRY(hipStreamSynchronize(c->cstream));
+        HIP_TRY(hipStreamSynchronize(c->pstream));
         HIP_TRY(hipStreamSynchronize(c->xstream));
-        if (c->custom(c->custom_user, (int)np, peers.data(), sp.data(), rp.data(), n * ab) != 0)
-          return fail(QH_ERR_COMM, "host-staged transport: the round callback failed");
-        if (packed) {
-          HIP_TRY(hipMemcpyAsync(staging, h_recv, need, hipMemcpyHostToDevice, c->xstream));
-          xfer(true, staging, ci << chunk_bits, sv, c->xstream);
-        } else {
-          const uint64_t off = qh::deposit_bits(ci << chunk_bits, free_mask) | sv;
-          for (size_t m = 0; m < np; ++m)
-            HIP_TRY(hipMemcpyAsync(psi + (off | blk_off(moves[m].land)) * ab, rp[m], n * ab, hipMemcpyHostToDevice, c->xstream));
-        }
-        HIP_TRY(hipStreamSynchronize(c->xstream));
-        c->stats.rounds++;
       }
-      hipEvent_t ev = c->event();
-      if (!ev) return fail(QH_ERR_HIP, "hipEventCreate failed");
-      HIP_TRY(hipEventRecord(ev, c->xstream));
-      c->arrivals.push_back(qh::Arrival{slab_mask, sv, ev});
+      HIP_TRY(c->staging.reserve(pl.staging_bytes));
     }
-    HIP_TRY(hipEventRecord(c->t1, c->xstream));
-  } else {
-    // RCCL: grouped send/recv per round on xstream, landing (copies / scatter kernel) on cstream, packing on pstream
-    if (!c->nccl) return fail(QH_ERR_COMM, "no communicator (qh_comm_init)");
-    const ncclDataType_t dt = h->bw == 128 ? ncclDouble : ncclFloat;
-    const size_t cnt = (size_t)n * 2;
-    auto &R = qh::rccl();
-    hipEvent_t copied[2] = {nullptr, nullptr};   // receive half free again
-    hipEvent_t sent[2] = {nullptr, nullptr};     // send half free again (packed)
-    uint64_t round = 0;
-    for (int k = 0; k < K; ++k) {
-      const uint64_t sv = slab_vals[k];
-      HIP_TRY(hipStreamWaitEvent(packed ? c->pstream : c->xstream, io.slab_done[k], 0));
-      if (k == 0) { HIP_TRY(hipEventRecord(c->t0, packed ? c->pstream : c->xstream)); }
-      hipEvent_t last_copy = nullptr;
-      for (uint64_t ci = 0; ci < nchunks; ++ci, ++round) {
-        const int par = (int)(round & 1);
-        const uint64_t off = qh::deposit_bits(ci << chunk_bits, free_mask) | sv;
-        char *stage = staging + par * half;
-        char *sstage = staging + (2 + par) * half;
-        if (packed) {
-          if (sent[par]) HIP_TRY(hipStreamWaitEvent(c->pstream, sent[par], 0));
-          xfer(false, sstage, ci << chunk_bits, sv, c->pstream);
-          hipEvent_t pk = c->event();
-          if (!pk) return fail(QH_ERR_HIP, "hipEventCreate failed");
-          HIP_TRY(hipEventRecord(pk, c->pstream));
-          HIP_TRY(hipStreamWaitEvent(c->xstream, pk, 0));
-        }
-        if (copied[par]) HIP_TRY(hipStreamWaitEvent(c->xstream, copied[par], 0));   // this half is free again
-        NCCL_TRY(R.GroupStart());
-        for (size_t m = 0; m < np; ++m) {
-          const void *src = packed ? (const void *)(sstage + m * n * ab) : (const void *)(psi + (off | blk_off(moves[m].blk)) * ab);
-          NCCL_TRY(R.Send(src, cnt, dt, moves[m].peer, c->nccl, c->xstream));
-          NCCL_TRY(R.Recv(stage + m * n * ab, cnt, dt, moves[m].peer, c->nccl, c->xstream));
-        }
-        NCCL_TRY(R.GroupEnd());
-        hipEvent_t landed = c->event();
-        if (!landed) return fail(QH_ERR_HIP, "hipEventCreate failed");
-        HIP_TRY(hipEventRecord(landed, c->xstream));
-        sent[par] = landed;
-        HIP_TRY(hipStreamWaitEvent(c->cstream, landed, 0));
-        if (packed) {
-          xfer(true, stage, ci << chunk_bits, sv, c->cstream);
-        } else {
-          for (size_t m = 0; m < np; ++m)
-            HIP_TRY(hipMemcpyAsync(psi + (off | blk_off(moves[m].land)) * ab, stage + m * n * ab, n * ab,
-                                   hipMemcpyDeviceToDevice, c->cstream));
-        }
-        hipEvent_t cp = c->event();
-        if (!cp) return fail(QH_ERR_HIP, "hipEventCreate failed");
-        HIP_TRY(hipEventRecord(cp, c->cstream));
-        copied[par] = cp;
-        last_copy = cp;
-        c->stats.rounds++;
-      }
-      c->arrivals.push_back(qh::Arrival{slab_mask, sv, last_copy});
-    }
-    HIP_TRY(hipEventRecord(c->t1, c->cstream));
+    rc = c->custom ? run_rounds_host_staged(h, pl, moves, io.slab_done) : run_rounds_rccl(h, pl, moves, io.slab_done);
+    if (rc) return rc;
+    rc = check_launch(h);
+    if (rc) return rc;
+    c->timing_open = true;
   }
-  rc = check_launch(h);
-  if (rc) return rc;
-  c->timing_open = true;
   c->stats.exchanges++;
-  c->stats.slabs += K;
-  c->stats.rounds_packed += packed ? (uint64_t)K * nchunks : 0;
-  c->stats.bytes_sent += (uint64_t)np * (1ull << (nloc - gbits)) * ab;
+  c->stats.slabs += pl.slabs();
+  c->stats.rounds_packed += pl.packed ? (uint64_t)pl.slabs() * pl.rounds_per_slab : 0;
+  c->stats.bytes_sent += (uint64_t)pl.np * (1ull << (h->nloc - gbits)) * pl.amp_bytes;
   return QH_OK;
 }
 
@@ -3233,9 +3192,7 @@ int qh_comm_init_custom(qh_handle h, int nranks, int rank, qh_round_fn fn, void 
 int qh_comm_init_dry(qh_handle h, int nranks, int rank) {
   if (!h || !h->dry) return fail(QH_ERR_ARG, "qh_comm_init_dry is for planner-only handles (qh_create_dry)");
   if (h->comm) return fail(QH_ERR_ARG, "handle already has a communicator");
-  if (nranks < 1 || (nranks & (nranks - 1)) || rank < 0 || rank >= nranks)
-    return fail(QH_ERR_ARG, "nranks %d must be a power of two, rank %d inside it", nranks, rank);
-  if (nranks > qh::kMaxXferMoves + 1) return fail(QH_ERR_ARG, "at most %d ranks", qh::kMaxXferMoves + 1);
+  if (int rc = check_ranks(nranks, rank)) return rc;
   auto *c = new qh::Comm;
   c->nranks = nranks;
   c->rank = rank;

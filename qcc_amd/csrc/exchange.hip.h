@@ -31,16 +31,17 @@
 #include <vector>
 
 #include "buffers.hip.h"
+#include "exchange_plan.h"
 #include "kernels_gate.hip.h"
 
 namespace qh {
 
-// PACKED rounds (engine.hip, do_exchange): when the blocks' index bits do not leave long contiguous runs --
+// PACKED rounds (exchange_plan.h): when the blocks' index bits do not leave long contiguous runs --
 // relayout sweeps move index bits around -- a gather kernel packs the amplitudes of one round into the staging
 // area, peer after peer, and a scatter kernel puts the received ones in place.  Work item i = (peer slot m,
 // amplitude j of the round): index = the round's counter with zeros inserted at the block and slab bits
 // (`ins`), plus the peer's block value and the slab value (`off[m]`).  HBM-bound: n x 16 B read + written.
-constexpr int kMaxXferMoves = 63;
+static_assert(kExchangeMaxIns == kMaxIns, "exchange_plan.h / kernels disagree on inserted bits");
 struct XferGeom {
   BitIns ins;
   int np;
@@ -164,28 +165,5 @@ struct Comm {
     return pool[pool_used++];
   }
 };
-
-// The blocks one exchange moves: block value `blk` of the g bits at `base` goes to `peer`, and
-// that peer's data lands in block value `land` (== blk except in the loop-back self test).
-struct BlockMove { int peer, blk, land; };
-
-// Picks up to `want` slab bits: the highest local bits outside `avoid`.
-inline uint64_t pick_slab_bits(int nloc, uint64_t avoid, int want, int min_bit) {
-  uint64_t m = 0;
-  for (int b = nloc - 1; b >= min_bit && want > 0; --b)
-    if (!((avoid >> b) & 1ull)) { m |= 1ull << b; --want; }
-  return m;
-}
-
-// deposit the low bits of v into the set bits of mask (ascending)
-inline uint64_t deposit_bits(uint64_t v, uint64_t mask) {
-  uint64_t out = 0;
-  for (uint64_t m = mask; m; m &= m - 1) {
-    const int b = __builtin_ctzll(m);
-    out |= (v & 1ull) << b;
-    v >>= 1;
-  }
-  return out;
-}
 
 }  // namespace qh

@@ -152,6 +152,35 @@ def test_loopback_exchange_at_shard_size(monkeypatch, relayout, pack, capsys):
     assert xs['rounds_packed'] == xs['rounds']
 
 
+@pytest.mark.parametrize('bw', [128, 64])
+def test_real_and_planner_only_handles_record_the_same_geometry(bw):
+  """Both kinds of handle cut an exchange by one planning function (exchange_plan.h): given the same circuit and the same
+  loop-back, a handle that moves data (host-staged, one rank) and a planner-only one record the same qh_xgeom, field by
+  field -- what ties the 36-qubit planner-only checks of tests/test_exchange_geometry_cpu.py to what a device does."""
+  n, bit, chunk = 20, 17, 1 << 12
+  a_ops, a_g = _circuit(n, 100 + bit, 40)
+  q_ops, q_g = workloads.qft_stream(range(n)).arrays()
+  recs = {}
+  for dry in (False, True):
+    with device.DeviceState(n, bw, fusion=native.QH_FUSE_SWEEP, dry=dry) as st:
+      if not dry:
+        st.init_basis(5)
+      st.run_stream(a_ops, a_g)
+      st.flush()
+      if dry:
+        st.comm_init_dry(1, 0)
+      else:
+        st.comm_init_custom(1, 0, _self_round)
+      st.run_stream(q_ops, q_g)          # left queued: the exchange plans it
+      st.exchange_loopback(bit, chunk)
+      recs[dry] = st.exchange_geometry()
+      if not dry:
+        st.sync()
+  assert recs[False]['signature'] != 0 and recs[False]['peers'] == 2 and recs[False]['sweeps_before'] >= 1
+  for field, value in recs[False].items():
+    assert recs[True][field] == value, (field, recs)
+
+
 def test_exchange_needs_a_communicator():
   with device.DeviceState(12, 128, fusion=native.QH_FUSE_SWEEP) as st:
     with pytest.raises(native.QhError):
