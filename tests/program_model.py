@@ -1,0 +1,1740 @@
+"""TEST-ONLY: random PROGRAMS over the whole device API (include/qcc_hip.h) and a NumPy model of them.  Host only.
+
+  gen_program(seed, bw, mode)   a deterministic list of steps (dicts) that interleaves queued gate bursts, barrier mutators,
+                                readers, handle steps, two-state steps and layout steps on a pool of handles
+  ModelState                    every step in plain NumPy on one complex128 vector per handle, in LOGICAL order
+  run_program(program, make_state, check)   drives any object with qcc_amd.device.DeviceState's interface through a program
+                                and compares every step with the model; the only place that compares
+  NumpyDevice                   a stand-in with DeviceState's interface (physical array + bit map + queue per handle) that
+                                re-lays its local bits out at a flush of >= 14 local bits, as relayout sweeps do
+
+A handle of a SHARD (qh_set_shard) is modelled as a vector of the GLOBAL size that is zero outside the indices the shard
+holds: gates on local bits, controls / diagonals / selectors / z masks on held bits and every per-shard reader then are the
+plain operation on that vector.  Bits are LOGICAL everywhere; a step never names a physical position (remap_swap names the
+two logical bits whose positions are exchanged, the runner looks the positions up).
+
+References are imported, not copied: tests/oracle_lib (gates), fake_device.np_marginal / np_keep, resize_util.np_extend /
+np_release, select_util.np_select / np_topk / fma_probs, test_dense_cpu.dense_reference, test_mux_cpu.mux_reference_fast /
+diag_reference, test_expect_cpu.np_expect, shard_util.check_exact_cdf (the inverse CDF of qh_sample in physical order)."""
+import os
+import sys
+
+import numpy as np
+
+from qcc_amd import native
+from tests import oracle_lib, shard_util
+from tests.fake_device import np_keep, np_marginal
+from tests.resize_util import np_extend, np_release
+from tests.select_util import fma_probs, np_select, np_topk
+from tests.test_dense_cpu import dense_reference
+from tests.test_expect_cpu import np_expect
+from tests.test_mux_cpu import diag_reference, mux_reference_fast
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools'))
+import fuzz_parity  # noqa: E402  (the gate pools and the control-density logic of the gate fuzzer)
+
+NLOCS = (3, 6, 8, 9, 12, 14, 15, 16, 17)
+SWEEPS_FROM = 8               # fused sweeps (and with them relayout) exist from 8 local bits on (sweep_supported)
+PERMUTED_FROM = 14            # tests/test_gpu_shard_readout.py: relayout sweeps permute local bits from here on
+MAX_BITS = 20                 # the largest state of a program: 2^20 amplitudes
+MAX_LIVE = 4
+LINEAR, TILES, GATHER = native.QH_INNER_LINEAR, native.QH_INNER_TILES, native.QH_INNER_GATHER
+
+BARRIERS = ('matrix', 'mux', 'diag', 'scale', 'project_bit', 'project_bits')
+READERS = ('norm2', 'prob_bit', 'marginal', 'sample', 'expect', 'argmax', 'amplitude', 'amplitudes', 'select', 'topk')
+HANDLE_STEPS = ('clone', 'copy', 'extend', 'release', 'close')
+TWO_STATE = ('inner', 'axpby')
+LAYOUT_STEPS = ('flush', 'set_relayout', 'remap')
+KINDS = ('gates',) + BARRIERS + READERS + HANDLE_STEPS + TWO_STATE + LAYOUT_STEPS + ('refused',)
+
+
+# the fixed programs of the suite (tests/test_program_fuzz_cpu.py on NumpyDevice, tests/test_gpu_program_fuzz.py on the GPU),
+# each at both widths; the coverage table of the CPU test is what this seed list was chosen by
+FIXED = [('own', seed) for seed in list(range(21)) + [42, 48, 139]] + [('shard', seed) for seed in range(6)] + \
+        [('attached', seed) for seed in range(4)] + [('mapped', seed) for seed in range(4)]
+# planner variants of tests/test_gpu_fuzz.py, each on 'own' programs whose first handle is large enough for sweeps
+ENV_VARIANTS = [{'QH_RELAYOUT': '0'}, {'QH_WAVE_BITS': '2', 'QH_LANE_VALU': '2'}, {'QH_SEATS': '2', 'QH_WAVE_BITS': '1'}]
+
+
+# ---- tolerances: the constants of the operations' own GPU test files ------------------------------------------------------
+def amp_tol(bw):
+  """amplitudes: _amp_tol of tests/test_gpu_shard_readout.py"""
+  return 1e-12 if bw == 128 else 5e-6
+
+
+def close(got, want, bw):
+  """sums of probabilities: _close of tests/test_gpu_shard_readout.py; returns the message of a miss or None"""
+  got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+  err = float(np.max(np.abs(got - want))) if got.size else 0.0
+  lim = 1e-12 if bw == 128 else 1e-6 * max(float(np.max(want)) if want.size else 0.0, 1e-30) + 1e-9
+  return None if err <= lim else f'off by {err:.3e} (limit {lim:.3e})'
+
+
+TOL = 1e-12                   # TOL of tests/test_gpu_inner.py: readers that accumulate in double from the stored amplitudes
+CHAIN_TOL_128 = 2e-11         # tools/fuzz_parity.py, complex128
+
+
+_ORACLE = []
+
+
+def _oracle():
+  if not _ORACLE:
+    _ORACLE.append(oracle_lib.load())
+  return _ORACLE[0]
+
+
+def apply_gate(vec, n, ctl_mask, tgt, g):
+  """one qh_apply_bits gate on a vector of 2^n amplitudes in logical order, in place, in the vector's own precision"""
+  orc = _oracle()
+  ctl = [b for b in range(n) if (ctl_mask >> b) & 1]
+  gq = np.asarray(g, dtype=vec.dtype).reshape(4)
+  if not ctl:
+    orc.apply1(vec, gq, n, n - 1 - tgt)
+  elif len(ctl) == 1:
+    orc.applyc(vec, gq, n, n - 1 - ctl[0], n - 1 - tgt)
+  else:                                           # (as tools/fuzz_parity.py: the gate where every control is 1)
+    idx = np.arange(1 << n, dtype=np.uint64)
+    on = (idx & np.uint64(ctl_mask)) == np.uint64(ctl_mask)
+    tmp = vec.copy()
+    orc.apply1(tmp, gq, n, n - 1 - tgt)
+    vec[on] = tmp[on]
+
+
+def swap_logical_bits(vec, n, a, b):
+  if a == b:
+    return vec.copy()
+  return np.ascontiguousarray(np.swapaxes(vec.reshape([2] * n), n - 1 - a, n - 1 - b)).reshape(-1)
+
+
+def held_mask_value(held):
+  return sum(1 << b for b in held), sum(v << b for b, v in held.items())
+
+
+def mine_of(n, held):
+  """the global logical indices a shard holds, ascending"""
+  mask, value = held_mask_value(held)
+  return np.flatnonzero(np_keep(1 << n, mask, value)).astype(np.uint64)
+
+
+def axpby_ref(d, alpha, s, beta):
+  """alpha * d + beta * s as qh_axpby defines it: a coefficient that is exactly 0 leaves its state unread"""
+  alpha, beta = complex(alpha), complex(beta)
+  out = np.zeros_like(d)
+  if alpha != 0:
+    out = out + alpha * d
+  if beta != 0:
+    out = out + beta * s
+  return out
+
+
+def init_vector(s):
+  """the GLOBAL state an 'init' step describes, complex128, logical order"""
+  n = s['nloc'] + s['g']
+  if s['how'] == 'basis':
+    v = np.zeros(1 << n, dtype=np.complex128)
+    v[s['index']] = 1
+  elif s['how'] == 'product':
+    v = np.ones(1, dtype=np.complex128)
+    for k, x in s['factors']:
+      if isinstance(x, (int, np.integer)):
+        t = np.zeros(1 << k, dtype=np.complex128)
+        t[int(x)] = 1
+      else:
+        t = np.asarray(x, dtype=np.complex128)
+      v = np.kron(v, t)
+  else:
+    rng = np.random.default_rng(s['seed'])
+    v = rng.standard_normal(1 << n) + 1j * rng.standard_normal(1 << n)
+    v /= np.linalg.norm(v)
+  return v
+
+
+def init_bitmap(s):
+  """physical position of every logical bit after the initial remap_swaps of a shard program"""
+  bm = list(range(s['nloc'] + s['g']))
+  for a, b in s['swaps']:
+    la, lb = bm.index(a), bm.index(b)
+    bm[la], bm[lb] = bm[lb], bm[la]
+  return bm
+
+
+class ModelState:
+  """Every live handle as one vector in logical order.  A burst of gates is applied at once but remembered as queued: the
+  vector BEFORE the burst is kept, so that a step that DROPS the queue (copy_from on the destination) finds it."""
+
+  def __init__(self, dtype=np.complex128):
+    self.dtype = dtype
+    self.v, self.base, self.q, self.n, self.held = {}, {}, {}, {}, {}
+    # relayout mode as include/qcc_hip.h describes it: -1 undecided (decided by the first fused flush), 0 off, 1 on; and
+    # whether the handle owns HBM memory (attached and host-mapped ones do not: they never re-lay out)
+    self.mode, self.owns = {}, {}
+
+  def _rnd(self, x):
+    return np.ascontiguousarray(x, dtype=np.complex128).astype(self.dtype) if self.dtype != np.complex128 else np.ascontiguousarray(x, dtype=np.complex128)
+
+  def wide(self, h):
+    return self.v[h].astype(np.complex128)
+
+  def put(self, h, vec, n=None, held=None):
+    self.v[h] = self.base[h] = self._rnd(vec)
+    self.q[h] = 0
+    if n is not None:
+      self.n[h], self.held[h] = n, dict(held)
+      self.mode[h], self.owns[h] = -1, True                # a new handle: undecided, memory of its own
+
+  def eligible(self, h):
+    """relayout_eligible of the engine: QH_RELAYOUT (read when asked), memory of its own, a size that has sweeps"""
+    return bool(self.owns[h] and int(os.environ.get('QH_RELAYOUT', '1')) != 0 and self.nloc(h) >= SWEEPS_FROM)
+
+  def wanted(self, h):
+    """would a flush of this handle re-lay it out (relayout_wanted of the engine)"""
+    return self.eligible(h) if self.mode[h] < 0 else self.mode[h] == 1
+
+  def run(self, h):
+    if self.q[h] and self.mode[h] < 0 and self.nloc(h) >= SWEEPS_FROM:
+      self.mode[h] = int(self.eligible(h))                 # the first fused flush decides
+    self.base[h] = self.v[h]
+    self.q[h] = 0
+
+  def queued(self, h, ahead, count):
+    """a burst of `count` gates was queued: `ahead` is the state with it applied, the state before it is kept"""
+    if self.q[h] == 0:
+      self.base[h] = self.v[h]
+    self.v[h] = ahead
+    self.q[h] += count
+
+  def drop(self, h):
+    self.v[h] = self.base[h]
+    self.q[h] = 0
+
+  def nloc(self, h):
+    return self.n[h] - len(self.held[h])
+
+  def local_bits(self, h):
+    return [b for b in range(self.n[h]) if b not in self.held[h]]
+
+  def norm(self, h):
+    w = self.wide(h)
+    return float(np.vdot(w, w).real)
+
+  def step(self, s):
+    return getattr(self, '_' + s['op'])(s)
+
+  # -- start ------------------------------------------------------------------------------------------------------------------
+  def _init(self, s):
+    n, nloc = s['nloc'] + s['g'], s['nloc']
+    psi, bm = init_vector(s), init_bitmap(s)
+    for shard, h in enumerate(s['slots']):
+      held = {b: (shard >> (bm[b] - nloc)) & 1 for b in range(n) if bm[b] >= nloc}
+      mask, value = held_mask_value(held)
+      self.put(h, np.where(np_keep(1 << n, mask, value), psi, 0), n, held)
+      if s['mode'] in ('attached', 'mapped'):
+        self.mode[h], self.owns[h] = 0, False
+
+  # -- gates --------------------------------------------------------------------------------------------------------------------
+  def _gates(self, s):
+    h = s['h']
+    ahead = self.v[h].copy()
+    for cm, t, g in s['gates']:
+      apply_gate(ahead, self.n[h], cm, t, g)
+    self.queued(h, ahead, len(s['gates']))
+
+  def _mut(self, h, fn):
+    self.run(h)
+    self.put(h, fn(self.wide(h)))
+
+  def _matrix(self, s):
+    self._mut(s['h'], lambda v: dense_reference(v, self.n[s['h']], s['m'], s['bits'], s['ctl']))
+
+  def _mux(self, s):
+    self._mut(s['h'], lambda v: mux_reference_fast(v, self.n[s['h']], s['gates'], s['sel'], s['tgt']))
+
+  def _diag(self, s):
+    self._mut(s['h'], lambda v: diag_reference(v, self.n[s['h']], s['values'], s['bits']))
+
+  def _scale(self, s):
+    self._mut(s['h'], lambda v: v * complex(s['z']))
+
+  def _project_bit(self, s):
+    self._mut(s['h'], lambda v: np.where(np_keep(v.size, 1 << s['bit'], s['value'] << s['bit']), v, 0))
+
+  def _project_bits(self, s):
+    self._mut(s['h'], lambda v: np.where(np_keep(v.size, s['mask'], s['value']), v, 0))
+
+  # -- readers ------------------------------------------------------------------------------------------------------------------
+  def _norm2(self, s):
+    self.run(s['h'])
+    return self.norm(s['h'])
+
+  def _prob_bit(self, s):
+    self.run(s['h'])
+    w = self.wide(s['h'])
+    sel = np_keep(w.size, 1 << s['bit'], s['value'] << s['bit'])
+    return float(np.vdot(w[sel], w[sel]).real)
+
+  def _marginal(self, s):
+    self.run(s['h'])
+    return np_marginal(self.wide(s['h']), s['bits'])
+
+  def _sample(self, s):
+    self.run(s['h'])              # (the answer depends on the physical order: the runner checks it there)
+
+  def _expect(self, s):
+    self.run(s['h'])
+    w = self.wide(s['h'])
+    return np.array([np_expect(w, x, z) for x, z in zip(s['x'], s['z'])], dtype=np.float64)
+
+  def _probs(self, h):
+    mine = mine_of(self.n[h], self.held[h])
+    a = self.wide(h)[mine.astype(np.int64)]
+    return mine, a, fma_probs(a)
+
+  def _argmax(self, s):
+    self.run(s['h'])
+    mine, _, p = self._probs(s['h'])
+    k = int(np.argmax(p))
+    return int(mine[k]), float(p[k])
+
+  def _amplitude(self, s):
+    self.run(s['h'])
+    return complex(self.wide(s['h'])[s['index']])
+
+  def _amplitudes(self, s):
+    self.run(s['h'])
+    return self.wide(s['h'])[np.asarray(s['indices'], dtype=np.int64)]
+
+  def _select(self, s):
+    self.run(s['h'])
+    mine, a, p = self._probs(s['h'])
+    idx, amp, w = np_select(a, s['threshold'], probs=p)
+    return mine[idx.astype(np.int64)], amp, int(idx.size), w
+
+  def _topk(self, s):
+    self.run(s['h'])
+    mine, a, p = self._probs(s['h'])
+    idx, amp = np_topk(a, s['k'], probs=p)
+    return mine[idx.astype(np.int64)], amp
+
+  # -- handles ------------------------------------------------------------------------------------------------------------------
+  def _clone(self, s):
+    self.run(s['h'])
+    self.put(s['new'], self.v[s['h']].copy(), self.n[s['h']], self.held[s['h']])
+
+  def _copy(self, s):
+    self.run(s['src'])
+    self.drop(s['h'])
+    self.put(s['h'], self.v[s['src']].copy())
+
+  def _extend(self, s):
+    h, k = s['h'], s['k']
+    self.run(h)
+    if s['amps'] is None:
+      f = np.zeros(1 << k, dtype=np.complex128)
+      f[s['basis']] = 1
+    else:
+      f = np.asarray(s['amps'], dtype=np.complex128)
+    self.put(s['new'], np_extend(self.wide(h), f), self.n[h] + k, {b + k: v for b, v in self.held[h].items()})
+
+  def _release(self, s):
+    h, bits = s['h'], s['bits']
+    self.run(h)
+    small, kept, dropped = np_release(self.wide(h), bits, s['value'])
+    held = {b - sum(1 for x in bits if x < b): v for b, v in self.held[h].items()}
+    self.put(s['new'], small, self.n[h] - len(bits), held)
+    return kept, dropped
+
+  def _close(self, s):
+    for d in (self.v, self.base, self.q, self.n, self.held, self.mode, self.owns):
+      d.pop(s['h'])
+
+  # -- two states ----------------------------------------------------------------------------------------------------------------
+  def _inner(self, s):
+    self.run(s['h'])
+    self.run(s['other'])
+    return complex(np.vdot(self.wide(s['h']), self.wide(s['other'])))
+
+  def _axpby(self, s):
+    h = s['h']
+    self.run(h)
+    self.run(s['other'])
+    self.put(h, axpby_ref(self.wide(h), s['alpha'], self.wide(s['other']), s['beta']))
+    return self.norm(h)
+
+  # -- layout -------------------------------------------------------------------------------------------------------------------
+  def _flush(self, s):
+    self.run(s['h'])
+
+  def _set_relayout(self, s):
+    h = s['h']
+    if not s['on']:
+      self.run(h)
+      self.mode[h] = 0
+    elif self.mode[h] != 1:
+      self.mode[h] = int(self.eligible(h))
+    return self.mode[h] == 1
+
+  def _remap(self, s):
+    h = s['h']
+    self.run(h)
+    self.put(h, swap_logical_bits(self.v[h], self.n[h], s['a'], s['b']))
+
+  def _refused(self, s):
+    pass
+
+
+# ---- the generator ------------------------------------------------------------------------------------------------------------
+def _rand_op(rng, k, unitary):
+  a = rng.standard_normal((1 << k, 1 << k)) + 1j * rng.standard_normal((1 << k, 1 << k))
+  if unitary:
+    a, _ = np.linalg.qr(a)
+  else:
+    a /= np.linalg.norm(a, 2)
+  return a
+
+
+def _rand_table(rng, k):
+  t = rng.standard_normal(1 << k) + 1j * rng.standard_normal(1 << k)
+  return t / np.linalg.norm(t)
+
+
+class _Gen:
+  def __init__(self, seed, bw, mode):
+    self.rng = np.random.default_rng([int(seed), bw, ('own', 'attached', 'mapped', 'shard').index(mode)])
+    self.bw, self.mode = bw, mode
+    self.m = ModelState()
+    self.steps = []
+    self.next_slot = 0
+    self.refused = 0
+
+  def live(self):
+    return sorted(self.m.v)
+
+  def emit(self, s):
+    self.steps.append(s)
+    out = self.m.step(s)
+    if s['op'] in ('gates', 'close', 'refused', 'init') or s.get('poison'):
+      return out
+    for h in [x for x in (s.get('new'), s.get('h')) if x is not None and x in self.m.v]:
+      nv = self.m.norm(h)
+      if self.m.q[h] == 0 and np.isfinite(nv) and nv > 0 and not 0.25 <= nv <= 4:      # norm control
+        z = {'op': 'scale', 'h': h, 'z': complex(1 / np.sqrt(nv))}
+        self.steps.append(z)
+        self.m.step(z)
+    return out
+
+  def start(self):
+    rng, mode = self.rng, self.mode
+    g = int(rng.integers(1, 3)) if mode == 'shard' else 0
+    pool = [x for x in NLOCS if (mode != 'mapped' or x <= 12) and x + g <= MAX_BITS - 1]
+    nloc = int(pool[int(rng.integers(len(pool)))])
+    n = nloc + g
+    swaps = []
+    if g and rng.random() < 0.5:                       # 'mid3' / 'midhalf' of tests/test_gpu_shard_readout.py
+      swaps = [(nloc, 3 if nloc > 3 else 1)] if rng.random() < 0.5 else [(nloc + k, nloc // 2 - k) for k in range(g)]
+    s = {'op': 'init', 'bw': self.bw, 'mode': mode, 'nloc': nloc, 'g': g, 'swaps': swaps, 'slots': list(range(1 << g))}
+    how = ('basis', 'product', 'upload')[int(rng.integers(3))]
+    s['how'] = how
+    if how == 'basis':
+      s['index'] = int(rng.integers(1 << n))
+    elif how == 'product':
+      fac, left = [], n
+      while left:
+        k = int(min(left, rng.integers(1, 5)))
+        r = rng.random()
+        fac.append((k, int(rng.integers(1 << k)) if r < 0.3 else (np.full(1 << k, 2.0 ** (-k / 2), dtype=np.complex128) if r < 0.6
+                                                                else _rand_table(rng, k))))
+        left -= k
+      s['factors'] = fac
+    else:
+      s['seed'] = int(rng.integers(1 << 30))
+    self.next_slot = 1 << g
+    self.max_live = MAX_LIVE + (1 << g) - 1
+    self.emit(s)
+
+  def new_slot(self):
+    self.next_slot += 1
+    return self.next_slot - 1
+
+  # -- one step of every kind; each returns False where the pool offers no valid instance -------------------------------------
+  def pick(self, cond=lambda h: True):
+    c = [h for h in self.live() if cond(h)]
+    return c[int(self.rng.integers(len(c)))] if c else None
+
+  def partner(self, h):
+    """another live handle of the same shape and shard index"""
+    m = self.m
+    c = [x for x in self.live() if x != h and m.n[x] == m.n[h] and m.held[x] == m.held[h]]
+    return c[int(self.rng.integers(len(c)))] if c else None
+
+  def usable(self, h):
+    nv = self.m.norm(h)
+    return np.isfinite(nv) and nv > 0
+
+  def k_gates(self):
+    rng, m = self.rng, self.m
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    n, loc = m.n[h], m.local_bits(h)
+    w = rng.dirichlet([1, 1, 1, 1])
+    pctl, pmulti = rng.uniform(0, 0.8), rng.uniform(0, 0.3)
+    focus = rng.random() < 0.4
+    hot = rng.choice(n, size=max(2, n // 3), replace=False)
+    bf, diag, real, gen = fuzz_parity.pools(rng)
+    want = int(rng.integers(5, 41))
+    trial = m.v[h].copy()
+    out = []
+    for _ in range(4 * want):
+      if len(out) == want:
+        break
+      kind = int(rng.choice(4, p=w))
+      pool = [bf, diag, real, gen][kind]
+      g = np.asarray(pool[int(rng.integers(len(pool)))], dtype=np.complex128).reshape(4)
+      t = int(rng.choice(hot)) if focus and rng.random() < 0.8 else int(rng.integers(n))
+      if t not in loc and not (g[1] == 0 and g[2] == 0):
+        t = loc[t % len(loc)]                              # dense gates stay on local bits
+      cm = 0
+      if rng.random() < pctl:
+        k = 1 + (int(rng.integers(1, 4)) if rng.random() < pmulti else 0)
+        others = [q for q in range(n) if q != t]
+        for c in rng.choice(others, size=min(k, len(others)), replace=False):
+          cm |= 1 << int(c)
+      g2 = g.reshape(2, 2)
+      if np.allclose(g2.conj().T @ g2, np.eye(2), rtol=0, atol=1e-12):
+        apply_gate(trial, n, cm, t, g)                     # unitary: the norm stays where it is
+      else:
+        nxt = trial.copy()
+        apply_gate(nxt, n, cm, t, g)
+        nv = float(np.vdot(nxt, nxt).real)
+        if not 0.25 <= nv <= 4:                            # a non-unitary operator that would take the norm out of range
+          continue
+        trial = nxt
+      out.append((cm, t, g))
+    if len(out) < 5:
+      return False
+    self.steps.append({'op': 'gates', 'h': h, 'gates': out})
+    m.queued(h, trial, len(out))                           # (what ModelState._gates computes, without applying the burst twice)
+    return True
+
+  def k_matrix(self):
+    rng, m = self.rng, self.m
+    h = self.pick(self.usable)
+    loc = m.local_bits(h) if h is not None else []
+    if not loc:
+      return False
+    k = int(rng.integers(1, min(6, len(loc)) + 1))
+    bits = [int(b) for b in rng.choice(loc, size=k, replace=False)]
+    ctl = 0
+    others = [b for b in range(m.n[h]) if b not in bits]
+    if others and rng.random() < 0.5:
+      for c in rng.choice(others, size=min(len(others), int(rng.integers(1, 4))), replace=False):
+        ctl |= 1 << int(c)
+    self.emit({'op': 'matrix', 'h': h, 'bits': bits, 'ctl': ctl, 'm': _rand_op(rng, k, rng.random() < 0.7)})
+    return True
+
+  def k_mux(self):
+    rng, m = self.rng, self.m
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    loc, n = m.local_bits(h), m.n[h]
+    tgt = int(loc[int(rng.integers(len(loc)))])
+    k = int(rng.integers(0, min(10, len(loc) - 1) + 1))
+    sel = [int(b) for b in rng.choice([b for b in range(n) if b != tgt], size=k, replace=False)]
+    gs = np.stack([_rand_op(rng, 1, rng.random() < 0.8) for _ in range(1 << k)])
+    self.emit({'op': 'mux', 'h': h, 'sel': sel, 'tgt': tgt, 'gates': gs})
+    return True
+
+  def k_diag(self):
+    rng, m = self.rng, self.m
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    n = m.n[h]
+    k = int(rng.integers(0, min(12, m.nloc(h)) + 1))
+    bits = [int(b) for b in rng.choice(n, size=k, replace=False)]
+    vals = np.exp(1j * rng.uniform(0, 6.28, 1 << k)) * (rng.uniform(0.8, 1.25, 1 << k) if rng.random() < 0.3 else 1.0)
+    self.emit({'op': 'diag', 'h': h, 'bits': bits, 'values': vals})
+    return True
+
+  def k_scale(self):
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    self.emit({'op': 'scale', 'h': h, 'z': complex(self.rng.uniform(0.8, 1.25) * np.exp(1j * self.rng.uniform(0, 6.28)))})
+    return True
+
+  def _renorm(self, h):
+    nv = self.m.norm(h)
+    self.emit({'op': 'scale', 'h': h, 'z': complex(1 / np.sqrt(nv))})
+
+  def k_project_bit(self):
+    rng, m = self.rng, self.m
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    bit, value = int(rng.integers(m.n[h])), int(rng.integers(2))
+    if m._prob_bit({'h': h, 'bit': bit, 'value': value}) < 1e-3 * m.norm(h):
+      value ^= 1
+    self.emit({'op': 'project_bit', 'h': h, 'bit': bit, 'value': value})
+    self._renorm(h)
+    return True
+
+  def k_project_bits(self):
+    rng, m = self.rng, self.m
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    n = m.n[h]
+    bits = [int(b) for b in rng.choice(n, size=int(rng.integers(1, min(4, n) + 1)), replace=False)]
+    p = m._marginal({'h': h, 'bits': bits})
+    j = int(rng.choice(np.flatnonzero(p >= 0.5 * p.max())))
+    mask = sum(1 << b for b in bits)
+    value = sum(((j >> t) & 1) << b for t, b in enumerate(bits))
+    self.emit({'op': 'project_bits', 'h': h, 'mask': mask, 'value': value})
+    self._renorm(h)
+    return True
+
+  def k_norm2(self):
+    h = self.pick()
+    self.emit({'op': 'norm2', 'h': h})
+    return True
+
+  def k_prob_bit(self):
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    self.emit({'op': 'prob_bit', 'h': h, 'bit': int(self.rng.integers(self.m.n[h])), 'value': int(self.rng.integers(2))})
+    return True
+
+  def k_marginal(self):
+    rng = self.rng
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    n = self.m.n[h]
+    self.emit({'op': 'marginal', 'h': h, 'bits': [int(b) for b in rng.choice(n, size=int(rng.integers(0, min(8, n) + 1)), replace=False)]})
+    return True
+
+  def k_sample(self):
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    u = np.sort(self.rng.random(int(self.rng.integers(1, 65))))
+    self.emit({'op': 'sample', 'h': h, 'u': u})
+    return True
+
+  def k_expect(self):
+    rng, m = self.rng, self.m
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    n, loc = m.n[h], m.local_bits(h)
+    xs = []
+    for _ in range(int(rng.integers(1, 4))):
+      x = 0
+      for b in rng.choice(loc, size=int(rng.integers(0, min(4, len(loc)) + 1)), replace=False):
+        x |= 1 << int(b)
+      xs.append(x)
+    nt = int(rng.integers(1, 21))
+    x = [xs[int(rng.integers(len(xs)))] for _ in range(nt)]
+    if rng.random() < 0.3:
+      x = [xs[0]] * nt                                     # up to 20 terms on ONE x mask: two reads of 16
+    z = [int(rng.integers(1 << n)) if rng.random() < 0.8 else 0 for _ in range(nt)]
+    self.emit({'op': 'expect', 'h': h, 'x': x, 'z': z})
+    return True
+
+  def k_argmax(self):
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    self.emit({'op': 'argmax', 'h': h})
+    return True
+
+  def _held_index(self, h, count):
+    mine = mine_of(self.m.n[h], self.m.held[h])
+    return mine[self.rng.integers(mine.size, size=count)]
+
+  def k_amplitude(self):
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    self.emit({'op': 'amplitude', 'h': h, 'index': int(self._held_index(h, 1)[0])})
+    return True
+
+  def k_amplitudes(self):
+    rng = self.rng
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    idx = rng.integers(1 << self.m.n[h], size=int(rng.integers(0, 40)))           # (other shards' indices: exact zeros)
+    idx = np.concatenate([idx, idx[:idx.size // 3], self._held_index(h, 3)]).astype(np.uint64)
+    self.emit({'op': 'amplitudes', 'h': h, 'indices': rng.permutation(idx)})
+    return True
+
+  def k_select(self):
+    rng = self.rng
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    _, _, p = self.m._probs(h)
+    ps = np.sort(p)
+    r = rng.random()
+    if r < 0.25:
+      thr = 0.0                                            # everything
+    elif r < 0.45:
+      thr = float(ps[-1]) * 2 + 1.0                        # nothing
+    elif r < 0.8:
+      thr = float(ps[-min(ps.size, int(rng.integers(1, 9)))])   # a few (ties with the threshold included)
+    else:
+      thr = float(ps[ps.size // 2])
+    self.emit({'op': 'select', 'h': h, 'threshold': thr})
+    return True
+
+  def k_topk(self):
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    self.emit({'op': 'topk', 'h': h, 'k': int(self.rng.choice([1, 5, 64]))})
+    return True
+
+  def room(self):
+    return len(self.live()) < self.max_live
+
+  def k_clone(self):
+    h = self.pick(self.usable)
+    if h is None or not self.room():
+      return False
+    self.emit({'op': 'clone', 'h': h, 'new': self.new_slot()})
+    return True
+
+  def k_copy(self):
+    rng, m = self.rng, self.m
+    pairs = [(d, s) for d in self.live() for s in self.live() if d != s and m.n[d] == m.n[s] and m.held[d] == m.held[s] and self.usable(s)]
+    if not pairs:
+      return False
+    pairs.sort(key=lambda p: -m.q[p[0]])                   # prefer a destination with gates queued
+    d, s = pairs[0] if m.q[pairs[0][0]] and rng.random() < 0.7 else pairs[int(rng.integers(len(pairs)))]
+    self.emit({'op': 'copy', 'h': d, 'src': s})
+    return True
+
+  def k_extend(self):
+    rng, m = self.rng, self.m
+    h = self.pick(lambda x: self.usable(x) and m.n[x] < MAX_BITS)
+    if h is None or not self.room():
+      return False
+    k = int(rng.integers(1, min(3, MAX_BITS - m.n[h]) + 1))
+    if m.n[h] + k > 17 and rng.random() < 0.5:
+      return False                                         # (keep the largest states rare: they cost host time)
+    amps, basis = (None, int(rng.integers(1 << k))) if rng.random() < 0.4 else (_rand_table(rng, k), 0)
+    self.emit({'op': 'extend', 'h': h, 'k': k, 'amps': amps, 'basis': basis, 'new': self.new_slot()})
+    return True
+
+  def k_release(self):
+    rng, m = self.rng, self.m
+    h = self.pick(lambda x: self.usable(x) and m.nloc(x) >= 3)
+    if h is None or not self.room():
+      return False
+    loc = m.local_bits(h)
+    k = int(rng.integers(1, min(3, len(loc) - 2) + 1))
+    bits = [int(b) for b in rng.choice(loc, size=k, replace=False)]
+    p = m._marginal({'h': h, 'bits': bits})
+    value = int(rng.choice(np.flatnonzero(p >= 0.5 * p.max())))
+    new = self.new_slot()
+    self.emit({'op': 'release', 'h': h, 'bits': bits, 'value': value, 'new': new})
+    self._renorm(new)
+    return True
+
+  def k_close(self):
+    m = self.m
+    c = self.live()
+    if len(c) < 2:                                         # never the last handle
+      return False
+    big = [h for h in c if m.n[h] >= 18]                   # (the largest states first: they cost host time)
+    h = big[0] if big else c[int(self.rng.integers(len(c)))]
+    self.emit({'op': 'close', 'h': h})
+    return True
+
+  def unalign(self, o, h):
+    """in a third of the two-state steps one side's local bits are swapped first, so that the two layouts differ whether or
+    not a sweep has re-laid one of them out (below 14 local bits nothing else would)"""
+    if o != h and self.m.nloc(o) >= 2 and self.rng.random() < 0.35:
+      a, b = (int(x) for x in self.rng.choice(self.m.local_bits(o), size=2, replace=False))
+      self.emit({'op': 'remap', 'h': o, 'a': a, 'b': b})
+
+  def k_inner(self):
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    o = self.partner(h)
+    if o is None or (self.rng.random() < 0.15):
+      o = h
+    if not self.usable(o):
+      return False
+    self.unalign(o, h)
+    self.emit({'op': 'inner', 'h': h, 'other': o})
+    return True
+
+  def k_axpby(self):
+    rng = self.rng
+    h = self.pick()
+    o = self.partner(h) if h is not None else None
+    if o is None or not self.usable(o):
+      return False
+    self.unalign(o, h)
+    r = rng.random()
+    cz = lambda: complex(rng.uniform(-1, 1), rng.uniform(-1, 1))      # noqa: E731
+    exact = [(0, cz()), (cz(), 0), (0, 0), (1, 0), (1, 1), (1, -1), (-1, 1), (0, 1)]
+    alpha, beta = (cz(), cz()) if r < 0.45 else exact[int(rng.integers(len(exact)))]
+    if complex(alpha) != 0 and not self.usable(h):
+      return False
+    if complex(alpha) == 0 and complex(beta) != 0 and rng.random() < 0.5:
+      # the header: alpha == 0 exactly, dst's old values are not read -- NaN in them does not propagate
+      self.emit({'op': 'scale', 'h': h, 'z': complex(np.nan, 0), 'poison': True})
+    trial = axpby_ref(self.m.wide(h), alpha, self.m.wide(o), beta)
+    nv = float(np.vdot(trial, trial).real)
+    if not (complex(alpha) == 0 and complex(beta) == 0) and not 1e-3 <= nv <= 100:
+      if self.steps[-1].get('poison'):
+        alpha, beta = 0, 1
+      else:
+        return False
+    self.emit({'op': 'axpby', 'h': h, 'other': o, 'alpha': complex(alpha), 'beta': complex(beta)})
+    if complex(alpha) == 0 and complex(beta) == 0:         # a state of zeros: give it content again
+      self.emit({'op': 'copy', 'h': h, 'src': o})
+    return True
+
+  def k_flush(self):
+    h = self.pick(lambda x: self.m.q[x] > 0) or self.pick()
+    self.emit({'op': 'flush', 'h': h})
+    return True
+
+  def k_set_relayout(self):
+    h = self.pick()
+    self.emit({'op': 'set_relayout', 'h': h, 'on': int(self.rng.integers(2))})
+    return True
+
+  def k_remap(self):
+    m = self.m
+    h = self.pick(lambda x: m.nloc(x) >= 2)
+    if h is None:
+      return False
+    a, b = (int(x) for x in self.rng.choice(m.local_bits(h), size=2, replace=False))
+    self.emit({'op': 'remap', 'h': h, 'a': a, 'b': b})
+    return True
+
+  def k_refused(self):
+    """one host-side refusal from the header's lists; nothing is launched, nothing changes"""
+    rng, m = self.rng, self.m
+    if self.refused >= 2:
+      return False
+    h = self.pick(lambda x: m.nloc(x) >= 2)
+    if h is None:
+      return False
+    loc = m.local_bits(h)
+    what = ('matrix_twice', 'mux_target_selected', 'marginal_twice', 'sample_descending', 'copy_self', 'axpby_self',
+            'extend_basis', 'release_value')[int(rng.integers(8))]
+    arg = 'same' if what in ('matrix_twice', 'mux_target_selected', 'marginal_twice') else 'arg'
+    self.refused += 1
+    self.emit({'op': 'refused', 'h': h, 'what': what, 'code': native.QH_ERR_SAME_QUBIT if arg == 'same' else native.QH_ERR_ARG,
+               'bits': [int(loc[0]), int(loc[1])]})
+    return True
+
+  WEIGHTS = {'gates': 9.0, 'close': 0.6, 'refused': 0.8, 'remap': 1.6, 'flush': 0.7, 'clone': 1.3, 'inner': 1.8, 'axpby': 1.8, 'copy': 1.3}
+
+  def run(self):
+    self.start()
+    nsteps = int(self.rng.integers(30, 56))              # fixed by the seed, never by a clock; a kind adds at most 5 steps
+    kinds = list(KINDS)
+    w = np.array([self.WEIGHTS.get(k, 1.0) for k in kinds])
+    w /= w.sum()
+    tries = 0
+    while len(self.steps) - 1 < nsteps and tries < 40 * nsteps:
+      tries += 1
+      getattr(self, 'k_' + kinds[int(self.rng.choice(len(kinds), p=w))])()
+    assert 30 <= len(self.steps) - 1 <= 60, len(self.steps)
+    return self.steps
+
+
+def gen_program(seed, bw, mode='own'):
+  """the steps of program `seed` at width bw in mode 'own' | 'attached' | 'mapped' | 'shard': the same list every time"""
+  assert bw in (128, 64) and mode in ('own', 'attached', 'mapped', 'shard')
+  return _Gen(seed, bw, mode).run()
+
+
+def describe(s):
+  """a step as a short JSON-able dict (tables and matrices by shape)"""
+  out = {}
+  for k, v in s.items():
+    if isinstance(v, np.ndarray):
+      out[k] = v.tolist() if v.size <= 8 else f'<{v.dtype} {list(v.shape)}>'
+    elif k == 'gates' and s['op'] == 'gates':
+      out[k] = f'<{len(v)} gates>'
+    elif k == 'factors':
+      out[k] = [(n, x if isinstance(x, int) else f'<table {len(x)}>') for n, x in v]
+    elif isinstance(v, complex):
+      out[k] = [v.real, v.imag]
+    else:
+      out[k] = v
+  return out
+
+
+# ---- the runner -----------------------------------------------------------------------------------------------------------------
+class StepFailure(AssertionError):
+  def __init__(self, index, step, what):
+    super().__init__(f'step {index} {describe(step)}: {what}')
+    self.index, self.step, self.what = index, step, what
+
+
+class Check:
+  """What a run of run_program is held to and what it saw: the width's tolerances, one event per step (for the coverage
+  table) and the figures of the chain comparison."""
+
+  def __init__(self, bw):
+    self.bw = bw
+    self.events = []            # (index, op, local bits out of canonical order, a queued burst ran in the step, inner path or None)
+    self.relaid = 0             # barrier / reader steps whose own flush re-laid the handle out
+    self.chain_err = self.chain_d = self.chain_tol = None
+    self.nloc0 = None
+
+
+def _bitmap(st):
+  return st.bitmap() if hasattr(st, 'bitmap') else shard_util.bitmap(st)
+
+
+def _pending(st):
+  if hasattr(st, 'pending_gates'):
+    return st.pending_gates()
+  import ctypes
+  c = ctypes.c_uint64()
+  native.check(st.lib.qh_pending_gates(st.h, ctypes.byref(c)))
+  return int(c.value)
+
+
+def _plans_relayout(st):
+  """does the plan of what the handle has QUEUED re-lay it out: qh_plan_json's per-sweep relayout field, which goes through
+  the engine's relayout_wanted and neither launches nor allocates (an empty queue has no sweeps and says nothing)"""
+  if hasattr(st, 'plans_relayout'):
+    return st.plans_relayout()
+  return '"relayout":1' in st.plan_json()
+
+
+def _canonical(bm, nloc):
+  pos = [p for p in bm if p < nloc]
+  return pos == sorted(pos)
+
+
+_LOGICAL_CACHE = {}
+
+
+def _logical_index(bm, shard, nloc):
+  """global logical index of every local physical index of a shard under the bit map bm"""
+  key = (tuple(bm), shard, nloc)
+  if key not in _LOGICAL_CACHE:
+    if len(_LOGICAL_CACHE) > 64:
+      _LOGICAL_CACHE.clear()
+    phys = (np.uint64(shard) << np.uint64(nloc)) | np.arange(1 << nloc, dtype=np.uint64)
+    _LOGICAL_CACHE[key] = shard_util.logical_of(list(bm), phys).astype(np.int64)
+  return _LOGICAL_CACHE[key]
+
+
+class _Runner:
+  def __init__(self, program, make_state, check):
+    self.prog, self.make, self.check = program, make_state, check
+    self.bw = program[0]['bw']
+    self.dev, self.shard, self.fixed_ptr = {}, {}, {}
+    self.m = ModelState()                                   # step-local: re-read from the device after every step
+    self.chain = ModelState()                               # never re-read
+    self.chain_r = ModelState(np.complex64) if self.bw == 64 else None
+    self.i, self.s = 0, None
+
+  def fail(self, what):
+    raise StepFailure(self.i, self.s, what)
+
+  def need(self, cond, what):
+    if not cond:
+      self.fail(what)
+
+  # -- reading a handle exactly: a clone's download through the clone's bit map (qh_download re-lays a permuted state out, so
+  # the handle under test is never downloaded before the end; _logical of tests/test_gpu_inner.py)
+  def read(self, h):
+    st = self.dev[h]
+    c = st.clone()
+    try:
+      self.need(_bitmap(c) == _bitmap(st), 'a clone does not carry its source\'s bit map')
+      phys = c.download().astype(np.complex128)
+      bm = _bitmap(c)                                        # (the download may have re-laid the clone out)
+    finally:
+      c.close()
+    out = np.zeros(1 << self.m.n[h], dtype=np.complex128)
+    out[_logical_index(bm, self.shard[h], st.nbits)] = phys
+    return out
+
+  def own_download(self, h):
+    st = self.dev[h]
+    phys = st.download().astype(np.complex128)
+    out = np.zeros(1 << self.m.n[h], dtype=np.complex128)
+    out[_logical_index(_bitmap(st), self.shard[h], st.nbits)] = phys
+    return out
+
+  def kernels(self, h):
+    return self.dev[h].stats()['kernels_launched']
+
+  def check_ptr(self, h, always=False):
+    # (qh_device_ptr brings a permuted layout back to canonical order: between steps it is only asked where that moves nothing)
+    if h in self.fixed_ptr and h in self.dev and (always or self.fixed_ptr[h][2] or _canonical(_bitmap(self.dev[h]), self.dev[h].nbits)):
+      self.need(self.fixed_ptr[h][0]() == self.fixed_ptr[h][1], 'the pointer of an attached / host-mapped handle moved')
+
+  def check_raw(self, h, vec, bm):
+    """the state of an attached / host-mapped handle lies in the caller's memory, in the handle's current layout: read there
+    (no call into the engine, so nothing is re-laid out) it is what the clone gave"""
+    st = self.dev[h]
+    if h in self.fixed_ptr and bm is not None and getattr(st, 'raw_view', None) is not None:
+      raw = np.asarray(st.raw_view()).astype(np.complex128)
+      self.need(np.array_equal(raw, vec[_logical_index(bm, self.shard[h], st.nbits)], equal_nan=True),
+                'the caller\'s memory does not hold the state of the attached / host-mapped handle')
+
+  def held_of(self, h):
+    st, bm = self.dev[h], _bitmap(self.dev[h])
+    return {b: (self.shard[h] >> (bm[b] - st.nbits)) & 1 for b in range(len(bm)) if bm[b] >= st.nbits}
+
+  # -- the start ---------------------------------------------------------------------------------------------------------------
+  def do_init(self, s):
+    nloc, g, n = s['nloc'], s['g'], s['nloc'] + s['g']
+    self.check.nloc0 = nloc
+    psi, bm = init_vector(s), init_bitmap(s)
+    dt = np.complex128 if self.bw == 128 else np.complex64
+    for shard, h in enumerate(s['slots']):
+      st = self.make(nloc, self.bw, s['mode'] if s['mode'] != 'shard' else 'own')
+      self.dev[h], self.shard[h] = st, shard
+      if g:
+        st.set_shard(n, shard)
+      if s['how'] == 'upload':                               # _make of tests/test_gpu_shard_readout.py: the swap relabels, so the
+        st.upload(psi[_logical_index(bm, shard, nloc)].astype(dt))      # data goes up in the order the swaps will give it
+      for a, b in s['swaps']:
+        st.remap_swap(a, b)
+      if s['how'] == 'basis':
+        st.init_basis(s['index'])
+      elif s['how'] == 'product':
+        st.init_product(s['factors'])
+      self.need(_bitmap(st) == bm, f'bit map {_bitmap(st)} after the start, expected {bm}')
+      if s['mode'] == 'attached':
+        self.fixed_ptr[h] = ((lambda st=st: st.device_ptr), st.device_ptr, False)
+      elif s['mode'] == 'mapped':                            # (qh_host_ptr moves nothing: asked after every step)
+        self.fixed_ptr[h] = ((lambda st=st: st.host_array().ctypes.data), st.host_array().ctypes.data, True)
+    for mdl in (self.m, self.chain, self.chain_r):
+      if mdl is not None:
+        mdl.step(s)
+    for h in s['slots']:
+      got = self.read(h)
+      err = float(np.max(np.abs(got - self.m.wide(h))))
+      self.need(err <= amp_tol(self.bw), f'initial state off by {err:.3e}')        # _amp_tol
+      self.need(self.held_of(h) == self.m.held[h], 'held bits differ from the model\'s')
+      self.m.put(h, got)
+      if s['how'] == 'upload':                               # an upload is exact: the chain starts from what the device holds
+        for mdl in (self.chain, self.chain_r):
+          if mdl is not None:
+            mdl.put(h, got)
+
+  # -- running one step on the device -------------------------------------------------------------------------------------------
+  def _call(self, s):
+    op, st = s['op'], self.dev[s['h']]
+    if op == 'gates':
+      for cm, t, g in s['gates']:
+        st.apply_bits(cm, t, g)
+    elif op == 'matrix':
+      st.apply_matrix(s['m'], s['bits'], s['ctl'])
+    elif op == 'mux':
+      st.apply_mux(s['gates'], s['sel'], s['tgt'])
+    elif op == 'diag':
+      st.apply_diag(s['values'], s['bits'])
+    elif op == 'scale':
+      st.scale(s['z'])
+    elif op == 'project_bit':
+      st.project_bit(s['bit'], s['value'])
+    elif op == 'project_bits':
+      st.project_bits(s['mask'], s['value'])
+    elif op == 'norm2':
+      return st.norm2()
+    elif op == 'prob_bit':
+      return st.prob_bit(s['bit'], s['value'])
+    elif op == 'marginal':
+      return st.marginal(s['bits'])
+    elif op == 'sample':
+      return st.sample(s['u'])
+    elif op == 'expect':
+      return st.expect_pauli(s['x'], s['z'])
+    elif op == 'argmax':
+      return st.argmax()
+    elif op == 'amplitude':
+      return complex(st.amplitude(s['index']))
+    elif op == 'amplitudes':
+      return st.amplitudes(s['indices'])
+    elif op == 'select':
+      return st.select(s['threshold'], cap=1 << 20)
+    elif op == 'topk':
+      return st.topk(s['k'])
+    elif op == 'clone':
+      self.dev[s['new']] = st.clone()
+    elif op == 'copy':
+      st.copy_from(self.dev[s['src']])
+    elif op == 'extend':
+      self.dev[s['new']] = st.extend(s['k'], s['amps'], s['basis'])
+    elif op == 'release':
+      self.dev[s['new']], kept, dropped = st.release(s['bits'], s['value'])
+      return kept, dropped
+    elif op == 'close':
+      st.close()
+      del self.dev[s['h']]
+    elif op == 'inner':
+      return st.inner(self.dev[s['other']])
+    elif op == 'axpby':
+      return st.axpby(s['alpha'], self.dev[s['other']], s['beta'], norm=True)
+    elif op == 'flush':
+      st.flush()
+    elif op == 'set_relayout':
+      return st.set_relayout(s['on'])
+    elif op == 'remap':
+      st.flush()                                           # positions are physical: those the queued sweeps leave
+      bm = _bitmap(st)
+      st.remap_swap(bm[s['a']], bm[s['b']])
+      return bm
+    return None
+
+  def call(self, s):
+    """a valid step the engine refuses is a failure of that step, named like any other"""
+    try:
+      return self._call(s)
+    except native.QhError as e:
+      self.fail(f'the engine refused a valid step: {e}')
+
+  def refused(self, s):
+    st, (a, b) = self.dev[s['h']], s['bits']
+    calls = {
+        'matrix_twice': lambda: st.apply_matrix(np.eye(4), [a, a]),
+        'mux_target_selected': lambda: st.apply_mux(np.stack([np.eye(2)] * 2), [a], a),
+        'marginal_twice': lambda: st.marginal([a, b, a]),
+        'sample_descending': lambda: st.sample([0.5, 0.25]),
+        'copy_self': lambda: st.copy_from(st),
+        'axpby_self': lambda: st.axpby(1, st, 1),
+        'extend_basis': lambda: st.extend(1, None, 2),
+        'release_value': lambda: st.release([a], 2),
+    }
+    try:
+      calls[s['what']]()
+    except native.QhError as e:
+      self.need(e.code == s['code'], f'error code {e.code}, expected {s["code"]}')
+      return
+    self.fail('the call was not refused')
+
+  # -- one step ------------------------------------------------------------------------------------------------------------------
+  def run_step(self, s):
+    op, h, bw, m = s['op'], s['h'], self.bw, self.m
+    involved = [x for x in (h, s.get('other'), s.get('src')) if x is not None]
+    involved = list(dict.fromkeys(involved))
+    for x in involved:
+      self.need(_pending(self.dev[x]) == m.q[x], f'handle {x}: {_pending(self.dev[x])} gates pending before the step, expected {m.q[x]}')
+    q_before = {x: m.q[x] for x in involved}
+    quiet = not any(q_before.values())                     # nothing queued: stats, bit maps and amplitudes can be held exactly
+    bm_before = {x: _bitmap(self.dev[x]) for x in involved}
+    if op == 'gates':
+      self.call(s)
+      for mdl in (m, self.chain, self.chain_r):
+        if mdl is not None:
+          mdl.step(s)
+      self.need(_pending(self.dev[h]) == m.q[h], f'{_pending(self.dev[h])} gates pending behind the burst, expected {m.q[h]}')
+      self.need(_bitmap(self.dev[h]) == bm_before[h], 'queueing gates changed the bit map')
+      self.check.events.append((self.i, op, not _canonical(bm_before[h], self.dev[h].nbits), False, None))
+      return
+    if op == 'refused':
+      k0 = self.kernels(h)
+      self.refused(s)
+      self.need(_pending(self.dev[h]) == q_before[h] and _bitmap(self.dev[h]) == bm_before[h] and self.kernels(h) == k0,
+                'a refused call changed the queue, the bit map or launched a kernel')
+      if quiet:
+        self.need(self.read(h).tobytes() == m.wide(h).tobytes(), 'a refused call changed the state')
+      self.check.events.append((self.i, op, False, False, None))
+      return
+    for x in involved:                                     # the mode, read without changing it, where a plan exists to show it
+      if q_before[x] and self.dev[x].nbits >= SWEEPS_FROM and not m.wanted(x):
+        self.need(not _plans_relayout(self.dev[x]), f'handle {x}: the queued burst is planned with relayout sweeps, its relayout mode is off')
+    k_before = {x: self.kernels(x) for x in involved}
+    n0 = {x: self.dev[x].marginal([]).tobytes() for x in involved} if quiet and op in READERS + ('inner',) else {}
+    if n0:
+      k_before = {x: self.kernels(x) for x in involved}
+    path = None
+    if op in TWO_STATE and quiet:
+      path = self.dev[h].inner_plan(self.dev[s['other']])['path']
+    got = self.call(s)
+    dk = {x: self.kernels(x) - k_before[x] for x in involved if x in self.dev}
+    want = m.step(s)
+    for mdl in (self.chain, self.chain_r):
+      if mdl is not None:
+        mdl.step(s)
+    if op == 'close':
+      self.check.events.append((self.i, op, False, False, None))
+      return
+    if op == 'set_relayout' and s['on'] and q_before[h]:   # allocates, runs nothing: the burst stays queued (and unread)
+      self.need(_pending(self.dev[h]) == q_before[h] and _bitmap(self.dev[h]) == bm_before[h], 'set_relayout(1) ran the queue')
+      self.need(bool(got) == bool(want), f'set_relayout(1) answered {got}, the mode should be {int(want)}')
+      self.check.events.append((self.i, op, not _canonical(bm_before[h], self.dev[h].nbits), False, None))
+      return
+    # every barrier: nothing is left queued -- on the destination of a copy because its queue was dropped
+    for x in involved:
+      self.need(_pending(self.dev[x]) == 0, f'handle {x}: {_pending(self.dev[x])} gates pending behind a barrier step')
+    new = s.get('new')
+    if new is not None:
+      self.shard[new] = self.shard[h]
+      self.need(_pending(self.dev[new]) == 0, 'a new handle with gates queued')
+      self.need(self.dev[new].stats()['kernels_launched'] == 0, 'a new handle whose stats are not zero')
+    if op in TWO_STATE and path is None:
+      path = self.dev[h].inner_plan(self.dev[s['other']])['path']
+    bm_after = {x: _bitmap(self.dev[x]) for x in involved}
+    # -- bit maps ------------------------------------------------------------------------------------------------------------
+    for x in involved:
+      moved = bm_after[x] != bm_before[x]
+      if op == 'copy' and x == h:
+        self.need(bm_after[h] == bm_after[s['src']], 'copy_from: the destination\'s bit map is not the source\'s')
+      elif op == 'remap' and x == h:
+        a, b = s['a'], s['b']
+        exp = list(got)                                    # (the map behind remap_swap's own flush)
+        self.need(exp == bm_before[h] or (q_before[h] and m.mode[h] == 1), 'remap_swap: its flush moved a bit map that relayout may not touch')
+        exp[a], exp[b] = exp[b], exp[a]
+        self.need(bm_after[h] == exp, f'remap_swap: bit map {bm_after[h]}, expected {exp}')
+      elif op == 'set_relayout' and not s['on']:
+        self.need(_canonical(bm_after[x], self.dev[x].nbits), 'set_relayout(0) left the local bits out of order')
+      elif q_before[x] == 0:
+        self.need(not moved, f'handle {x}: the bit map moved in a step that had nothing to flush')
+      elif moved:                                          # only relayout sweeps do that, and only where the mode is on
+        self.need(m.mode[x] == 1, f'handle {x}: a flush re-laid the handle out, its relayout mode is {m.mode[x]}')
+        if op in BARRIERS + READERS:
+          self.check.relaid += 1                           # relayout sweeps left a permuted map in front of this very call
+      self.need({b for b, p in enumerate(bm_after[x]) if p >= self.dev[x].nbits} == set(m.held[x]), 'the held bits changed')
+      self.check_ptr(x)
+    if op == 'set_relayout':
+      self.need(bool(got) == bool(want), f'set_relayout({s["on"]}) answered {got}, the mode should be {int(want)}')
+    if op == 'clone':
+      self.need(_bitmap(self.dev[new]) == bm_after[h], 'clone: the bit map is not the source\'s')
+    if op == 'extend':
+      nl, k = self.dev[h].nbits, s['k']
+      exp = list(range(nl, nl + k)) + [p if p < nl else p + k for p in bm_after[h]]
+      self.need(_bitmap(self.dev[new]) == exp, f'extend: bit map {_bitmap(self.dev[new])}, expected {exp}')
+    if op == 'release':
+      gone = sorted(bm_after[h][b] for b in s['bits'])
+      exp = [p - sum(1 for r in gone if r < p) for b, p in enumerate(bm_after[h]) if b not in s['bits']]
+      self.need(_bitmap(self.dev[new]) == exp, f'release: bit map {_bitmap(self.dev[new])}, expected {exp}')
+    # -- amplitudes: what every touched handle holds now, exactly, against the model's step from what it held before ------------
+    touched = involved + ([new] if new is not None else [])
+    exact_ops = READERS + ('clone', 'copy', 'release', 'flush', 'set_relayout', 'remap', 'inner', 'project_bit', 'project_bits')
+    after = {}
+    for x in touched:
+      after[x] = self.read(x)
+      w = m.wide(x)
+      if s.get('poison'):
+        self.need(bool(np.all(np.isnan(after[x][mine_of(m.n[x], m.held[x]).astype(np.int64)]))), 'scale by NaN left numbers')
+        continue
+      exact = quiet and (op in exact_ops or (op == 'extend' and (x == h or s['amps'] is None)) or
+                         (op == 'axpby' and (x != h or (s['alpha'] == 1 and s['beta'] == 0))))
+      if exact:       # zero tolerance (array_equal: equal as numbers, the sign of a zero may differ)
+        self.need(np.array_equal(after[x], w), f'handle {x}: amplitudes changed where the header promises them as stored '
+                  f'(max diff {float(np.max(np.abs(after[x] - w))):.3e})')
+      else:
+        err = float(np.max(np.abs(after[x] - w)))
+        self.need(err <= amp_tol(bw), f'handle {x}: amplitudes off by {err:.3e} (limit {amp_tol(bw):.1e})')      # _amp_tol
+      if op in ('project_bit', 'project_bits') and x == h:
+        keep = np_keep(w.size, *((1 << s['bit'], s['value'] << s['bit']) if op == 'project_bit' else (s['mask'], s['value'])))
+        self.need(not np.any(after[x][~keep]), 'a projection left something where it writes zeros')
+      m.put(x, after[x])
+      self.check_raw(x, after[x], bm_after.get(x))
+    if op in ('clone', 'copy'):
+      a, b = (new, h) if op == 'clone' else (h, s['src'])
+      self.need(after[a].tobytes() == after[b].tobytes(), f'{op}: the two states differ')
+    # -- results, from what the handle holds now (a reader changes nothing: the model's answer on the exact state) --------------
+    if op in READERS or op == 'inner':
+      want = m.step(s)
+      self.results(s, got, want, after, bm_after)
+      for x, b in n0.items():
+        self.need(self.dev[x].marginal([]).tobytes() == b, f'handle {x}: marginal([]) changed its bits across a reader')
+    elif op == 'release':
+      for name, g_, w_ in (('kept', got[0], want[0]), ('dropped', got[1], want[1])):
+        miss = close(g_, w_, bw)                           # _close
+        self.need(miss is None, f'release: weight {name} {miss}')
+    elif op == 'axpby' and not np.isnan(want):
+      want = m.norm(h)
+      miss = close(got, want, bw)                          # _close
+      self.need(miss is None, f'axpby: norm2 {miss}')
+    # -- stats, where the header gives an exact number ---------------------------------------------------------------------------
+    if quiet:
+      exp = None
+      if op in ('mux', 'diag', 'select'):
+        exp = {h: 1}
+      elif op == 'amplitudes':
+        exp = {h: 0}
+      elif op == 'expect':
+        xs = {}
+        for x in s['x']:
+          xs[x] = xs.get(x, 0) + 1
+        exp = {h: sum(-(-c // 16) for c in xs.values())}
+      elif op == 'inner':
+        exp = {h: 1, s['other']: 0} if s['other'] != h else {h: 1}
+      elif op == 'axpby':
+        exp = {h: 0 if s['alpha'] == 1 and s['beta'] == 0 else 1, s['other']: 0}
+      elif op in ('extend', 'release'):
+        exp = {h: 1}
+      if exp is not None:
+        for x, e in exp.items():
+          self.need(dk[x] == e, f'handle {x}: kernels_launched grew by {dk[x]}, the header says {e}')
+    local_perm = not _canonical(bm_after[h], self.dev[h].nbits)
+    self.check.events.append((self.i, op, local_perm, bool(q_before[h]), path))
+
+  def results(self, s, got, want, after, bm_after):
+    op, h, bw, st = s['op'], s['h'], self.bw, self.dev[s['h']]
+    if op in ('norm2', 'prob_bit', 'marginal'):
+      miss = close(got, want, bw)                           # _close
+      self.need(miss is None, f'{op}: {miss}')
+      if op == 'marginal':
+        self.need(st.marginal(s['bits']).tobytes() == np.asarray(got).tobytes(), 'marginal: two calls, two answers')
+    elif op == 'expect':
+      err = float(np.max(np.abs(got - want))) if len(want) else 0.0
+      # TOL of tests/test_gpu_inner.py is for normalised states; a program's norms lie in [0.25, 4] and these sums are
+      # quadratic in the amplitudes, so the bound is TOL times the norm where that is above 1 (at most 4e-12)
+      self.need(err < TOL * max(1.0, self.m.norm(h)), f'expect_pauli off by {err:.3e}')
+      self.need(st.expect_pauli(s['x'], s['z']).tobytes() == got.tobytes(), 'expect_pauli: two calls, two answers')
+    elif op == 'inner':
+      err = abs(got - want)
+      scale = max(1.0, float(np.sqrt(self.m.norm(h) * self.m.norm(s['other']))))      # (TOL scaled as for expect_pauli)
+      self.need(err < TOL * scale, f'inner off by {err:.3e}')
+      if s['other'] == h:
+        self.need(got.imag == 0.0, f'inner(a, a) has imaginary part {got.imag!r}')
+      again = st.inner(self.dev[s['other']])
+      self.need((again.real, again.imag) == (got.real, got.imag), 'inner: two calls, two answers')
+    elif op == 'argmax':
+      mine, _, p = self.m._probs(h)
+      top = float(p.max())
+      where = np.flatnonzero(mine == np.uint64(got[0]))
+      eps = 1e-6 if bw == 64 else 4e-16                     # tools/fuzz_parity.py's argmax rule
+      self.need(where.size == 1 and p[where[0]] >= top * (1 - eps) - 1e-300 and abs(got[1] - top) <= eps * top + 1e-300,
+                f'argmax {got}, the largest probability is {top!r} at {want[0]}')
+    elif op == 'amplitude':
+      self.need(got == want, f'amplitude {got!r}, stored {want!r}')
+    elif op == 'amplitudes':
+      self.need(np.array_equal(got, want), 'amplitudes: entries differ from what is stored')
+    elif op == 'select':
+      idx, amp, cnt, w = got
+      self.need(cnt == want[2], f'select: count {cnt}, expected {want[2]}')
+      self.need(np.array_equal(idx, want[0]) and np.array_equal(amp, want[1]), 'select: entries differ (ascending logical index, as stored)')
+      miss = close(w, want[3], bw)                          # _close
+      self.need(miss is None, f'select: weight {miss}')
+      self.need(st.select(s['threshold'], cap=0)[3] == w, 'select: two calls, two weights')
+    elif op == 'topk':
+      self.need(np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]),
+                f'topk: indices {got[0][:8].tolist()}..., expected {want[0][:8].tolist()}...')
+    elif op == 'sample':
+      nloc = st.nbits
+      lidx = _logical_index(bm_after[h], self.shard[h], nloc)
+      a = after[h][lidx]
+      pp = a.real ** 2 + a.imag ** 2                        # physical order
+      inv = np.full(1 << self.m.n[h], -1, dtype=np.int64)
+      inv[lidx] = np.arange(lidx.size)
+      g = inv[np.asarray(got, dtype=np.int64)]
+      self.need(bool(np.all(g >= 0)), 'sample: an index another shard holds')
+      try:
+        shard_util.check_exact_cdf(pp, g, np.asarray(s['u']))
+      except AssertionError as e:
+        self.fail(f'sample: not the inverse CDF in physical order {e}')
+
+  # -- the whole program ---------------------------------------------------------------------------------------------------------
+  def run(self):
+    try:
+      for self.i, self.s in enumerate(self.prog):
+        if self.s['op'] == 'init':
+          self.do_init(self.s)
+        else:
+          self.run_step(self.s)
+      self.finish()
+    finally:
+      for st in self.dev.values():
+        st.close()
+      self.dev = {}
+
+  def finish(self):
+    """the chain: every live handle's OWN download against a model that never looked at the device"""
+    self.i, self.s = len(self.prog), {'op': 'final download', 'h': None}
+    err = d = 0.0
+    for h in sorted(self.dev):
+      self.chain.run(h)
+      got = self.own_download(h)
+      self.check_ptr(h, always=True)
+      self.need(got.tobytes() == self.m.wide(h).tobytes() if self.m.q[h] == 0 else True,
+                f'handle {h}: its own download differs from what its clone gave')
+      w = self.chain.wide(h)
+      if np.all(np.isfinite(w)):
+        err = max(err, float(np.max(np.abs(got - w))))
+        if self.chain_r is not None:
+          d = max(d, float(np.max(np.abs(self.chain_r.wide(h) - w))))
+      else:
+        self.need(np.array_equal(np.isfinite(got), np.isfinite(w)), f'handle {h}: NaN where the model has numbers')
+    # complex128: tools/fuzz_parity.py's bound.  complex64: d = how far the same program drifts on the CPU when the state is
+    # rounded to complex64 after every gate and every step (the per-gate engine's worst case); the engine may order its
+    # roundings differently, never more often per gate: max(_amp_tol(64), 4 d)
+    tol = CHAIN_TOL_128 if self.bw == 128 else max(amp_tol(64), 4 * d)
+    self.check.chain_err, self.check.chain_d, self.check.chain_tol = err, d, tol
+    print(f'chain: bw={self.bw} nloc0={self.check.nloc0} steps={len(self.prog) - 1} d={d:.3e} gpu_err={err:.3e} tol={tol:.3e}')
+    self.need(err <= tol, f'chain: the final states are off by {err:.3e} (limit {tol:.3e}, d = {d:.3e})')
+
+
+def run_program(program, make_state, check):
+  """Runs `program` on handles made by make_state(nloc, bw, kind) (kind 'own' | 'attached' | 'mapped'; fused: gates queue)
+  and holds every step to the model.  Raises StepFailure (an AssertionError that names the step)."""
+  _Runner(program, make_state, check).run()
+  return check
+
+
+def make_device_state(nloc, bw, kind):
+  """make_state for the real engine: a fused qcc_amd.device.DeviceState that owns HBM memory ('own'), works on a torch
+  allocation ('attached') or on pinned host memory ('mapped'); raw_view reads the caller's memory without the engine"""
+  from qcc_amd import device  # pylint: disable=import-outside-toplevel
+  dt = np.complex128 if bw == 128 else np.complex64
+  if kind == 'mapped':
+    st = device.DeviceState(nloc, bw, fusion=native.QH_FUSE_SWEEP, host_mapped=True)
+    st.raw_view = lambda: np.array(st.host_array())
+    return st
+  if kind == 'attached':
+    import torch  # pylint: disable=import-outside-toplevel
+    buf = torch.zeros(2 << nloc, dtype=torch.float64 if bw == 128 else torch.float32, device='cuda')
+    torch.cuda.synchronize()
+    st = device.DeviceState(nloc, bw, fusion=native.QH_FUSE_SWEEP, device_ptr=buf.data_ptr())
+    st.raw_view = lambda: buf.cpu().numpy().view(dt)        # (the allocation lives as long as the handle object)
+    return st
+  return device.DeviceState(nloc, bw, fusion=native.QH_FUSE_SWEEP)
+
+
+# ---- the NumPy stand-in ---------------------------------------------------------------------------------------------------------
+class NumpyDevice:
+  """DeviceState's interface on a physical array, a bit map (physical position of every logical bit) and a gate queue per
+  handle.  Operations run the model's functions on the logical vector and store the result back through the bit map.  A flush
+  of a queue on >= PERMUTED_FROM local bits re-lays the local bits out pseudo-randomly, standing in for relayout sweeps
+  (handles that own their memory and have not been told set_relayout(0))."""
+  _serial = [0]
+
+  def __init__(self, nbits, bit_width=128, kind='own'):
+    self.nbits = self.nbits_global = int(nbits)
+    self.bit_width = bit_width
+    self.dtype = np.complex128 if bit_width == 128 else np.complex64
+    self.phys = np.zeros(1 << nbits, dtype=self.dtype)
+    self.bm = list(range(nbits))
+    self.shard = 0
+    self.queue = []
+    self.kind = kind
+    self.relayout = -1                                     # undecided: the first fused flush decides (attached / mapped: off)
+    self.kernels = 0
+    NumpyDevice._serial[0] += 1
+    self.device_ptr = 0x1000 * NumpyDevice._serial[0]
+    self.rng = np.random.default_rng(NumpyDevice._serial[0])
+
+  # -- plumbing ----------------------------------------------------------------------------------------------------------------
+  def _lidx(self):
+    return _logical_index(self.bm, self.shard, self.nbits)
+
+  def to_logical(self):
+    out = np.zeros(1 << self.nbits_global, dtype=np.complex128)
+    out[self._lidx()] = self.phys
+    return out
+
+  def store(self, vec):
+    self.phys = np.asarray(vec)[self._lidx()].astype(self.dtype)
+
+  def held(self):
+    return {b: (self.shard >> (p - self.nbits)) & 1 for b, p in enumerate(self.bm) if p >= self.nbits}
+
+  def _move_local(self, new_pos):
+    """local logical bit b goes to position new_pos[b]; the data follows"""
+    vec = self.to_logical()
+    for b, p in new_pos.items():
+      self.bm[b] = p
+    self.store(vec)
+
+  def _canonicalize(self):
+    loc = [b for b in range(self.nbits_global) if self.bm[b] < self.nbits]
+    if [self.bm[b] for b in loc] != sorted(self.bm[b] for b in loc):
+      self._move_local(dict(zip(loc, sorted(self.bm[b] for b in loc))))
+
+  def bitmap(self):
+    return list(self.bm)
+
+  def pending_gates(self):
+    return len(self.queue)
+
+  def stats(self):
+    return {'kernels_launched': self.kernels}
+
+  def host_array(self):
+    if not hasattr(self, '_host'):
+      self._host = np.empty(1)                             # (its address stands for the host pointer: a constant)
+    return self._host
+
+  def close(self):
+    self.phys = None
+
+  def set_shard(self, nbits_global, shard_index):
+    self.nbits_global, self.shard = int(nbits_global), int(shard_index)
+    self.bm = list(range(self.nbits_global))
+
+  def flush(self):
+    if not self.queue:
+      return
+    q, self.queue = self.queue, []
+    vec = self.to_logical().astype(self.dtype)
+    for cm, t, g in q:
+      apply_gate(vec, self.nbits_global, cm, t, g)
+    self.kernels += 1
+    self.store(vec)
+    if self.relayout < 0 and self.nbits >= SWEEPS_FROM:
+      self.relayout = int(self._eligible())
+    if self.nbits >= PERMUTED_FROM and self.relayout == 1:
+      loc = [b for b in range(self.nbits_global) if self.bm[b] < self.nbits]
+      self._move_local(dict(zip(loc, self.rng.permutation([self.bm[b] for b in loc]).tolist())))
+
+  sync = flush
+
+  def _eligible(self):
+    return self.kind == 'own' and int(os.environ.get('QH_RELAYOUT', '1')) != 0 and self.nbits >= SWEEPS_FROM
+
+  def plans_relayout(self):
+    want = self._eligible() if self.relayout < 0 else self.relayout == 1
+    return bool(self.queue) and want
+
+  @property
+  def raw_view(self):
+    return (lambda: self.phys) if self.kind != 'own' else None
+
+  def set_relayout(self, on):
+    if on:
+      if self.relayout != 1:
+        self.relayout = int(self._eligible())
+    else:
+      self.flush()
+      self._canonicalize()
+      self.relayout = 0
+    return self.relayout == 1
+
+  def remap_swap(self, a, b):
+    self.flush()
+    la, lb = self.bm.index(a), self.bm.index(b)
+    self.bm[la], self.bm[lb] = self.bm[lb], self.bm[la]
+
+  # -- initialisation / IO -------------------------------------------------------------------------------------------------------
+  def _fresh(self):
+    self.queue = []
+    if self.nbits_global == self.nbits:
+      self.bm = list(range(self.nbits))
+
+  def init_basis(self, index=0):
+    self._fresh()
+    v = np.zeros(1 << self.nbits_global, dtype=np.complex128)
+    v[index] = 1
+    self.store(v)
+
+  def init_product(self, factors):
+    self._fresh()
+    self.store(init_vector({'how': 'product', 'factors': factors, 'nloc': self.nbits_global, 'g': 0}))
+
+  def upload(self, host, offset=0):
+    assert offset == 0
+    self._fresh()
+    self._canonicalize()
+    self.phys = np.asarray(host).astype(self.dtype).copy()
+
+  def download(self, offset=0, count=None, out=None):
+    self.flush()
+    self._canonicalize()
+    return self.phys.copy()
+
+  # -- gates and barrier mutators --------------------------------------------------------------------------------------------------
+  def apply_bits(self, ctl_mask, tgt_bit, gate):
+    self.queue.append((int(ctl_mask), int(tgt_bit), np.asarray(gate, dtype=np.complex128).reshape(4)))
+
+  def _barrier(self, fn, kernels=1):
+    self.flush()
+    self.store(fn(self.to_logical()))
+    self.kernels += kernels
+
+  def apply_matrix(self, matrix, bits, ctl_mask=0):
+    bits = [int(b) for b in bits]
+    if len(set(bits)) != len(bits) or any((ctl_mask >> b) & 1 for b in bits):
+      raise native.QhError(native.QH_ERR_SAME_QUBIT, 'apply_matrix: a bit twice')
+    self._barrier(lambda v: dense_reference(v, self.nbits_global, np.asarray(matrix, dtype=np.complex128), bits, ctl_mask))
+
+  def _sel(self, sel_bits):
+    return [int(b) for b in sel_bits]
+
+  def apply_mux(self, gates, sel_bits, tgt_bit):
+    sel = self._sel(sel_bits)
+    if len(set(sel)) != len(sel) or tgt_bit in sel:
+      raise native.QhError(native.QH_ERR_SAME_QUBIT, 'apply_mux: the target among the selectors')
+    self._barrier(lambda v: mux_reference_fast(v, self.nbits_global, gates, sel, tgt_bit))
+
+  def apply_diag(self, values, bits):
+    self._barrier(lambda v: diag_reference(v, self.nbits_global, values, [int(b) for b in bits]))
+
+  def scale(self, z):
+    self._barrier(lambda v: v * complex(z))
+
+  def project_bit(self, logical_bit, value):
+    self.project_bits(1 << logical_bit, value << logical_bit)
+
+  def project_bits(self, mask, value):
+    self._barrier(lambda v: np.where(np_keep(v.size, mask, value), v, 0))
+
+  # -- readers -------------------------------------------------------------------------------------------------------------------
+  def _read(self, kernels=1):
+    self.flush()
+    self.kernels += kernels
+    return self.to_logical()
+
+  def _model(self, vec=None):
+    m = ModelState()
+    m.put(0, self._read(0) if vec is None else vec, self.nbits_global, self.held())
+    return m
+
+  def norm2(self):
+    return self._model(self._read()).norm(0)
+
+  def prob_bit(self, logical_bit, value=1):
+    return self._model(self._read())._prob_bit({'h': 0, 'bit': logical_bit, 'value': value})
+
+  def marginal(self, bits):
+    bits = [int(b) for b in bits]
+    if len(set(bits)) != len(bits):
+      raise native.QhError(native.QH_ERR_SAME_QUBIT, 'marginal: a bit twice')
+    return self._marginal(self._read(), bits)
+
+  def _marginal(self, vec, bits):
+    return np_marginal(vec, bits)
+
+  def sample(self, u):
+    u = np.asarray(u, dtype=np.float64)
+    if np.any(np.diff(u) < 0):
+      raise native.QhError(native.QH_ERR_ARG, 'sample: u is not ascending')
+    self.flush()
+    self.kernels += 2
+    a = self.phys.astype(np.complex128)
+    p = a.real ** 2 + a.imag ** 2
+    cdf = np.cumsum(p)
+    i = np.minimum(np.searchsorted(cdf, u * cdf[-1], side='right'), np.flatnonzero(p)[-1])
+    return self._lidx()[i].astype(np.uint64)
+
+  def expect_pauli(self, xmasks, zmasks):
+    reads = {}
+    for x in xmasks:
+      reads[int(x)] = reads.get(int(x), 0) + 1
+    vec = self._read(sum(-(-c // 16) for c in reads.values()))
+    return np.array([np_expect(vec, x, z) for x, z in zip(xmasks, zmasks)], dtype=np.float64)
+
+  def argmax(self):
+    return self._model(self._read())._argmax({'h': 0})
+
+  def amplitude(self, logical_index):
+    return self.dtype(self._read(0)[int(logical_index)])
+
+  def amplitudes(self, indices, nlocal=False):
+    return self._read(0)[np.asarray(indices, dtype=np.int64)]
+
+  def select(self, threshold, cap=1 << 16):
+    idx, amp, n, w = self._select(self._model(self._read()), threshold)
+    if n > cap:
+      return np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.complex128), n, w
+    return idx, amp, n, w
+
+  def _select(self, m, threshold):
+    return m._select({'h': 0, 'threshold': threshold})
+
+  def topk(self, k):
+    return self._topk(self._model(self._read(2)), k)
+
+  def _topk(self, m, k):
+    return m._topk({'h': 0, 'k': k})
+
+  # -- handles -------------------------------------------------------------------------------------------------------------------
+  def _sibling(self, nbits, nglob, bm, vec):
+    o = NumpyDevice(nbits, self.bit_width)
+    o.__class__ = self.__class__                           # (a mutant's handles are mutants)
+    o.nbits_global, o.shard, o.bm = nglob, self.shard, list(bm)
+    o.store(vec)
+    return o
+
+  def clone(self):
+    self.flush()
+    o = self._sibling(self.nbits, self.nbits_global, self._clone_bitmap(), np.zeros(1 << self.nbits_global))
+    o.phys = self.phys.copy()
+    return o
+
+  def _clone_bitmap(self):
+    return self.bm
+
+  def copy_from(self, other):
+    if other is self:
+      raise native.QhError(native.QH_ERR_ARG, 'copy: dst == src')
+    other.flush()
+    self._copy_queue()
+    self.phys, self.bm = other.phys.copy(), list(other._clone_bitmap())
+
+  def _copy_queue(self):
+    self.queue = []
+
+  def extend(self, nqubits, amps=None, basis=0):
+    k = int(nqubits)
+    if amps is None and basis >= 1 << k:
+      raise native.QhError(native.QH_ERR_ARG, 'extend: basis state out of range')
+    self.flush()
+    f = np.zeros(1 << k, dtype=np.complex128)
+    if amps is None:
+      f[basis] = 1
+    else:
+      f[:] = amps
+    self.kernels += 1
+    return self._sibling(self.nbits + k, self.nbits_global + k, self._extend_bitmap(k), self._extend_vec(self.to_logical(), f))
+
+  def _extend_vec(self, vec, f):
+    return np_extend(vec, f)
+
+  def _extend_bitmap(self, k):
+    return list(range(self.nbits, self.nbits + k)) + [p if p < self.nbits else p + k for p in self.bm]
+
+  def release(self, bits, value=0):
+    bits = [int(b) for b in bits]
+    if value >= 1 << len(bits):
+      raise native.QhError(native.QH_ERR_ARG, 'release: value out of range')
+    self.flush()
+    small, kept, dropped = np_release(self.to_logical(), bits, value)
+    self.kernels += 1
+    return self._sibling(self.nbits - len(bits), self.nbits_global - len(bits), self._release_bitmap(bits), small), kept, dropped
+
+  def _release_bitmap(self, bits):
+    gone = sorted(self.bm[b] for b in bits)
+    return [p - sum(1 for r in gone if r < p) for b, p in enumerate(self.bm) if b not in bits]
+
+  # -- two states ------------------------------------------------------------------------------------------------------------------
+  def inner_plan(self, other):
+    if self.bm == other.bm:
+      return {'path': LINEAR}
+    return {'path': TILES if self.nbits >= 8 else GATHER}
+
+  def inner(self, other):
+    self.flush()
+    other.flush()
+    self.kernels += 1
+    return complex(np.vdot(self.to_logical(), other.to_logical()))
+
+  def axpby(self, alpha, other, beta, norm=False):
+    if other is self:
+      raise native.QhError(native.QH_ERR_ARG, 'axpby: dst == src')
+    self.flush()
+    other.flush()
+    if not (complex(alpha) == 1 and complex(beta) == 0):
+      self.store(self._axpby(self.to_logical(), alpha, other.to_logical(), beta))
+      self.kernels += 1
+    a = self.phys.astype(np.complex128)
+    return float(np.vdot(a, a).real) if norm else None
+
+  def _axpby(self, d, alpha, s, beta):
+    return axpby_ref(d, alpha, s, beta)

@@ -1,0 +1,62 @@
+"""Random programs over the whole device API on the MI355X (tests/program_model.py): every fixed program, one per test item,
+in this process.  run_program holds every step to the NumPy model -- amplitudes read through a clone before and after the
+step, results, bit maps, pending counts, kernel counts -- and the final downloads to a model that never looked at the device.
+
+The last item reads what the earlier ones recorded from the real qh_get_bitmap / qh_inner_plan: relayout sweeps did leave a
+permuted local map in front of a barrier step or a reader in at least a third of the 'own' programs that start at 14 local
+bits or more, and all three paths of the two-state kernels were taken.  The CPU table (tests/test_program_fuzz_cpu.py) only
+predicts this.
+
+The figures recorded when the file was added (time, chain errors per program) are in HISTORY.md, section T1.
+"""
+import pytest
+
+from qcc_amd import native
+from tests import program_model as pm
+
+pytestmark = pytest.mark.gpu
+
+SEEN = {'own': 0, 'own_big': 0, 'own_big_relaid': 0, 'paths': set()}
+# the six 'own' programs that run again, two under each planner variant: (seed, width) whose first handle has sweeps that
+# re-lay out (checked below, so that a change of the generator cannot quietly empty the list)
+VARIANT_PROGRAMS = [(env, seed, bw) for env, pair in zip(pm.ENV_VARIANTS, ([(1, 128), (4, 64)], [(3, 128), (5, 64)], [(6, 128), (8, 64)]))
+                    for seed, bw in pair]
+
+
+def _run(mode, seed, bw):
+  prog = pm.gen_program(seed, bw, mode)
+  print(f'\n{mode}-{seed}-c{bw} ', end='')                  # (with -s: the chain figures of run_program follow on this line)
+  check = pm.run_program(prog, pm.make_device_state, pm.Check(bw))
+  return prog, check
+
+
+@pytest.mark.parametrize('bw', [128, 64])
+@pytest.mark.parametrize('mode,seed', pm.FIXED, ids=[f'{m}-{s}' for m, s in pm.FIXED])
+def test_program(mode, seed, bw):
+  prog, check = _run(mode, seed, bw)
+  if mode == 'own':
+    SEEN['own'] += 1
+    SEEN['paths'] |= {e[4] for e in check.events if e[4] is not None}
+    if prog[0]['nloc'] >= pm.PERMUTED_FROM:
+      SEEN['own_big'] += 1
+      SEEN['own_big_relaid'] += check.relaid > 0
+
+
+@pytest.mark.parametrize('env,seed,bw', VARIANT_PROGRAMS,
+                         ids=['-'.join(f'{k}={v}' for k, v in e.items()) + f'-{sd}-c{w}' for e, sd, w in VARIANT_PROGRAMS])
+def test_program_under_planner_variants(env, seed, bw, monkeypatch):
+  for k, v in env.items():
+    monkeypatch.setenv(k, v)                                # (the planner reads its switches at every flush)
+  prog, check = _run('own', seed, bw)
+  assert prog[0]['nloc'] >= pm.PERMUTED_FROM
+  if env.get('QH_RELAYOUT') == '0':
+    assert check.relaid == 0                                # no flush re-laid a handle out: clones and siblings decide as told
+
+
+def test_zz_relayout_and_inner_paths_were_met():
+  if not SEEN['own']:
+    pytest.skip('reads what the program items of this file recorded: run the file as a whole')
+  print(f"'own' programs from {pm.PERMUTED_FROM} local bits: {SEEN['own_big']}, re-laid out in front of a barrier or reader: "
+        f"{SEEN['own_big_relaid']}; inner paths {sorted(SEEN['paths'])}")
+  assert 3 * SEEN['own_big_relaid'] >= SEEN['own_big'] > 0
+  assert SEEN['paths'] == {native.QH_INNER_LINEAR, native.QH_INNER_TILES, native.QH_INNER_GATHER}

@@ -17,9 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from qcc_amd import device, gates, native  # noqa: E402
 from tests import oracle_lib  # noqa: E402
 
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-orc = oracle_lib.load()
+orc = None                     # the CPU oracle, loaded by main() (tests/program_model.py imports the gate pools only)
 NO = oracle_lib.NO_CTL
 argmax_bad = []
 
@@ -119,13 +117,22 @@ def one_case(rng, case):
   return ok, n, s['sweeps']
 
 
-t0 = time.time()
-case = fails = 0
-while time.time() - t0 < budget:
-  rng = np.random.default_rng(seed0 * 100003 + case)
-  ok, n, sw = one_case(rng, case)
-  fails += not ok
-  case += 1
-print(json.dumps({'cases': case, 'failures': fails, 'seconds': round(time.time() - t0, 1), 'seed': seed0,
-                  'env': {k: v for k, v in os.environ.items() if k.startswith('QH_')}}))
-sys.exit(1 if fails else 0)
+def main():
+  global orc
+  budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
+  seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+  orc = oracle_lib.load()
+  t0 = time.time()
+  case = fails = 0
+  while time.time() - t0 < budget:
+    rng = np.random.default_rng(seed0 * 100003 + case)
+    ok, n, sw = one_case(rng, case)
+    fails += not ok
+    case += 1
+  print(json.dumps({'cases': case, 'failures': fails, 'seconds': round(time.time() - t0, 1), 'seed': seed0,
+                    'env': {k: v for k, v in os.environ.items() if k.startswith('QH_')}}))
+  sys.exit(1 if fails else 0)
+
+
+if __name__ == '__main__':
+  main()
