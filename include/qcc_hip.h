@@ -151,6 +151,48 @@ int qh_apply_mux(qh_handle h, int k, const int32_t *sel_bits, int tgt_bit, const
  * be held by the shard index).  k = 0 is qh_scale.  Otherwise as qh_apply_mux.                                        */
 int qh_apply_diag(qh_handle h, int k, const int32_t *bits, const double *values);
 
+/* Register permutation (kernels_perm.hip.h): |s> -> |table[s]> on the register made of LOGICAL bits bits[0..k-1] (bits[0]
+ * least significant, as in qh_apply_diag), 1 <= k <= QH_PERM_MAX_BITS.  table: 2^k entries, a bijection of [0, 2^k).  For
+ * every index i whose bits under ctl_mask are all 1, with register value s(i): new[i with register := table[s]] = old[i];
+ * every other amplitude stays where it is.  Amplitudes are moved as stored: no arithmetic, bit-for-bit at both widths.
+ * A barrier like qh_apply_mux: what is queued runs first, and the call works on the layout it finds.  The caller's table is
+ * not referenced after the call returns.  Bit map, relayout mode and device pointer are as before.
+ * Two paths (qh_perm_tiles below): tiles that fit LDS are permuted in place, one read and one write of the tiles whose
+ * controls are met; larger tiles go through a second buffer of the state's size (the relayout buffer where the handle has
+ * one, otherwise a temporary: QH_ERR_NOMEM, state unchanged, when there is no room) and are copied back.
+ * qh_stats: gates_submitted + 1, kernels_launched + 1, bytes_algorithmic + 2 x the shard's bytes / 2^(local controls),
+ * bytes_swept + what was read and written (the second path: the state twice read and twice written).
+ * A control on a shard bit is dropped where met, and the call is a counted no-op (gates_noop) where not.
+ * Errors, nothing runs and nothing changes: QH_ERR_ARG (null pointer, k out of range, dry handle, a table entry >= 2^k or a
+ * value hit twice: qh_last_error names the first offending entry), QH_ERR_BAD_QUBIT, QH_ERR_SAME_QUBIT (a bit twice, a
+ * control that is also a register bit), QH_ERR_NONLOCAL (a register bit held by the shard index: nothing is flushed).     */
+#define QH_PERM_MAX_BITS 16
+int qh_apply_perm(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, const uint32_t *table);
+/* How qh_apply_perm would walk the state right now (nothing runs, nothing is flushed; planner-only handles too).  Positions
+ * are physical, local.  A tile is the amplitudes that agree outside tile_mask: the register's positions, the positions inside
+ * a 128-byte line, padded with the lowest positions left to 10 bits; bit r of an in-tile index is the r-th lowest position of
+ * tile_mask, the remaining positions, ascending, number the tiles.  Controls inside the tile (ctl_in) are a predicate per
+ * amplitude; the tiles where a control outside it (ctl_out) is 0 are skipped.  QH_PERM_GATHER walks every amplitude of the
+ * state instead: there the tile only says why (lds_bytes above 128 KiB).  ctl_met = 0: a control held by the shard index is 0
+ * on this shard and the call would be a no-op.  Errors as qh_apply_perm, without those of the table and of dry handles.  */
+#define QH_PERM_LDS 0           /* in place, tile by tile through LDS                          */
+#define QH_PERM_GATHER 1        /* out of place: linear writes, gathered reads, copied back    */
+typedef struct {
+  uint32_t path;               /* QH_PERM_*                                                   */
+  uint32_t tile_bits;          /* bits of an in-tile index                                    */
+  uint64_t tile_mask;          /* positions of a tile's free bits                             */
+  uint64_t reg_mask;           /* positions of the register (all inside tile_mask)            */
+  uint64_t ctl_in, ctl_out;    /* positions of the local controls inside / outside the tile   */
+  uint64_t ntiles;             /* 2^(nbits_local - tile_bits)                                 */
+  uint64_t tiles_skipped;      /* of those, the tiles where a control of ctl_out is 0         */
+  uint64_t lds_bytes;          /* amplitudes of one tile, in bytes                            */
+  uint32_t ctl_met;            /* controls held by the shard index are all 1 on this shard    */
+  uint32_t k;
+  uint8_t reg_pos[QH_PERM_MAX_BITS];    /* position of register bit j                         */
+  uint8_t reg_rank[QH_PERM_MAX_BITS];   /* the bit of the in-tile index that stands for it    */
+} qh_perm_tiles;
+int qh_perm_plan(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, qh_perm_tiles *out);
+
 /* The whole stream in one call: ops[2k] = control qubit of gate k or QH_NO_CTL (then qh_apply1), ops[2k+1] =
  * target qubit, gates + 8k = its 8 doubles -- exactly `count` qh_apply1/qh_applyc calls (xgates.cc:89-145), without
  * the per-call cost of the host language's FFI (ctypes: ~3 us per gate).  Stops at the first error.          */

@@ -25,6 +25,8 @@
 #include "kernels_gate.hip.h"
 #include "kernels_dense.hip.h"
 #include "kernels_mux.hip.h"
+#include "kernels_perm.hip.h"
+#include "perm_plan.h"
 #include "kernels_measure.hip.h"
 #include "kernels_select.hip.h"
 #include "select_plan.h"
@@ -730,7 +732,7 @@ int select_device(int device) {
 extern "C" {
 
 const char *qh_last_error(void) { return g_err.c_str(); }
-int qh_version(void) { return 113; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
+int qh_version(void) { return 114; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
 
 int qh_device_count(int *count) {
   if (!count) return fail(QH_ERR_ARG, "null");
@@ -1739,6 +1741,189 @@ int qh_apply_diag(qh_handle h, int k, const int32_t *bits, const double *values)
   qh::TabArgs a{};
   a.nwork = 1ull << h->nloc;
   return run_tab(h, 2, t, 0x3full, 1, values, a);
+}
+
+}  // extern "C"
+
+// ---- register permutations: qh_apply_perm, qh_perm_plan (kernels_perm.hip.h, perm_plan.h) -----------------------------
+namespace {
+
+// The argument checks both calls share, then the tile (perm_plan.h) on the bit map as it is now.
+int plan_perm_call(const qh_state_s *h, const char *who, int k, const int32_t *bits, uint64_t ctl_mask, qh_perm_tiles *out) {
+  if (k < 1 || k > QH_PERM_MAX_BITS) return fail(QH_ERR_ARG, "%s: k = %d outside [1,%d]", who, k, QH_PERM_MAX_BITS);
+  if (h->nglob < 64 && (ctl_mask >> h->nglob))
+    return fail(QH_ERR_BAD_QUBIT, "%s: control mask 0x%llx has bits >= %d", who, (unsigned long long)ctl_mask, h->nglob);
+  uint64_t rmask = 0;
+  const int rc = check_bit_list(h, who, k, bits, &rmask);
+  if (rc) return rc;
+  if (ctl_mask & rmask)
+    return fail(QH_ERR_SAME_QUBIT, "%s: control and register share bits 0x%llx", who, (unsigned long long)(ctl_mask & rmask));
+  // (a logical bit stays local or in the shard index whatever the relayout sweeps do)
+  int pos[QH_PERM_MAX_BITS];
+  for (int j = 0; j < k; ++j) {
+    pos[j] = h->perm[bits[j]];
+    if (pos[j] >= h->nloc)
+      return fail(QH_ERR_NONLOCAL, "%s: register bit %d is held by the shard index (physical bit %d, local bits: %d); exchange first",
+                  who, bits[j], pos[j], h->nloc);
+  }
+  const Placed ctl = place(h, to_phys(h, ctl_mask));
+  qh::plan_perm_tiles(h->nloc, h->bw, k, pos, ctl.local, out);
+  out->k = (uint32_t)k;
+  out->ctl_met = (h->shard & ctl.held) == ctl.held;
+  return QH_OK;
+}
+
+// `bytes` of table through the handle's staging pair (the one qh_apply_mux / qh_apply_diag use)
+int stage_perm_table(qh_state_s *h, const void *src, size_t bytes, const void **dev) {
+  size_t cap = 64u << 10;
+  while (cap < bytes) cap *= 2;
+  char *host = nullptr, *d = nullptr;
+  unsigned slot = 0;
+  const int rc = acquire(h, h->tab, cap, "qh_apply_perm", &host, &d, &slot);
+  if (rc) return rc;
+  memcpy(host, src, bytes);
+  HIP_TRY(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, h->stream));
+  *dev = d;
+  return QH_OK;
+}
+
+// a block may declare more than 64 KiB of LDS only after the kernel has been told so (on the device that is current)
+template <typename R> int allow_big_lds() {
+  const hipError_t e =
+      hipFuncSetAttribute((const void *)qh::k_perm_lds<R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(QH_ERR_HIP, "apply_perm: hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(e));
+  }
+  return QH_OK;
+}
+
+int run_perm_lds(qh_state_s *h, const qh_perm_tiles &t, const std::vector<uint32_t> &inv) {
+  const int k = (int)t.k;
+  uint8_t ranks[QH_PERM_MAX_BITS];
+  memcpy(ranks, t.reg_rank, sizeof ranks);
+  std::sort(ranks, ranks + k);
+  qh::PermArgs a{};
+  a.g.n = qh::perm_runs(k, ranks, a.g.run);
+  a.tile_mask = t.tile_mask;
+  a.rest_mask = h->local_mask() & ~t.tile_mask & ~t.ctl_out;
+  a.ctl_out = t.ctl_out;
+  a.ntiles = t.ntiles - t.tiles_skipped;
+  a.m = t.tile_bits;
+  a.nent = 1u << k;
+  for (int p = 0, r = 0; p < h->nloc; ++p) {
+    if (!((t.tile_mask >> p) & 1ull)) continue;
+    if ((t.reg_mask >> p) & 1ull) a.reg_tile |= 1u << r;
+    if ((t.ctl_in >> p) & 1ull) a.ctl_tile |= 1u << r;
+    ++r;
+  }
+  std::vector<uint16_t> tab(a.nent);
+  for (uint32_t c = 0; c < a.nent; ++c) tab[c] = (uint16_t)qh::perm_deposit(inv[c], k, ranks);
+  const size_t lds = (size_t)t.lds_bytes + tab.size() * sizeof(uint16_t);
+  const uint64_t nitems = t.lds_bytes / 16;
+  unsigned threads = 64;                                   // four items per thread (eight in the largest tiles), one to sixteen waves
+  while (threads < 1024 && threads * 4ull < nitems) threads *= 2;
+  if ((uint64_t)threads * qh::kPermItems < nitems) return fail(QH_ERR_ARG, "apply_perm: a tile of %llu items", (unsigned long long)nitems);
+  int rc = QH_OK;
+  if (lds > (64u << 10)) with_real(h, [&](auto x) { rc = allow_big_lds<decltype(x)>(); });
+  if (rc) return rc;
+  const void *dtab = nullptr;
+  if ((rc = stage_perm_table(h, tab.data(), tab.size() * sizeof(uint16_t), &dtab))) return rc;
+  // every block stages the table first and grid-strides over the tiles (QH_PERM_GRID: another cap, read at every call)
+  const unsigned grid = (unsigned)std::min<uint64_t>(a.ntiles, (uint64_t)std::max(1, env_int("QH_PERM_GRID", 2048)));
+  with_real(h, [&](auto x) {
+    using R = decltype(x);
+    hipLaunchKernelGGL(qh::k_perm_lds<R>, dim3(grid), dim3(threads), lds, h->stream, (typename qh::AmpT<R>::type *)h->d_psi,
+                       (const uint16_t *)dtab, a);
+  });
+  if ((rc = check_launch(h))) return rc;
+  HIP_TRY(h->tab.commit(h->stream, 0));
+  h->stats.gates_submitted++;
+  count_kernel(h, 1ull << (h->nloc - __builtin_popcountll(t.ctl_in | t.ctl_out)), a.ntiles << t.tile_bits);
+  return QH_OK;
+}
+
+int run_perm_gather(qh_state_s *h, const qh_perm_tiles &t, const std::vector<uint32_t> &inv) {
+  const int k = (int)t.k;
+  uint8_t pos[QH_PERM_MAX_BITS];
+  memcpy(pos, t.reg_pos, sizeof pos);
+  std::sort(pos, pos + k);
+  qh::PermGatherArgs a{};
+  a.g.n = qh::perm_runs(k, pos, a.g.run);
+  a.reg_mask = t.reg_mask;
+  a.ctl = t.ctl_in | t.ctl_out;
+  const size_t bytes = (size_t)h->amp_bytes() << h->nloc;
+  a.nitems = bytes / 16;
+  std::vector<uint64_t> tab((size_t)1 << k);
+  for (size_t c = 0; c < tab.size(); ++c) tab[c] = qh::perm_deposit(inv[c], k, pos);
+  // the second buffer: the one relayout sweeps keep, or a temporary that goes when this call returns
+  qh::DeviceBuffer tmp;
+  void *scratch = h->d_alt;
+  if (!scratch) {
+    if (tmp.reserve(bytes) != hipSuccess)
+      return fail(QH_ERR_NOMEM, "apply_perm: no room for the second buffer of %llu bytes that a register of %d bits on these positions "
+                  "needs (the state is unchanged)", (unsigned long long)bytes, k);
+    scratch = tmp.ptr;
+  }
+  const void *dtab = nullptr;
+  int rc = stage_perm_table(h, tab.data(), tab.size() * sizeof(uint64_t), &dtab);
+  if (rc) return rc;
+  with_real(h, [&](auto x) {
+    using R = decltype(x);
+    using A = typename qh::AmpT<R>::type;
+    hipLaunchKernelGGL(qh::k_perm_gather<R>, dim3(grid_for(a.nitems, 1ull << 16)), dim3(256), 0, h->stream, (const A *)h->d_psi,
+                       (A *)scratch, (const uint64_t *)dtab, a);
+  });
+  rc = check_launch(h);
+  if (rc == QH_OK) {
+    hipError_t e = h->tab.commit(h->stream, 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->d_psi, scratch, bytes, hipMemcpyDeviceToDevice, h->stream);
+    if (e != hipSuccess) rc = fail(QH_ERR_HIP, "apply_perm: %s", hipGetErrorString(e));
+  }
+  if (tmp.ptr) {                                           // (the kernel and the copy still use it)
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess && rc == QH_OK) rc = fail(QH_ERR_HIP, "apply_perm: %s", hipGetErrorString(e));
+  }
+  if (rc) return rc;
+  h->stats.gates_submitted++;
+  count_kernel(h, 1ull << (h->nloc - __builtin_popcountll(a.ctl)), 1ull << h->nloc);
+  h->stats.bytes_swept += 2 * bytes;                       // the copy back
+  return QH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qh_perm_plan(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, qh_perm_tiles *out) {
+  if (!h || !bits || !out) return fail(QH_ERR_ARG, "perm_plan: null handle, bits or out");
+  return plan_perm_call(h, "perm_plan", k, bits, ctl_mask, out);
+}
+
+int qh_apply_perm(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, const uint32_t *table) {
+  if (!h || !bits || !table) return fail(QH_ERR_ARG, "apply_perm: null handle, bits or table");
+  qh_perm_tiles t;
+  int rc = plan_perm_call(h, "apply_perm", k, bits, ctl_mask, &t);
+  if (rc) return rc;
+  int64_t other = -1;
+  const int64_t bad = qh::perm_check_table(k, table, &other);
+  if (bad >= 0 && other < 0)
+    return fail(QH_ERR_ARG, "apply_perm: table[%lld] = %u is outside [0,%u): not a permutation of the register's values",
+                (long long)bad, table[bad], 1u << k);
+  if (bad >= 0)
+    return fail(QH_ERR_ARG, "apply_perm: table[%lld] = %u is hit twice (table[%lld] has the same value): not a bijection",
+                (long long)bad, table[bad], (long long)other);
+  if ((rc = enter(h))) return rc;          // a barrier: what is queued runs first, on whatever layout it leaves
+  if ((rc = plan_perm_call(h, "apply_perm", k, bits, ctl_mask, &t))) return rc;
+  if (!t.ctl_met) {                        // a shard-bit control that is 0 on this shard (met: dropped)
+    h->stats.gates_submitted++;
+    h->stats.gates_noop++;
+    return QH_OK;
+  }
+  int order[QH_PERM_MAX_BITS];
+  qh::perm_order(k, t.reg_pos, order);
+  const std::vector<uint32_t> inv = qh::perm_inverse(k, table, order);
+  return t.path == QH_PERM_LDS ? run_perm_lds(h, t, inv) : run_perm_gather(h, t, inv);
 }
 
 }  // extern "C"

@@ -228,6 +228,25 @@ class DeviceState:
       raise ValueError(f'apply_diag: values of shape {v.shape} for {k} bits (want ({1 << k},))')
     native.check(self.lib.qh_apply_diag(self.h, k, b.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), v.ctypes.data_as(_dp)))
 
+  def apply_perm(self, table, bits, ctl_mask=0):
+    """|s> -> |table[s]> on the register of LOGICAL bits `bits` (bits[0] the least significant bit of s) where every bit of
+    ctl_mask is 1 (qh_apply_perm): `table` is a bijection of range(2^k), 1 <= k <= 16.  Amplitudes are moved, not computed."""
+    b = np.ascontiguousarray([int(x) for x in bits], dtype=np.int32)
+    k = len(b)
+    t = np.asarray(table)
+    if t.shape != (1 << k,) or np.any(t < 0) or np.any(t >= 1 << 32):
+      raise ValueError(f'apply_perm: a table of shape {t.shape} for {k} bits (want ({1 << k},) of non-negative integers)')
+    t = np.ascontiguousarray(t, dtype=np.uint32)
+    native.check(self.lib.qh_apply_perm(self.h, k, b.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(ctl_mask),
+                                        t.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+
+  def perm_plan(self, bits, ctl_mask=0):
+    """How apply_perm on these bits would walk the state right now (qh_perm_plan), as a dict."""
+    b = np.ascontiguousarray([int(x) for x in bits], dtype=np.int32)
+    t = native.QhPermTiles()
+    native.check(self.lib.qh_perm_plan(self.h, len(b), b.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(ctl_mask), ctypes.byref(t)))
+    return t.as_dict()
+
   def apply_bits_raw(self, ctl_mask, tgt_bit, addr):
     """apply_bits with the gate given as the address of 8 contiguous doubles."""
     rc = self.lib.qh_apply_bits(self.h, ctl_mask, tgt_bit, ctypes.cast(addr, _dp))

@@ -657,10 +657,10 @@ class qc:
 
     # table-selected gates (extensions with the standing of apply_matrix: eager, one kernel each on the device).  In all
     # four the FIRST listed qubit is the most significant bit of the table index (np.kron order, as apply_matrix).
-    def _table_device(self, who, method, qubits, nentries, tgt=None):
+    def _table_device(self, who, method, qubits, nentries, tgt=None, ctl=()):
         """Checks the qubit lists, drains what is queued and returns (device, logical bits, least significant first)."""
         qubits = [int(q) for q in qubits]
-        every = qubits + ([int(tgt)] if tgt is not None else [])
+        every = qubits + ([int(tgt)] if tgt is not None else []) + [int(c) for c in ctl]
         if len(qubits) > _TABLE_MAX_BITS:
             raise ValueError(f'{who}: {len(qubits)} selection qubits (at most {_TABLE_MAX_BITS})')
         if nentries != 1 << len(qubits):
@@ -721,6 +721,64 @@ class qc:
             raise ValueError(f'phase_oracle: {len(xs)} input qubits (at most {_TABLE_MAX_BITS})')
         t = self._truth_table(f, len(xs))
         self.diagonal(1.0 - 2.0 * t, xs)
+
+    # register permutations (reversible classical arithmetic): amplitudes moved by a table, one call each, exact to the bit
+    def permutation(self, table, qubits, ctl=()):
+        """|s> -> |table[s]> on the register `qubits` (qubits[0] the most significant bit of s) where every qubit of `ctl`
+        is 1.  table: a bijection of range(2^k) as a sequence, or a callable on ints evaluated 2^k times on the host."""
+        qubits, ctl = list(qubits), list(ctl)
+        k = len(qubits)
+        if not 1 <= k <= _TABLE_MAX_BITS:
+            raise ValueError(f'permutation: {k} register qubits (1 to {_TABLE_MAX_BITS})')
+        t = np.array([int(table(s)) for s in range(1 << k)] if callable(table) else [int(v) for v in table], dtype=np.int64)
+        if t.shape != (1 << k,):
+            raise ValueError(f'permutation: a table of {t.shape[0]} entries for {k} qubits (want {1 << k})')
+        if np.any(t < 0) or np.any(t >= 1 << k) or np.unique(t).shape[0] != 1 << k:
+            seen = {}
+            for s, v in enumerate(t.tolist()):
+                if not 0 <= v < 1 << k or v in seen:
+                    raise ValueError(f'permutation: table[{s}] = {v} is out of range or already hit: not a bijection of range({1 << k})')
+                seen[v] = s
+        dev, bits = self._table_device('permutation', 'apply_perm', qubits, t.shape[0], ctl=ctl)
+        mask = 0
+        for c in ctl:
+            mask |= 1 << (self._nbits - 1 - int(c))
+        dev.apply_perm(t, bits, mask)
+        self._gate_done()
+
+    def add_const(self, a, reg, ctl=()):
+        """x -> (x + a) mod 2^k on the register `reg` (reg[0] most significant); a may be negative."""
+        size = 1 << len(list(reg))
+        self.permutation((np.arange(size, dtype=np.int64) + int(a)) % size, reg, ctl)
+
+    def modadd(self, a, N, reg, ctl=()):
+        """x -> (x + a) mod N for x < N, identity for x >= N."""
+        reg = list(reg)
+        a, N, size = int(a), int(N), 1 << len(reg)
+        if not 1 <= N <= size:
+            raise ValueError(f'modadd: N = {N} outside [1, 2^{len(reg)}]')
+        x = np.arange(size, dtype=np.int64)
+        self.permutation(np.where(x < N, (x + a) % N, x), reg, ctl)
+
+    def modmul(self, a, N, reg, ctl=()):
+        """x -> a x mod N for x < N, identity for x >= N; gcd(a, N) must be 1 and N at most 2^k."""
+        reg = list(reg)
+        a, N, size = int(a), int(N), 1 << len(reg)
+        if not 1 <= N <= size:
+            raise ValueError(f'modmul: N = {N} outside [1, 2^{len(reg)}]')
+        if math.gcd(a, N) != 1:
+            raise ValueError(f'modmul: gcd({a}, {N}) != 1: x -> {a} x mod {N} is not reversible')
+        x = np.arange(size, dtype=np.int64)
+        self.permutation(np.where(x < N, (x * (a % N)) % N, x), reg, ctl)
+
+    def add(self, src, dst):
+        """|a>|b> -> |a>|(a + b) mod 2^len(dst)>, a on the qubits `src`, b on `dst`: one permutation of both registers."""
+        src, dst = list(src), list(dst)
+        if len(src) + len(dst) > _TABLE_MAX_BITS:
+            raise ValueError(f'add: {len(src)} + {len(dst)} qubits (at most {_TABLE_MAX_BITS})')
+        s = np.arange(1 << (len(src) + len(dst)), dtype=np.int64)
+        a, b = s >> len(dst), s & ((1 << len(dst)) - 1)
+        self.permutation((a << len(dst)) | ((a + b) & ((1 << len(dst)) - 1)), src + dst)
 
     # ------------------------------------------------------------------ readers / measurement
     def maxprob(self):

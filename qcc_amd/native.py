@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB_PATH = os.environ.get('QCC_HIP_LIB') or os.path.join(PKG, 'libqcc_hip.so')  # env: A/B builds only
 SOURCES = [os.path.join(PKG, 'csrc', f) for f in
-           ('engine.hip', 'buffers.hip.h', 'kernels_gate.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_measure.hip.h', 'kernels_select.hip.h', 'select_plan.h', 'kernels_expect.hip.h', 'kernels_inner.hip.h', 'kernels_axpby.hip.h', 'inner_plan.h', 'kernels_resize.hip.h', 'resize_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h', 'exchange_plan.h',
+           ('engine.hip', 'buffers.hip.h', 'kernels_gate.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_perm.hip.h', 'perm_plan.h', 'kernels_measure.hip.h', 'kernels_select.hip.h', 'select_plan.h', 'kernels_expect.hip.h', 'kernels_inner.hip.h', 'kernels_axpby.hip.h', 'inner_plan.h', 'kernels_resize.hip.h', 'resize_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h', 'exchange_plan.h',
             'sweep_island_rb2.inc', 'sweep_island_rb3.inc', 'sweep_island_rb4.inc',
             'sweep_island_rb5.inc', 'sweep_island_f32_rb2.inc', 'sweep_island_f32_rb3.inc',
             'sweep_island_f32_rb4.inc', 'sweep_island_f32_rb5.inc', 'sweep_island_f32_rb6.inc', 'sweep_handlers.inc',
@@ -45,6 +45,21 @@ class QhInnerTiles(ctypes.Structure):
   _fields_ = [('path', ctypes.c_uint32), ('nrest', ctypes.c_uint32), ('free_a', _u64), ('free_b', _u64),
               ('tile_a', _u8 * 8), ('tile_b', _u8 * 8), ('shuffle', _u8 * 8), ('rest_a', _u8 * 56), ('rest_b', _u8 * 56),
               ('pos_b', _u8 * 64)]
+
+  def as_dict(self):
+    return {k: (int(getattr(self, k)) if isinstance(getattr(self, k), int) else list(getattr(self, k))) for k, _ in self._fields_}
+
+
+QH_PERM_MAX_BITS = 16
+QH_PERM_LDS, QH_PERM_GATHER = 0, 1
+
+
+class QhPermTiles(ctypes.Structure):
+  """include/qcc_hip.h qh_perm_tiles: how qh_apply_perm walks the state."""
+  _u8 = ctypes.c_uint8
+  _fields_ = [('path', ctypes.c_uint32), ('tile_bits', ctypes.c_uint32), ('tile_mask', _u64), ('reg_mask', _u64),
+              ('ctl_in', _u64), ('ctl_out', _u64), ('ntiles', _u64), ('tiles_skipped', _u64), ('lds_bytes', _u64),
+              ('ctl_met', ctypes.c_uint32), ('k', ctypes.c_uint32), ('reg_pos', _u8 * 16), ('reg_rank', _u8 * 16)]
 
   def as_dict(self):
     return {k: (int(getattr(self, k)) if isinstance(getattr(self, k), int) else list(getattr(self, k))) for k, _ in self._fields_}
@@ -83,6 +98,8 @@ SIGNATURES = {
     'qh_apply_matrix': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _u64, _dp]),
     'qh_apply_mux': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _i32, _dp]),
     'qh_apply_diag': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _dp]),
+    'qh_apply_perm': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _u64, ctypes.POINTER(ctypes.c_uint32)]),
+    'qh_perm_plan': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _u64, ctypes.POINTER(QhPermTiles)]),
     'qh_set_fusion': (_i32, [_vp, _i32]),
     'qh_set_relayout': (_i32, [_vp, _i32, ctypes.POINTER(_i32)]),
     'qh_apply_stream': (_i32, [_vp, _u64, ctypes.POINTER(ctypes.c_int32), _dp]),
