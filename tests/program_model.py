@@ -15,7 +15,8 @@ two logical bits whose positions are exchanged, the runner looks the positions u
 
 References are imported, not copied: tests/oracle_lib (gates), fake_device.np_marginal / np_keep, resize_util.np_extend /
 np_release, select_util.np_select / np_topk / fma_probs, test_dense_cpu.dense_reference, test_mux_cpu.mux_reference_fast /
-diag_reference, test_expect_cpu.np_expect, shard_util.check_exact_cdf (the inverse CDF of qh_sample in physical order)."""
+diag_reference, test_expect_cpu.np_expect, test_perm_cpu.perm_reference (and the tile rule of qh_perm_plan it states),
+shard_util.check_exact_cdf (the inverse CDF of qh_sample in physical order)."""
 import os
 import sys
 
@@ -29,6 +30,7 @@ from tests.select_util import fma_probs, np_select, np_topk
 from tests.test_dense_cpu import dense_reference
 from tests.test_expect_cpu import np_expect
 from tests.test_mux_cpu import diag_reference, mux_reference_fast
+from tests.test_perm_cpu import LDS_BUDGET, _expected_tile, perm_reference
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools'))
 import fuzz_parity  # noqa: E402  (the gate pools and the control-density logic of the gate fuzzer)
@@ -40,7 +42,7 @@ MAX_BITS = 20                 # the largest state of a program: 2^20 amplitudes
 MAX_LIVE = 4
 LINEAR, TILES, GATHER = native.QH_INNER_LINEAR, native.QH_INNER_TILES, native.QH_INNER_GATHER
 
-BARRIERS = ('matrix', 'mux', 'diag', 'scale', 'project_bit', 'project_bits')
+BARRIERS = ('matrix', 'mux', 'diag', 'perm', 'scale', 'project_bit', 'project_bits')
 READERS = ('norm2', 'prob_bit', 'marginal', 'sample', 'expect', 'argmax', 'amplitude', 'amplitudes', 'select', 'topk')
 HANDLE_STEPS = ('clone', 'copy', 'extend', 'release', 'close')
 TWO_STATE = ('inner', 'axpby')
@@ -50,8 +52,9 @@ KINDS = ('gates',) + BARRIERS + READERS + HANDLE_STEPS + TWO_STATE + LAYOUT_STEP
 
 # the fixed programs of the suite (tests/test_program_fuzz_cpu.py on NumpyDevice, tests/test_gpu_program_fuzz.py on the GPU),
 # each at both widths; the coverage table of the CPU test is what this seed list was chosen by
-FIXED = [('own', seed) for seed in list(range(21)) + [42, 48, 139]] + [('shard', seed) for seed in range(6)] + \
-        [('attached', seed) for seed in range(4)] + [('mapped', seed) for seed in range(4)]
+# (re-chosen when 'perm' became a kind: one stream draws the kinds, so a new kind changes every program of every seed)
+FIXED = [('own', seed) for seed in list(range(21)) + [42, 48, 60, 88, 92, 139]] + [('shard', seed) for seed in list(range(6)) + [15, 34, 54]] + \
+        [('attached', seed) for seed in list(range(4)) + [7]] + [('mapped', seed) for seed in range(4)]
 # planner variants of tests/test_gpu_fuzz.py, each on 'own' programs whose first handle is large enough for sweeps
 ENV_VARIANTS = [{'QH_RELAYOUT': '0'}, {'QH_WAVE_BITS': '2', 'QH_LANE_VALU': '2'}, {'QH_SEATS': '2', 'QH_WAVE_BITS': '1'}]
 
@@ -68,6 +71,32 @@ def close(got, want, bw):
   err = float(np.max(np.abs(got - want))) if got.size else 0.0
   lim = 1e-12 if bw == 128 else 1e-6 * max(float(np.max(want)) if want.size else 0.0, 1e-30) + 1e-9
   return None if err <= lim else f'off by {err:.3e} (limit {lim:.3e})'
+
+
+# ---- register permutations: which path a register of k bits can take (plan_perm_tiles of perm_plan.h) -------------------------
+# The tile is the register's positions plus the positions inside a 128-byte line (3 at complex128, 4 at complex64), padded to
+# min(10, nloc) bits; it goes through LDS while amp_bytes << tile_bits <= 128 KiB, i.e. up to 13 (14) tile bits.  So k <= 10 is
+# always LDS, k >= 14 (15) always gather, and in between the path depends on how many line positions hold register bits.
+PERM_MAX_BITS = native.QH_PERM_MAX_BITS
+PERM_BANDS = ('small', 'lds_edge', 'layout', 'gather')
+
+
+def perm_sure_gather(bw):
+  """the smallest k that takes the gather path on every layout"""
+  return 14 if bw == 128 else 15
+
+
+def perm_band(k, bw):
+  return 'small' if k <= 6 else 'lds_edge' if k <= 10 else 'layout' if k < perm_sure_gather(bw) else 'gather'
+
+
+def perm_tiles(nloc, bw, bm, shard, bits, ctl_mask):
+  """path, tile_bits, ctl_met and reg_pos of qh_perm_plan from a bit map, by the tile rule tests/test_perm_cpu.py states"""
+  reg_pos = [bm[b] for b in bits]
+  tile_bits = bin(_expected_tile(nloc, bw, reg_pos)).count('1')
+  path = native.QH_PERM_LDS if ((16 if bw == 128 else 8) << tile_bits) <= LDS_BUDGET else native.QH_PERM_GATHER
+  held = sum(1 << (bm[b] - nloc) for b in range(len(bm)) if (ctl_mask >> b) & 1 and bm[b] >= nloc)
+  return {'path': path, 'tile_bits': tile_bits, 'ctl_met': int((shard & held) == held), 'k': len(bits), 'reg_pos': reg_pos}
 
 
 TOL = 1e-12                   # TOL of tests/test_gpu_inner.py: readers that accumulate in double from the stored amplitudes
@@ -252,6 +281,10 @@ class ModelState:
   def _diag(self, s):
     self._mut(s['h'], lambda v: diag_reference(v, self.n[s['h']], s['values'], s['bits']))
 
+  def _perm(self, s):
+    # (on the vector of the GLOBAL size with the full control mask: a shard's vector is zero wherever a held control is 0)
+    self._mut(s['h'], lambda v: perm_reference(v, self.n[s['h']], s['table'], s['bits'], s['ctl']))
+
   def _scale(self, s):
     self._mut(s['h'], lambda v: v * complex(s['z']))
 
@@ -395,6 +428,25 @@ def _rand_op(rng, k, unitary):
 def _rand_table(rng, k):
   t = rng.standard_normal(1 << k) + 1j * rng.standard_normal(1 << k)
   return t / np.linalg.norm(t)
+
+
+def _rand_perm_table(rng, k):
+  """mostly a random bijection; now and then one with structure (long cycles, fixed points) that a random one rarely has"""
+  size, r = 1 << k, rng.random()
+  x = np.arange(size, dtype=np.int64)
+  if r < 0.7:
+    t = rng.permutation(size)
+  elif r < 0.8 or k == 1:
+    t = (x + int(rng.integers(1, size))) % size             # x + c mod 2^k: one cycle of length 2^k / gcd
+  elif r < 0.9:
+    big = int(rng.integers(3, size + 1))                     # a * x mod N below N, the identity from N on
+    a = int(rng.integers(1, big))
+    while np.gcd(a, big) != 1:
+      a = int(rng.integers(1, big))
+    t = np.where(x < big, (a * x) % big, x)
+  else:
+    t = sum(((x >> j) & 1) << (k - 1 - j) for j in range(k))   # bit reversal: 2^ceil(k/2) fixed points, the rest in pairs
+  return np.asarray(t, dtype=np.uint32)
 
 
 class _Gen:
@@ -555,6 +607,33 @@ class _Gen:
     bits = [int(b) for b in rng.choice(n, size=k, replace=False)]
     vals = np.exp(1j * rng.uniform(0, 6.28, 1 << k)) * (rng.uniform(0.8, 1.25, 1 << k) if rng.random() < 0.3 else 1.0)
     self.emit({'op': 'diag', 'h': h, 'bits': bits, 'values': vals})
+    return True
+
+  def k_perm(self):
+    rng, m = self.rng, self.m
+    h = self.pick(self.usable)
+    if h is None:
+      return False
+    loc, n = m.local_bits(h), m.n[h]
+    kmax, sure = min(PERM_MAX_BITS, len(loc)), perm_sure_gather(self.bw)
+    # the bands of perm_band, with equal weight where the handle is large enough for them; and the register that is the whole
+    # shard (one tile, no bit left to number the tiles)
+    bands = [(lo, min(hi, kmax)) for lo, hi in ((1, 6), (7, 10), (11, sure - 1), (sure, PERM_MAX_BITS)) if lo <= kmax]
+    if len(loc) <= PERM_MAX_BITS and rng.random() < 0.15:
+      k = len(loc)
+    else:
+      lo, hi = bands[int(rng.integers(len(bands)))]
+      k = int(rng.integers(lo, hi + 1))
+    bits = [int(b) for b in rng.choice(loc, size=k, replace=False)]
+    ctl = 0
+    others = [b for b in range(n) if b not in bits]          # (held bits included: dropped where met, a no-op where not)
+    if others and rng.random() < 0.5:
+      for c in rng.choice(others, size=min(len(others), int(rng.integers(1, 4))), replace=False):
+        ctl |= 1 << int(c)
+    held = sorted(m.held[h])
+    if held and rng.random() < 0.4:
+      ctl |= 1 << held[int(rng.integers(len(held)))]
+    self.emit({'op': 'perm', 'h': h, 'bits': bits, 'ctl': ctl, 'table': _rand_perm_table(rng, k)})
     return True
 
   def k_scale(self):
@@ -831,12 +910,18 @@ class _Gen:
     if h is None:
       return False
     loc = m.local_bits(h)
-    what = ('matrix_twice', 'mux_target_selected', 'marginal_twice', 'sample_descending', 'copy_self', 'axpby_self',
-            'extend_basis', 'release_value')[int(rng.integers(8))]
-    arg = 'same' if what in ('matrix_twice', 'mux_target_selected', 'marginal_twice') else 'arg'
+    whats = ['matrix_twice', 'mux_target_selected', 'marginal_twice', 'sample_descending', 'copy_self', 'axpby_self',
+             'extend_basis', 'release_value', 'perm_not_bijection', 'perm_control_in_register']
+    if m.held[h]:
+      whats.append('perm_register_held')                     # (a register bit on the shard index: nothing is flushed)
+    what = whats[int(rng.integers(len(whats)))]
+    code = native.QH_ERR_SAME_QUBIT if what in ('matrix_twice', 'mux_target_selected', 'marginal_twice', 'perm_control_in_register') \
+        else native.QH_ERR_NONLOCAL if what == 'perm_register_held' else native.QH_ERR_ARG
+    s = {'op': 'refused', 'h': h, 'what': what, 'code': code, 'bits': [int(loc[0]), int(loc[1])]}
+    if what == 'perm_register_held':
+      s['held'] = int(sorted(m.held[h])[int(rng.integers(len(m.held[h])))])
     self.refused += 1
-    self.emit({'op': 'refused', 'h': h, 'what': what, 'code': native.QH_ERR_SAME_QUBIT if arg == 'same' else native.QH_ERR_ARG,
-               'bits': [int(loc[0]), int(loc[1])]})
+    self.emit(s)
     return True
 
   WEIGHTS = {'gates': 9.0, 'close': 0.6, 'refused': 0.8, 'remap': 1.6, 'flush': 0.7, 'clone': 1.3, 'inner': 1.8, 'axpby': 1.8, 'copy': 1.3}
@@ -891,7 +976,9 @@ class Check:
 
   def __init__(self, bw):
     self.bw = bw
-    self.events = []            # (index, op, local bits out of canonical order, a queued burst ran in the step, inner path or None)
+    # (index, op, local bits out of canonical order, a queued burst ran in the step, inner path or None, the record of a
+    # 'perm' step or None: what qh_perm_plan said of the layout the call worked on, and what kind of handle it was)
+    self.events = []
     self.relaid = 0             # barrier / reader steps whose own flush re-laid the handle out
     self.chain_err = self.chain_d = self.chain_tol = None
     self.nloc0 = None
@@ -1047,6 +1134,8 @@ class _Runner:
       st.apply_mux(s['gates'], s['sel'], s['tgt'])
     elif op == 'diag':
       st.apply_diag(s['values'], s['bits'])
+    elif op == 'perm':
+      st.apply_perm(s['table'], s['bits'], s['ctl'])
     elif op == 'scale':
       st.scale(s['z'])
     elif op == 'project_bit':
@@ -1118,6 +1207,9 @@ class _Runner:
         'axpby_self': lambda: st.axpby(1, st, 1),
         'extend_basis': lambda: st.extend(1, None, 2),
         'release_value': lambda: st.release([a], 2),
+        'perm_not_bijection': lambda: st.apply_perm([0, 1, 1, 3], [a, b]),
+        'perm_control_in_register': lambda: st.apply_perm([0, 1, 2, 3], [a, b], 1 << b),
+        'perm_register_held': lambda: st.apply_perm([0, 1, 2, 3], [a, s.get('held')]),
     }
     try:
       calls[s['what']]()
@@ -1143,7 +1235,7 @@ class _Runner:
           mdl.step(s)
       self.need(_pending(self.dev[h]) == m.q[h], f'{_pending(self.dev[h])} gates pending behind the burst, expected {m.q[h]}')
       self.need(_bitmap(self.dev[h]) == bm_before[h], 'queueing gates changed the bit map')
-      self.check.events.append((self.i, op, not _canonical(bm_before[h], self.dev[h].nbits), False, None))
+      self.check.events.append((self.i, op, not _canonical(bm_before[h], self.dev[h].nbits), False, None, None))
       return
     if op == 'refused':
       k0 = self.kernels(h)
@@ -1152,7 +1244,7 @@ class _Runner:
                 'a refused call changed the queue, the bit map or launched a kernel')
       if quiet:
         self.need(self.read(h).tobytes() == m.wide(h).tobytes(), 'a refused call changed the state')
-      self.check.events.append((self.i, op, False, False, None))
+      self.check.events.append((self.i, op, False, False, None, None))
       return
     for x in involved:                                     # the mode, read without changing it, where a plan exists to show it
       if q_before[x] and self.dev[x].nbits >= SWEEPS_FROM and not m.wanted(x):
@@ -1164,19 +1256,21 @@ class _Runner:
     path = None
     if op in TWO_STATE and quiet:
       path = self.dev[h].inner_plan(self.dev[s['other']])['path']
+    stats0 = self.dev[h].stats() if op == 'perm' else None
     got = self.call(s)
     dk = {x: self.kernels(x) - k_before[x] for x in involved if x in self.dev}
     want = m.step(s)
+    perm = self.perm_record(s, q_before[h], bm_before[h]) if op == 'perm' else None      # (no call between: m is the model)
     for mdl in (self.chain, self.chain_r):
       if mdl is not None:
         mdl.step(s)
     if op == 'close':
-      self.check.events.append((self.i, op, False, False, None))
+      self.check.events.append((self.i, op, False, False, None, None))
       return
     if op == 'set_relayout' and s['on'] and q_before[h]:   # allocates, runs nothing: the burst stays queued (and unread)
       self.need(_pending(self.dev[h]) == q_before[h] and _bitmap(self.dev[h]) == bm_before[h], 'set_relayout(1) ran the queue')
       self.need(bool(got) == bool(want), f'set_relayout(1) answered {got}, the mode should be {int(want)}')
-      self.check.events.append((self.i, op, not _canonical(bm_before[h], self.dev[h].nbits), False, None))
+      self.check.events.append((self.i, op, not _canonical(bm_before[h], self.dev[h].nbits), False, None, None))
       return
     # every barrier: nothing is left queued -- on the destination of a copy because its queue was dropped
     for x in involved:
@@ -1234,7 +1328,10 @@ class _Runner:
         continue
       exact = quiet and (op in exact_ops or (op == 'extend' and (x == h or s['amps'] is None)) or
                          (op == 'axpby' and (x != h or (s['alpha'] == 1 and s['beta'] == 0))))
-      if exact:       # zero tolerance (array_equal: equal as numbers, the sign of a zero may differ)
+      if op == 'perm' and quiet:                           # "moved as stored": the same bytes, the sign of a zero included
+        self.need(after[x].tobytes() == w.tobytes(), f'handle {x}: a permutation did not move the amplitudes bit for bit '
+                  f'(max diff {float(np.max(np.abs(after[x] - w))):.3e}, {int(np.sum(np.signbit(after[x].view(np.float64)) != np.signbit(w.view(np.float64))))} signs differ)')
+      elif exact:     # zero tolerance (array_equal: equal as numbers, the sign of a zero may differ)
         self.need(np.array_equal(after[x], w), f'handle {x}: amplitudes changed where the header promises them as stored '
                   f'(max diff {float(np.max(np.abs(after[x] - w))):.3e})')
       else:
@@ -1280,11 +1377,30 @@ class _Runner:
         exp = {h: 0 if s['alpha'] == 1 and s['beta'] == 0 else 1, s['other']: 0}
       elif op in ('extend', 'release'):
         exp = {h: 1}
+      elif op == 'perm':                                   # one kernel on either path; a held control that is 0 here: none
+        exp = {h: perm['ctl_met']}
+        ds = {k: perm['stats'][k] - stats0[k] for k in ('gates_submitted', 'gates_noop')}
+        self.need(ds == {'gates_submitted': 1, 'gates_noop': 1 - perm['ctl_met']},
+                  f'apply_perm with ctl_met = {perm["ctl_met"]}: {ds}, the header says gates_submitted + 1 and gates_noop + {1 - perm["ctl_met"]}')
       if exp is not None:
         for x, e in exp.items():
           self.need(dk[x] == e, f'handle {x}: kernels_launched grew by {dk[x]}, the header says {e}')
     local_perm = not _canonical(bm_after[h], self.dev[h].nbits)
-    self.check.events.append((self.i, op, local_perm, bool(q_before[h]), path))
+    self.check.events.append((self.i, op, local_perm, bool(q_before[h]), path, perm))
+
+  def perm_record(self, s, queued, bm_before):
+    """What qh_perm_plan says of the step's bits right behind the call: the call does not move the bit map, so this is the
+    layout it worked on (the one its own flush left).  The plan is held to the bit map by the tile rule."""
+    h, st, m = s['h'], self.dev[s['h']], self.m
+    plan, bm = st.perm_plan(s['bits'], s['ctl']), _bitmap(st)
+    want = perm_tiles(st.nbits, self.bw, bm, self.shard[h], s['bits'], s['ctl'])
+    got = {k: (list(plan[k])[:len(s['bits'])] if k == 'reg_pos' else int(plan[k])) for k in want}
+    self.need(got == want, f'qh_perm_plan says {got}, the tile rule on bit map {bm} gives {want}')
+    ctl_held = sum(1 << b for b in m.held[h] if (s['ctl'] >> b) & 1)
+    return {'k': len(s['bits']), 'nloc': st.nbits, 'band': perm_band(len(s['bits']), self.bw), 'path': want['path'],
+            'tile_bits': want['tile_bits'], 'ctl_met': want['ctl_met'], 'ctl_local': bool(s['ctl'] & ~ctl_held), 'ctl_held': bool(ctl_held),
+            'shard': bool(m.held[h]), 'held_inside': bool(m.held[h]) and min(m.held[h]) < m.n[h] - len(m.held[h]),
+            'relayout_on': m.mode[h] == 1, 'relaid': bool(queued) and bm != bm_before and not _canonical(bm, st.nbits), 'stats': st.stats()}
 
   def results(self, s, got, want, after, bm_after):
     op, h, bw, st = s['op'], s['h'], self.bw, self.dev[s['h']]
@@ -1426,7 +1542,7 @@ class NumpyDevice:
     self.queue = []
     self.kind = kind
     self.relayout = -1                                     # undecided: the first fused flush decides (attached / mapped: off)
-    self.kernels = 0
+    self.kernels = self.submitted = self.noop = 0          # (submitted / noop: counted for apply_perm only)
     NumpyDevice._serial[0] += 1
     self.device_ptr = 0x1000 * NumpyDevice._serial[0]
     self.rng = np.random.default_rng(NumpyDevice._serial[0])
@@ -1465,7 +1581,7 @@ class NumpyDevice:
     return len(self.queue)
 
   def stats(self):
-    return {'kernels_launched': self.kernels}
+    return {'kernels_launched': self.kernels, 'gates_submitted': self.submitted, 'gates_noop': self.noop}
 
   def host_array(self):
     if not hasattr(self, '_host'):
@@ -1575,6 +1691,40 @@ class NumpyDevice:
 
   def apply_diag(self, values, bits):
     self._barrier(lambda v: diag_reference(v, self.nbits_global, values, [int(b) for b in bits]))
+
+  def perm_plan(self, bits, ctl_mask=0):
+    return perm_tiles(self.nbits, self.bit_width, self.bm, self.shard, [int(b) for b in bits], int(ctl_mask))
+
+  def apply_perm(self, table, bits, ctl_mask=0):
+    bits, ctl_mask, table = [int(b) for b in bits], int(ctl_mask), np.asarray(table, dtype=np.int64)
+    if len(set(bits)) != len(bits) or any((ctl_mask >> b) & 1 for b in bits):
+      raise native.QhError(native.QH_ERR_SAME_QUBIT, 'apply_perm: a bit twice, or a control in the register')
+    if any(self.bm[b] >= self.nbits for b in bits):
+      raise native.QhError(native.QH_ERR_NONLOCAL, 'apply_perm: a register bit held by the shard index')
+    if not np.array_equal(np.sort(table), np.arange(1 << len(bits))):
+      raise native.QhError(native.QH_ERR_ARG, 'apply_perm: not a bijection')
+    met, mask = self._perm_controls(ctl_mask)
+    self.submitted += 1
+    if not met:                                            # a barrier all the same: the queue runs, then nothing
+      self.flush()
+      self.noop += 1
+      self.kernels += self._perm_noop_kernels()
+      return
+    self._barrier(lambda v: self._perm_apply(v, table, bits, mask))
+    self._perm_layout()
+
+  def _perm_controls(self, ctl_mask):
+    """(are the controls the shard index holds all 1 here, the mask to apply: on the vector of the global size the whole mask)"""
+    return all(v for b, v in self.held().items() if (ctl_mask >> b) & 1), ctl_mask
+
+  def _perm_apply(self, vec, table, bits, ctl_mask):
+    return perm_reference(vec, self.nbits_global, table, bits, ctl_mask)
+
+  def _perm_noop_kernels(self):
+    return 0
+
+  def _perm_layout(self):
+    pass
 
   def scale(self, z):
     self._barrier(lambda v: v * complex(z))

@@ -4,10 +4,13 @@ step, results, bit maps, pending counts, kernel counts -- and the final download
 
 The last item reads what the earlier ones recorded from the real qh_get_bitmap / qh_inner_plan: relayout sweeps did leave a
 permuted local map in front of a barrier step or a reader in at least a third of the 'own' programs that start at 14 local
-bits or more, and all three paths of the two-state kernels were taken.  The CPU table (tests/test_program_fuzz_cpu.py) only
-predicts this.
+bits or more, and all three paths of the two-state kernels were taken.  Of the register permutations it reads what the real
+qh_perm_plan said right behind each call: at both widths the LDS path and the gather path ran, the gather path on a handle
+that keeps a relayout buffer (which it borrows), on one that keeps none (a temporary) and on a shard, and a permutation ran on a
+non-identity local map that its own flush had left.  The CPU table (tests/test_program_fuzz_cpu.py) only predicts this.
 
-The figures recorded when the file was added (time, chain errors per program) are in HISTORY.md, section T1.
+The figures recorded when the file was added (time, chain errors per program) are in HISTORY.md, section T1; those of the
+register permutations in section T2.
 """
 import pytest
 
@@ -16,10 +19,13 @@ from tests import program_model as pm
 
 pytestmark = pytest.mark.gpu
 
-SEEN = {'own': 0, 'own_big': 0, 'own_big_relaid': 0, 'paths': set()}
-# the six 'own' programs that run again, two under each planner variant: (seed, width) whose first handle has sweeps that
-# re-lay out (checked below, so that a change of the generator cannot quietly empty the list)
-VARIANT_PROGRAMS = [(env, seed, bw) for env, pair in zip(pm.ENV_VARIANTS, ([(1, 128), (4, 64)], [(3, 128), (5, 64)], [(6, 128), (8, 64)]))
+SEEN = {'own': 0, 'own_big': 0, 'own_big_relaid': 0, 'paths': set(), 'gather_relayout_0': 0}
+PERMS = []                    # (mode, width, the record of a 'perm' step: program_model._Runner.perm_record), fixed programs only
+# the 'own' programs that run again under a planner variant: (seed, width) whose first handle has sweeps that re-lay out and
+# which hold a register permutation (checked below, so that a change of the generator cannot quietly empty the list); of
+# the four under QH_RELAYOUT=0 the last two were added for a register wide enough for the gather path, there through a
+# temporary on a handle that owns its memory
+VARIANT_PROGRAMS = [(env, seed, bw) for env, pair in zip(pm.ENV_VARIANTS, ([(1, 128), (4, 64), (8, 128), (15, 64)], [(15, 128), (18, 64)], [(6, 128), (8, 64)]))
                     for seed, bw in pair]
 
 
@@ -34,6 +40,7 @@ def _run(mode, seed, bw):
 @pytest.mark.parametrize('mode,seed', pm.FIXED, ids=[f'{m}-{s}' for m, s in pm.FIXED])
 def test_program(mode, seed, bw):
   prog, check = _run(mode, seed, bw)
+  PERMS.extend((mode, bw, e[5]) for e in check.events if e[1] == 'perm')
   if mode == 'own':
     SEEN['own'] += 1
     SEEN['paths'] |= {e[4] for e in check.events if e[4] is not None}
@@ -48,9 +55,12 @@ def test_program_under_planner_variants(env, seed, bw, monkeypatch):
   for k, v in env.items():
     monkeypatch.setenv(k, v)                                # (the planner reads its switches at every flush)
   prog, check = _run('own', seed, bw)
-  assert prog[0]['nloc'] >= pm.PERMUTED_FROM
+  assert prog[0]['nloc'] >= pm.PERMUTED_FROM and any(s['op'] == 'perm' for s in prog)
   if env.get('QH_RELAYOUT') == '0':
     assert check.relaid == 0                                # no flush re-laid a handle out: clones and siblings decide as told
+    perms = [e[5] for e in check.events if e[1] == 'perm']
+    assert not any(r['relayout_on'] for r in perms)
+    SEEN['gather_relayout_0'] += sum(1 for r in perms if r['ctl_met'] and r['path'] == native.QH_PERM_GATHER)
 
 
 def test_zz_relayout_and_inner_paths_were_met():
@@ -60,3 +70,19 @@ def test_zz_relayout_and_inner_paths_were_met():
         f"{SEEN['own_big_relaid']}; inner paths {sorted(SEEN['paths'])}")
   assert 3 * SEEN['own_big_relaid'] >= SEEN['own_big'] > 0
   assert SEEN['paths'] == {native.QH_INNER_LINEAR, native.QH_INNER_TILES, native.QH_INNER_GATHER}
+  for bw in (128, 64):
+    ran = [(mode, r) for mode, w, r in PERMS if w == bw and r['ctl_met']]       # (a held control that is 0 on the shard runs nothing)
+    gather = [(mode, r) for mode, r in ran if r['path'] == native.QH_PERM_GATHER]
+    n = {'lds': len(ran) - len(gather), 'gather': len(gather),
+         'gather, own handle, relayout buffer': sum(1 for mode, r in gather if mode in ('own', 'shard') and r['relayout_on']),
+         'gather, temporary': sum(1 for mode, r in gather if not r['relayout_on']),
+         'gather on a shard': sum(1 for mode, r in gather if r['shard']),
+         'permuted map behind its own flush': sum(1 for mode, r in ran if r['relaid']),
+         'no-op (held control 0)': sum(1 for mode, w, r in PERMS if w == bw and not r['ctl_met'])}
+    by_kind = {m: [sum(1 for mode, r in ran if mode == m and r['path'] == p) for p in (native.QH_PERM_LDS, native.QH_PERM_GATHER)]
+               for m in ('own', 'shard', 'attached', 'mapped')}
+    print(f'perm steps at complex{bw}: {n}; [lds, gather] by program kind: {by_kind}')
+    assert n['lds'] and n['gather'] and n['gather, own handle, relayout buffer'] and n['gather, temporary'], n
+    assert n['permuted map behind its own flush'] and n['gather on a shard'], n
+  print(f"gather-path perm steps under QH_RELAYOUT=0 (a temporary on a handle that owns its memory): {SEEN['gather_relayout_0']}")
+  assert SEEN['gather_relayout_0']

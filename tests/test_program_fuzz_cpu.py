@@ -56,6 +56,7 @@ class QueueBehindBarrier(pm.NumpyDevice):
   def _barrier(self, fn, kernels=1):
     self.store(fn(self.to_logical()))
     self.flush()
+    self.kernels += kernels                                # (counted as ever: only the order is broken)
 
 
 class CopyKeepsQueue(pm.NumpyDevice):
@@ -166,20 +167,82 @@ class ReaderTurnsRelayoutOn(pm.NumpyDevice):
     return vec
 
 
+# -- register permutations.  Which check of the runner catches which (found by deleting each check in turn: the mutant named
+#    "only" then passes every fixed program, the other five are still caught)
+#      14, 15  the amplitudes behind the step: bit for bit on a quiet step, _amp_tol behind a queue
+#      16      the same where the table moves something; gates_noop + 1 where it does not (the first catch: an identity table)
+#      17      only the bit map: it may not move in a step with nothing to flush, nor behind a flush whose relayout mode is off
+#      18      only the stats of a quiet step: kernels_launched + 0, gates_noop + 1 where a held control is 0 on the shard
+#      19      only the BYTES of a quiet step: the values are equal as numbers, array_equal and the chain see nothing
+#      20      the amplitudes behind a step with a queue (_amp_tol), as for every other barrier
+class PermTableBackwards(pm.NumpyDevice):
+  """14. apply_perm applies the inverse table"""
+  def _perm_apply(self, vec, table, bits, ctl_mask):
+    return super()._perm_apply(vec, np.argsort(table), bits, ctl_mask)
+
+
+class PermBitsAscending(pm.NumpyDevice):
+  """15. apply_perm reads the register bits in ascending logical order, not in the order listed"""
+  def _perm_apply(self, vec, table, bits, ctl_mask):
+    return super()._perm_apply(vec, table, sorted(bits), ctl_mask)
+
+
+class PermHeldControlMet(pm.NumpyDevice):
+  """16. apply_perm treats a control the shard index holds as met"""
+  def _perm_controls(self, ctl_mask):
+    return True, ctl_mask & ~sum(1 << b for b in self.held())
+
+
+class PermCanonicalises(pm.NumpyDevice):
+  """17. apply_perm leaves the local bits in canonical order"""
+  def _perm_layout(self):
+    self._canonicalize()
+
+
+class PermNoopCountsAKernel(pm.NumpyDevice):
+  """18. apply_perm under a held control that is 0 on this shard counts a kernel"""
+  def _perm_noop_kernels(self):
+    return 1
+
+
+class PermComputes(pm.NumpyDevice):
+  """19. apply_perm passes the amplitudes through arithmetic (x + 0): a negative zero loses its sign"""
+  def _perm_apply(self, vec, table, bits, ctl_mask):
+    return super()._perm_apply(vec, table, bits, ctl_mask) + 0.0
+
+
+class PermBeforeItsQueue(pm.NumpyDevice):
+  """20. apply_perm runs before what is queued: mutant 1, for this call alone (it goes through _barrier like the others)"""
+  def apply_perm(self, table, bits, ctl_mask=0):
+    self._barrier = lambda fn, kernels=1: QueueBehindBarrier._barrier(self, fn, kernels)
+    try:
+      super().apply_perm(table, bits, ctl_mask)
+    finally:
+      del self._barrier
+
+
 MUTANTS = [QueueBehindBarrier, CopyKeepsQueue, CopyDropsBitmap, ReleaseKeepsLogicalNumbers, ExtendOnTop, MuxSelectorsReversed,
            TopkTiesByPhysicalIndex, AxpbyReadsDstAnyway, SelectInPhysicalOrder, ReaderCanonicalises, MarginalIgnoresHeldBits,
-           RoundsTwice, ReaderTurnsRelayoutOn]
+           RoundsTwice, ReaderTurnsRelayoutOn, PermTableBackwards, PermBitsAscending, PermHeldControlMet, PermCanonicalises,
+           PermNoopCountsAKernel, PermComputes, PermBeforeItsQueue]
+PERM_MUTANTS = MUTANTS[13:]
 
 
 @pytest.mark.parametrize('mutant', MUTANTS, ids=[m.__name__ for m in MUTANTS])
 def test_the_runner_fails_on_a_broken_device(mutant):
   order = sorted(((mode, seed, bw) for bw in WIDTHS for mode, seed in pm.FIXED), key=lambda k: len(program(*k)[0]['slots']) << program(*k)[0]['nloc'])
+  if mutant in PERM_MUTANTS:                                  # (they differ from NumpyDevice in apply_perm alone)
+    order = [key for key in order if any(s['op'] == 'perm' for s in program(*key))]
+    if mutant in (PermHeldControlMet, PermNoopCountsAKernel):                       # ... and these on a shard alone
+      order = [key for key in order if key[0] == 'shard']
   for key in order:
     try:
       run_on(mutant, *key)
     except pm.StepFailure as e:
       print(f'{mutant.__name__}: {key}: {e}'[:400])
       assert f'step {e.index} ' in str(e) and 0 <= e.index <= len(program(*key))      # the assertion names the step
+      if mutant in PERM_MUTANTS:                                                      # ... and it is a permutation that breaks them
+        assert e.step['op'] == 'perm', e.step['op']
       return
   raise AssertionError(f'{mutant.__name__} ({mutant.__doc__}) passes every fixed program')
 
@@ -193,7 +256,7 @@ def coverage(bw):
   for (mode, seed, w), c in checks().items():
     if w != bw:
       continue
-    for _, op, perm, q, path in c.events:
+    for _, op, perm, q, path, _ in c.events:
       kinds[op] += 1
       if op in permuted and perm:
         permuted[op] += 1
@@ -202,6 +265,45 @@ def coverage(bw):
       if path is not None:
         paths[op, path] += 1
   return kinds, permuted, queued, paths
+
+
+def perm_coverage(bw):
+  """what the 'perm' steps of the fixed programs met, from the path NumpyDevice.perm_plan predicts on its own bit map; a path
+  counts where the call ran a kernel (a held control that is 0 on the shard runs none)"""
+  lds, gather = pm.native.QH_PERM_LDS, pm.native.QH_PERM_GATHER
+  names = ('lds', 'gather', 'gather, relayout buffer', 'gather, temporary', 'layout band', 'layout band, queued, relayout on', 'local control',
+           'held control met', 'held control unmet', 'k == nloc', 'nloc < 10', 'gather on a shard', 'shard, held bit inside the register') + tuple('band ' + b for b in pm.PERM_BANDS)
+  n = dict.fromkeys(names, 0)
+  for (mode, seed, w), c in checks().items():
+    for _, op, _, q, _, r in c.events:
+      if w != bw or op != 'perm':
+        continue
+      ran = r['ctl_met'] == 1
+      n['lds'] += ran and r['path'] == lds
+      n['gather'] += ran and r['path'] == gather
+      n['gather, relayout buffer'] += ran and r['path'] == gather and r['relayout_on']
+      n['gather, temporary'] += ran and r['path'] == gather and not r['relayout_on']
+      n['band ' + r['band']] += 1
+      n['layout band'] += r['band'] == 'layout'
+      n['layout band, queued, relayout on'] += r['band'] == 'layout' and q and r['relayout_on']
+      n['local control'] += r['ctl_local']
+      n['held control met'] += mode == 'shard' and r['ctl_held'] and ran
+      n['held control unmet'] += mode == 'shard' and r['ctl_held'] and not ran
+      n['k == nloc'] += r['k'] == r['nloc']
+      n['nloc < 10'] += r['nloc'] < 10
+      n['gather on a shard'] += ran and r['path'] == gather and r['shard']
+      n['shard, held bit inside the register'] += ran and r['held_inside']      # (the 'mid3' / 'midhalf' starts)
+  for (mode, seed, w) in checks():                             # the refusals of apply_perm, from the programs themselves
+    for s in program(mode, seed, w):
+      if w == bw and s['op'] == 'refused' and s['what'].startswith('perm_'):
+        n['refused: ' + s['what']] = n.get('refused: ' + s['what'], 0) + 1
+  return {k: int(v) for k, v in n.items()}
+
+
+PERM_AT_LEAST = {'lds': 3, 'gather': 2, 'gather, relayout buffer': 1, 'gather, temporary': 1, 'layout band': 2,
+                 'layout band, queued, relayout on': 1, 'local control': 3, 'held control met': 1, 'held control unmet': 1, 'k == nloc': 1,
+                 'nloc < 10': 1, 'gather on a shard': 1, 'shard, held bit inside the register': 1, 'refused: perm_not_bijection': 1,
+                 'refused: perm_control_in_register': 1, 'refused: perm_register_held': 1}
 
 
 @pytest.mark.parametrize('bw', WIDTHS)
@@ -216,3 +318,24 @@ def test_coverage_of_the_fixed_programs(bw):
   assert all(n >= 3 for n in permuted.values()), permuted
   assert all(n >= 2 for n in paths.values()), paths
   assert all(n >= 2 for n in queued.values()), queued        # (every barrier mutator, and every other step that runs a queue)
+  perms = perm_coverage(bw)
+  print('  perm steps: ' + ', '.join(f'{k} {n}' + (f' (>= {PERM_AT_LEAST[k]})' if k in PERM_AT_LEAST else '') for k, n in perms.items()))
+  assert all(perms.get(k, 0) >= least for k, least in PERM_AT_LEAST.items()), perms
+
+
+def test_the_long_running_tool_ends_at_the_first_failure(monkeypatch, capsys):
+  """tools/fuzz_programs.py on a stand-in that breaks its first barrier: one FAIL line, the summary, exit status 1 -- and no
+  program started behind the one that failed (on the GPU a failure may be a fault)"""
+  import json
+  import fuzz_programs                                       # (tools/ is on sys.path: tests/program_model.py put it there)
+  def make(nloc, w, kind):
+    return QueueBehindBarrier(nloc, w, kind)
+  monkeypatch.setattr('sys.argv', ['fuzz_programs.py', '3600', '1', 'all'])
+  with pytest.raises(SystemExit) as e:
+    fuzz_programs.main(make_state=make)
+  assert e.value.code == 1
+  lines = [json.loads(x) for x in capsys.readouterr().out.splitlines() if x.startswith('{')]
+  assert len(lines) == 2 and lines[0]['FAIL'] == 1 and lines[0]['step_index'] is not None
+  first = (lines[0]['mode'], lines[0]['bw'])
+  order = [(md, w) for md in ('own', 'shard', 'attached', 'mapped') for w in (128, 64)]
+  assert lines[1] == dict(lines[1], programs=order.index(first) + 1, failures=1, next_seed=2, mode='all')
