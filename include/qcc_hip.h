@@ -373,7 +373,7 @@ int qh_topk(qh_handle h, uint64_t k, qh_entry *out, uint64_t *count);
  * Errors, nothing written: QH_ERR_ARG (null, count > 2^24, an index >= 2^nbits_global).                                   */
 int qh_amplitudes(qh_handle h, uint64_t count, const uint64_t *logical, double *out, uint64_t *nlocal);
 
-/* ---- two states (kernels_inner.hip.h) ------------------------------------ */
+/* ---- two states (kernels_two_state.hip.h) ------------------------------------ */
 /* A new handle on src's device holding a copy of src's state: what src has queued runs first, then one device-to-device
  * copy of the buffer as it lies, with nbits (local and global), width, shard index, fusion level and the bit map as it is
  * (no canonical order; src's pointer, layout and relayout mode are as before).  The clone always owns HBM memory and its own

@@ -22,7 +22,9 @@
 
 #include "../../include/qcc_hip.h"
 #include "buffers.hip.h"
+#include "kernels_common.hip.h"
 #include "kernels_gate.hip.h"
+#include "kernels_argmax.hip.h"
 #include "kernels_dense.hip.h"
 #include "kernels_mux.hip.h"
 #include "kernels_perm.hip.h"
@@ -31,6 +33,7 @@
 #include "kernels_select.hip.h"
 #include "select_plan.h"
 #include "kernels_expect.hip.h"
+#include "kernels_two_state.hip.h"
 #include "kernels_inner.hip.h"
 #include "kernels_axpby.hip.h"
 #include "kernels_resize.hip.h"
@@ -619,6 +622,28 @@ int read_back(qh_state_s *h, void *host, const void *dev, size_t bytes, const ch
   HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream));
   return wait_stream(h, h->stream, what);
 }
+// The host half of the readers' fixed-order sum (kernels_common.hip.h), in h->meas: a slab of rows x cols doubles, of which
+// the reading kernel writes one row per block, and nout results.  fold() adds the rows in block order, get() is the read_back.
+struct SlabSum {
+  qh_state_s *h;
+  size_t bytes = 0;
+  double *slab = nullptr, *out = nullptr;
+  hipError_t reserve(size_t rows, size_t cols, size_t nout) {
+    qh::ScratchLayout lay;
+    const size_t slab_off = lay.add(rows * cols * sizeof(double)), out_off = lay.add(nout * sizeof(double));
+    bytes = lay.total;
+    const hipError_t e = h->meas.reserve(bytes);
+    if (e != hipSuccess) return e;
+    slab = (double *)(h->meas.as<char>() + slab_off);
+    out = (double *)(h->meas.as<char>() + out_off);
+    return hipSuccess;
+  }
+  // out[at + t] = scale * (column t of the first nblk rows), for t < n
+  void fold(uint64_t nblk, int cols, unsigned n, double scale = 1.0, uint64_t at = 0) const {
+    hipLaunchKernelGGL(qh::k_slab_fold, dim3(n), dim3(256), 0, h->stream, (const double *)slab, (uint32_t)nblk, cols, scale, out + at);
+  }
+  int get(double *vals, size_t n, const char *what = "reader") const { return read_back(h, vals, out, n * sizeof(double), what); }
+};
 
 // on: allocate the second buffer now (false if it does not fit); off: queued gates run, the layout returns to
 // canonical order, the second buffer is freed.  *actual (optional) = the resulting mode.
@@ -709,7 +734,7 @@ int common_init(qh_state_s *h) {
 }
 
 int check_args(int nbits, int bit_width) {
-  static_assert(qh::kInnerMaxLocalBits == 40, "kernels_inner.hip.h sizes its tables for the limit below");
+  static_assert(qh::kInnerMaxLocalBits == 40, "kernels_two_state.hip.h sizes its tables for the limit below");
   if (nbits < 1 || nbits > 40) return fail(QH_ERR_ARG, "nbits %d out of range [1,40]", nbits);
   if (bit_width != 64 && bit_width != 128)
     return fail(QH_ERR_BAD_DTYPE, "bit_width %d (want 64 or 128)", bit_width);
@@ -1205,136 +1230,30 @@ int qh_prob_bit(qh_handle h, int logical_bit, double *p1) { return qh_prob_bit_v
 
 // ---- argmax (state.py:60-78 maxprob: the FIRST basis state, in logical order, with the largest probability) ----------
 namespace {
-// logical index of a physical one: bit inv[p] of the result = bit p (inv = where each physical bit position lives logically)
-struct BitMap { int n; uint8_t to[64]; };
-__device__ __forceinline__ uint64_t map_bits(uint64_t v, const BitMap &m) {
-  uint64_t o = 0;
-  for (int p = 0; p < m.n; ++p) o |= ((v >> p) & 1ull) << m.to[p];
-  return o;
-}
-// The tables of the kernels that report LOGICAL indices, as the layout is now: physical -> logical of the local bits
-// (p2l, meas.to), its inverse (l2p), and the logical bits the shard index holds at 1 on this shard (meas.shard_logical).
+// The tables of the kernels that report LOGICAL indices, as the layout is now: physical -> logical of the local bits with
+// the logical bits the shard index holds at 1 on this shard (p2l), and the inverse for the one kernel that walks in logical
+// order (l2p).
 struct LocalBits {
-  BitMap p2l{}, l2p{};
-  qh::MeasMap meas{};
+  qh::IndexMap p2l{};
+  qh::BitMap l2p{};
   bool mapped = false;      // some local bit is off its canonical position
 };
 LocalBits local_bits(const qh_state_s *h) {
   LocalBits lb;
-  lb.p2l.n = lb.l2p.n = h->nloc;
+  lb.l2p.n = h->nloc;
   for (int b = 0; b < h->nglob; ++b) {
     const Placed at = place_bit(h, b);
     if (at.held) {
-      if (h->shard & at.held) lb.meas.shard_logical |= 1ull << b;
+      if (h->shard & at.held) lb.p2l.shard_logical |= 1ull << b;
       continue;
     }
     const int p = h->perm[b];
-    lb.p2l.to[p] = lb.meas.to[p] = (uint8_t)b;
+    lb.p2l.to[p] = (uint8_t)b;
     lb.l2p.to[b] = (uint8_t)p;
     lb.mapped |= p != b;
   }
   return lb;
 }
-__device__ __forceinline__ double prob_of(double2 a) { return __builtin_fma(a.y, a.y, a.x * a.x); }   // (as the sweep islands compute it)
-__device__ __forceinline__ double prob_of(float2 a) { return __builtin_fma((double)a.y, (double)a.y, (double)a.x * (double)a.x); }
-
-// per block: the largest probability and the smallest LOGICAL index that has it (identity map: the physical index)
-template <typename A, bool MAPPED>
-__global__ __launch_bounds__(256) void k_argmax_logical(const A *__restrict__ psi, uint64_t n, BitMap bm, double *best_p, uint64_t *best_i) {
-  __shared__ double sp[256];
-  __shared__ uint64_t si[256];
-  // physical -> logical through five byte tables (a near-uniform state -- a QFT's output -- ties at almost every amplitude:
-  // the bit-by-bit map there cost 10 ms of a 30-qubit pass)
-  __shared__ uint64_t lut[MAPPED ? 5 * 256 : 1];
-  if (MAPPED) {
-    for (int t = 0; t < 5; ++t) lut[t * 256 + threadIdx.x] = map_bits((uint64_t)threadIdx.x << (8 * t), bm);
-    __syncthreads();
-  }
-  auto logical = [&](uint64_t idx) -> uint64_t {
-    if (!MAPPED) return idx;
-    return lut[idx & 255] | lut[256 + ((idx >> 8) & 255)] | lut[512 + ((idx >> 16) & 255)] | lut[768 + ((idx >> 24) & 255)] |
-           lut[1024 + ((idx >> 32) & 255)];
-  };
-  double bp = -1.0;
-  uint64_t bi = ~0ull;
-  const uint64_t stride = (uint64_t)gridDim.x * 256;
-  uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  auto take = [&](double p, uint64_t idx) {
-    if (p > bp) { bp = p; bi = logical(idx); }
-    else if (p == bp) { const uint64_t li = logical(idx); if (li < bi) bi = li; }
-  };
-  for (; i + 3 * stride < n; i += 4 * stride) {      // four loads in flight per thread
-    A a[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) a[k] = qh::ld_amp<true>(psi + i + k * stride);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) take(prob_of(a[k]), i + k * stride);
-  }
-  for (; i < n; i += stride) take(prob_of(qh::ld_amp<true>(psi + i)), i);
-  sp[threadIdx.x] = bp;
-  si[threadIdx.x] = bi;
-  __syncthreads();
-  for (unsigned st = 128; st > 0; st >>= 1) {
-    if (threadIdx.x < st) {
-      const double op = sp[threadIdx.x + st];
-      const uint64_t oi = si[threadIdx.x + st];
-      if (op > sp[threadIdx.x] || (op == sp[threadIdx.x] && oi < si[threadIdx.x])) { sp[threadIdx.x] = op; si[threadIdx.x] = oi; }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { best_p[blockIdx.x] = sp[0]; best_i[blockIdx.x] = si[0]; }
-}
-
-// the per-unit maxima of the last sweep (bit patterns of non-negative doubles: they order like the doubles)
-__global__ __launch_bounds__(256) void k_tmax_reduce(const uint64_t *__restrict__ t, uint64_t n, uint64_t *out) {
-  __shared__ uint64_t sm[256];
-  uint64_t m = 0;
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) m = t[i] > m ? t[i] : m;
-  sm[threadIdx.x] = m;
-  __syncthreads();
-  for (unsigned st = 128; st > 0; st >>= 1) {
-    if (threadIdx.x < st && sm[threadIdx.x + st] > sm[threadIdx.x]) sm[threadIdx.x] = sm[threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[blockIdx.x] = sm[0];
-}
-constexpr unsigned kTmaxIds = 64;
-// units whose maximum is the global one: ids[0] = how many, ids[1..] the first kTmaxIds of them
-__global__ __launch_bounds__(256) void k_tmax_collect(const uint64_t *__restrict__ t, uint64_t n, uint64_t want, unsigned long long *ids) {
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
-    if (t[i] == want) {
-      const unsigned long long k = atomicAdd(ids, 1ull);
-      if (k < kTmaxIds) ids[1 + k] = i;
-    }
-}
-// one block per collected unit: the smallest logical index among its amplitudes with probability == want
-template <typename A>
-__global__ __launch_bounds__(256) void k_tmax_scan(const A *__restrict__ psi, const unsigned long long *__restrict__ ids, qh::BitIns ins,
-                                                    uint64_t tile_mask, int tile_bits, double want, BitMap bm, unsigned long long *out) {
-  const uint64_t base = qh::expand_index(ids[1 + blockIdx.x], ins);
-  unsigned long long best = ~0ull;
-  for (uint64_t j = threadIdx.x; j < (1ull << tile_bits); j += 256) {
-    uint64_t off = 0, jj = j;
-    for (uint64_t m = tile_mask; m; m &= m - 1) { off |= (jj & 1ull) << __builtin_ctzll(m); jj >>= 1; }
-    const uint64_t idx = base | off;
-    if (prob_of(qh::ld_amp<false>(psi + idx)) == want) {
-      const unsigned long long li = map_bits(idx, bm);
-      best = li < best ? li : best;
-    }
-  }
-  if (best != ~0ull) atomicMin(out, best);
-}
-
-// the smallest logical index in [l0, l1) whose amplitude has probability == want (l2p: logical -> physical)
-template <typename A>
-__global__ __launch_bounds__(256) void k_prefix_scan(const A *__restrict__ psi, uint64_t l0, uint64_t l1, double want, BitMap l2p,
-                                                      unsigned long long *out) {
-  unsigned long long best = ~0ull;
-  for (uint64_t l = l0 + (uint64_t)blockIdx.x * 256 + threadIdx.x; l < l1; l += (uint64_t)gridDim.x * 256)
-    if (prob_of(qh::ld_amp<false>(psi + map_bits(l, l2p))) == want) { best = l; break; }     // (ascending per thread: the first hit is its smallest)
-  if (best != ~0ull) atomicMin(out, best);
-}
-
 // The last sweep of the flush left per-unit maxima: the largest of them is the answer's probability; the answer's index is the
 // smallest logical index that has it.  Few units hold it (a peaked state: Grover, most algorithms' outputs): those units are
 // scanned.  Many do (a flat state: a QFT's output ties at a tenth of its amplitudes): the first of them in LOGICAL order is
@@ -1342,7 +1261,7 @@ __global__ __launch_bounds__(256) void k_prefix_scan(const A *__restrict__ psi, 
 int argmax_from_tilemax(qh_state_s *h, const qh::TileMaxOut &tm, const LocalBits &lb, uint64_t *logical, double *prob, bool *found) {
   *found = false;
   const unsigned grid = grid_for(tm.nunits, kRedBlocks);
-  hipLaunchKernelGGL(k_tmax_reduce, dim3(grid), dim3(256), 0, h->stream, (const uint64_t *)tm.buf, tm.nunits, h->d_redi());
+  hipLaunchKernelGGL(qh::k_tmax_reduce, dim3(grid), dim3(256), 0, h->stream, (const uint64_t *)tm.buf, tm.nunits, h->d_redi());
   std::vector<uint64_t> part(grid);
   int rc = read_back(h, part.data(), h->d_redi(), grid * sizeof(uint64_t));
   if (rc) return rc;
@@ -1350,25 +1269,25 @@ int argmax_from_tilemax(qh_state_s *h, const qh::TileMaxOut &tm, const LocalBits
   for (uint64_t v : part) top = std::max(top, v);
   double want;
   memcpy(&want, &top, 8);
-  unsigned long long *ids = (unsigned long long *)h->d_redi();      // (kRedBlocks u64: room for 1 + kTmaxIds + the result)
-  static_assert(kRedBlocks >= 2 + kTmaxIds, "reduction scratch");
+  unsigned long long *ids = (unsigned long long *)h->d_redi();      // (kRedBlocks u64: room for 1 + qh::kTmaxIds + the result)
+  static_assert(kRedBlocks >= 2 + qh::kTmaxIds, "reduction scratch");
   HIP_TRY(hipMemsetAsync(ids, 0, 8, h->stream));
-  HIP_TRY(hipMemsetAsync(ids + 1 + kTmaxIds, 0xff, 8, h->stream));
-  hipLaunchKernelGGL(k_tmax_collect, dim3(grid), dim3(256), 0, h->stream, (const uint64_t *)tm.buf, tm.nunits, top, ids);
+  HIP_TRY(hipMemsetAsync(ids + 1 + qh::kTmaxIds, 0xff, 8, h->stream));
+  hipLaunchKernelGGL(qh::k_tmax_collect, dim3(grid), dim3(256), 0, h->stream, (const uint64_t *)tm.buf, tm.nunits, top, ids);
   unsigned long long cnt = 0;
   if ((rc = read_back(h, &cnt, ids, 8))) return rc;
   if (cnt == 0) return QH_OK;
-  if (cnt > kTmaxIds) {
+  if (cnt > qh::kTmaxIds) {
     const uint64_t n = 1ull << h->nloc;
     uint64_t l0 = 0;
     for (uint64_t l1 = std::min<uint64_t>(n, 1ull << 16); l0 < n; l0 = l1, l1 = std::min<uint64_t>(n, l1 << 6)) {
       with_real(h, [&](auto x) {
         using A = typename qh::AmpT<decltype(x)>::type;
-        hipLaunchKernelGGL(k_prefix_scan<A>, dim3(grid_for(l1 - l0, 1u << 16)), dim3(256), 0, h->stream, (const A *)h->d_psi, l0, l1, want,
-                           lb.l2p, ids + 1 + kTmaxIds);
+        hipLaunchKernelGGL(qh::k_prefix_scan<A>, dim3(grid_for(l1 - l0, 1u << 16)), dim3(256), 0, h->stream, (const A *)h->d_psi, l0, l1, want,
+                           lb.l2p, ids + 1 + qh::kTmaxIds);
       });
       unsigned long long hit = ~0ull;
-      if ((rc = read_back(h, &hit, ids + 1 + kTmaxIds, 8))) return rc;
+      if ((rc = read_back(h, &hit, ids + 1 + qh::kTmaxIds, 8))) return rc;
       if (hit != ~0ull) {
         *logical = hit;
         *prob = want;
@@ -1380,11 +1299,11 @@ int argmax_from_tilemax(qh_state_s *h, const qh::TileMaxOut &tm, const LocalBits
   }
   with_real(h, [&](auto x) {
     using A = typename qh::AmpT<decltype(x)>::type;
-    hipLaunchKernelGGL(k_tmax_scan<A>, dim3((unsigned)cnt), dim3(256), 0, h->stream, (const A *)h->d_psi, ids, tm.ins, tm.tile_mask,
-                       __builtin_popcountll(tm.tile_mask), want, lb.p2l, ids + 1 + kTmaxIds);
+    hipLaunchKernelGGL(qh::k_tmax_scan<A>, dim3((unsigned)cnt), dim3(256), 0, h->stream, (const A *)h->d_psi, ids, tm.ins, tm.tile_mask,
+                       __builtin_popcountll(tm.tile_mask), want, lb.p2l, h->nloc, ids + 1 + qh::kTmaxIds);
   });
   unsigned long long li = ~0ull;
-  if ((rc = read_back(h, &li, ids + 1 + kTmaxIds, 8))) return rc;
+  if ((rc = read_back(h, &li, ids + 1 + qh::kTmaxIds, 8))) return rc;
   if (li == ~0ull) return QH_OK;       // (cannot happen: a unit's maximum is one of its amplitudes) -> the full pass decides
   *logical = li;
   *prob = want;
@@ -1422,8 +1341,8 @@ extern "C" int qh_argmax(qh_handle h, uint64_t *phys_index, double *prob) {
     const unsigned grid = grid_for(n, kRedBlocks);
     with_real(h, [&](auto x) {
       using A = typename qh::AmpT<decltype(x)>::type;
-      if (lb.mapped) hipLaunchKernelGGL((k_argmax_logical<A, true>), dim3(grid), dim3(256), 0, h->stream, (const A *)h->d_psi, n, lb.p2l, h->d_red(), h->d_redi());
-      else hipLaunchKernelGGL((k_argmax_logical<A, false>), dim3(grid), dim3(256), 0, h->stream, (const A *)h->d_psi, n, lb.p2l, h->d_red(), h->d_redi());
+      if (lb.mapped) hipLaunchKernelGGL((qh::k_argmax_logical<A, true>), dim3(grid), dim3(256), 0, h->stream, (const A *)h->d_psi, n, lb.p2l, h->d_red(), h->d_redi());
+      else hipLaunchKernelGGL((qh::k_argmax_logical<A, false>), dim3(grid), dim3(256), 0, h->stream, (const A *)h->d_psi, n, lb.p2l, h->d_red(), h->d_redi());
     });
     std::vector<double> bp(grid);
     std::vector<uint64_t> bi(grid);
@@ -2044,7 +1963,7 @@ int qh_sample(qh_handle h, uint64_t count, const double *u, uint64_t *logical_ou
   HIP_TRY(hipMemcpyAsync(d_tgt, tgt.data(), count * 8, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(d_ids, ids.data(), m * 8, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(d_first, first.data(), (m + 1) * 8, hipMemcpyHostToDevice, h->stream));
-  const qh::MeasMap mm = local_bits(h).meas;
+  const qh::IndexMap mm = local_bits(h).p2l;
   const unsigned g2 = (unsigned)std::min<uint64_t>(m, 2048);
   with_real(h, [&](auto x) {
     using R = decltype(x);
@@ -2100,7 +2019,7 @@ void count_state_read(qh_state_s *h, uint64_t amps) {
   h->stats.bytes_algorithmic += amps * h->amp_bytes();
 }
 
-double entry_prob(const qh_entry &e) { return std::fma(e.im, e.im, e.re * e.re); }     // (the device's sel_prob, bit for bit)
+double entry_prob(const qh_entry &e) { return std::fma(e.im, e.im, e.re * e.re); }     // (the device's prob_fma, bit for bit)
 
 // One compaction pass: the entries with klo <= key <= khi.  *count: how many there are; *weight (optional): the sum of
 // their probabilities; out (optional, cap entries): written, in the order the waves arrived, iff *count <= cap.
@@ -2116,7 +2035,7 @@ int select_pass(qh_state_s *h, uint64_t klo, uint64_t khi, uint64_t cap, qh_entr
   double *d_w = (double *)(scr + w_off);
   qh::SelEntry *d_ent = cap ? (qh::SelEntry *)(scr + ent_off) : nullptr;
   HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, h->stream));
-  const qh::MeasMap mm = local_bits(h).meas;
+  const qh::IndexMap mm = local_bits(h).p2l;
   with_real(h, [&](auto x) {
     using R = decltype(x);
     hipLaunchKernelGGL(qh::k_select<R>, dim3(grid), dim3(256), 0, h->stream, (const typename qh::AmpT<R>::type *)h->d_psi, c, nchunks, klo,
@@ -2314,7 +2233,7 @@ int qh_amplitudes(qh_handle h, uint64_t count, const uint64_t *logical, double *
 
 }  // extern "C"
 
-// ---- two states: qh_clone, qh_copy, qh_inner, qh_axpby (kernels_inner.hip.h, kernels_axpby.hip.h) ---------------------
+// ---- two states: qh_clone, qh_copy, qh_inner, qh_axpby (kernels_two_state.hip.h and its two operations) ---------------------
 namespace {
 
 constexpr uint64_t kInnerBlocks = 4096;     // blocks at most (one slab row of (re, im) each)
@@ -2386,35 +2305,6 @@ int make_sibling(const qh_state_s *src, int nloc, int nglob, const char *who, qh
   return QH_OK;
 }
 
-// The launch geometry the two-state kernels share (k_inner_*, k_axpby_*).  Linear walk over 2^items 16-byte items: chunks of
-// 256 threads x kInnerLoads items, a whole number of chunks per block.
-struct LinearGeom { int cw; uint32_t cpb; uint64_t nblk; };
-LinearGeom linear_geom(int items) {
-  const int cw = std::min(8 + 3, items);
-  const uint64_t nchunks = 1ull << (items - cw), nblk = std::min(nchunks, kInnerBlocks);
-  return {cw, (uint32_t)(nchunks / nblk), nblk};
-}
-qh::InnerTileArgs tile_args(const qh_inner_tiles &pl, uint64_t *nblk) {
-  qh::InnerTileArgs t{};
-  memcpy(t.tile_a, pl.tile_a, 8);
-  memcpy(t.tile_b, pl.tile_b, 8);
-  memcpy(t.shuffle, pl.shuffle, 8);
-  memcpy(t.rest_a, pl.rest_a, sizeof t.rest_a);
-  memcpy(t.rest_b, pl.rest_b, sizeof t.rest_b);
-  t.nrest = (int)pl.nrest;
-  t.cbits = std::min(qh::kInnerChunkBits, t.nrest);
-  const uint64_t nchunks = 1ull << (t.nrest - t.cbits);
-  *nblk = std::min(nchunks, kInnerBlocks);
-  t.cpb = (uint32_t)(nchunks / *nblk);
-  return t;
-}
-qh::InnerGatherArgs gather_args(int nloc, const qh_inner_tiles &pl) {
-  qh::InnerGatherArgs g{};
-  g.nloc = nloc;
-  memcpy(g.pos_b, pl.pos_b, sizeof g.pos_b);
-  return g;
-}
-
 // b's stream has been given work that a's stream is about to read (or must not overtake): an event between them
 int order_after(qh_state_s *a, qh_state_s *b) {
   if (!b->ev_read) HIP_TRY(hipEventCreateWithFlags(&b->ev_read, hipEventDisableTiming));
@@ -2423,35 +2313,55 @@ int order_after(qh_state_s *a, qh_state_s *b) {
   return QH_OK;
 }
 
+// The one dispatch of the two-state walks (kernels_two_state.hip.h): the walk pl names, with its geometry (at most
+// kInnerBlocks blocks, a whole number of chunks per block), on a's stream.  Returns the blocks launched: the slab rows an
+// operation that sums has written.
+template <typename Op> uint64_t launch_two_state(qh_state_s *a, const qh_state_s *b, const qh_inner_tiles &pl, const Op &op, double *slab) {
+  uint64_t nblk = 1;
+  with_real(a, [&](auto x) {
+    using R = decltype(x);
+    qh::TwoDst<R, Op> *pa = (qh::TwoDst<R, Op> *)a->d_psi;
+    const typename qh::AmpT<R>::type *pb = (const typename qh::AmpT<R>::type *)b->d_psi;
+    if (pl.path == QH_INNER_LINEAR) {      // 2^items 16-byte items in chunks of 256 threads x kInnerLoads
+      const int items = a->nloc - qh::Item16<R>::kAmpBits, cw = std::min(8 + 3, items);
+      const uint64_t nchunks = 1ull << (items - cw);
+      nblk = std::min(nchunks, kInnerBlocks);
+      hipLaunchKernelGGL((qh::k_two_linear<R, Op>), dim3((unsigned)nblk), dim3(256), 0, a->stream, pa, pb, op, cw, (uint32_t)(nchunks / nblk), slab);
+    } else if constexpr (Op::RS) {      // (the other two walks read b)
+      if (pl.path == QH_INNER_TILES) {
+        qh::InnerTileArgs t{};
+        memcpy(t.tile_a, pl.tile_a, 8);
+        memcpy(t.tile_b, pl.tile_b, 8);
+        memcpy(t.shuffle, pl.shuffle, 8);
+        memcpy(t.rest_a, pl.rest_a, sizeof t.rest_a);
+        memcpy(t.rest_b, pl.rest_b, sizeof t.rest_b);
+        t.nrest = (int)pl.nrest;
+        t.cbits = std::min(qh::kInnerChunkBits, t.nrest);
+        const uint64_t nchunks = 1ull << (t.nrest - t.cbits);
+        nblk = std::min(nchunks, kInnerBlocks);
+        t.cpb = (uint32_t)(nchunks / nblk);
+        hipLaunchKernelGGL((qh::k_two_tiles<R, Op>), dim3((unsigned)nblk), dim3(256), 0, a->stream, pa, pb, op, t, slab);
+      } else {
+        qh::InnerGatherArgs g{};
+        g.nloc = a->nloc;
+        memcpy(g.pos_b, pl.pos_b, sizeof g.pos_b);
+        hipLaunchKernelGGL((qh::k_two_gather<R, Op>), dim3(1), dim3(256), 0, a->stream, pa, pb, op, g, slab);
+      }
+    }
+  });
+  return nblk;
+}
+
 // <a|b> into vals, on a's stream, behind what b's stream has been given; both flushed, pl = their plan.  The host waits.
 // No stats: the callers count.
 int run_inner(qh_state_s *a, qh_state_s *b, const qh_inner_tiles &pl, double vals[2]) {
   int rc;
-  qh::ScratchLayout lay;
-  const size_t slab_off = lay.add((size_t)kInnerBlocks * 2 * sizeof(double)), out_off = lay.add(2 * sizeof(double));
-  HIP_TRY(a->meas.reserve(lay.total));
-  double *slab = (double *)(a->meas.as<char>() + slab_off), *dout = (double *)(a->meas.as<char>() + out_off);
+  SlabSum sum{a};
+  HIP_TRY(sum.reserve(kInnerBlocks, 2, 2));
   if (b != a && (rc = order_after(a, b))) return rc;      // a's stream reads b: behind everything b's stream has been given
-  uint64_t nblk = 1;
-  with_real(a, [&](auto x) {
-    using R = decltype(x);
-    using A = typename qh::AmpT<R>::type;
-    const A *pa = (const A *)a->d_psi, *pb = (const A *)b->d_psi;
-    if (pl.path == QH_INNER_LINEAR) {
-      const LinearGeom g = linear_geom(a->nloc - qh::InnerItem<R>::kAmpBits);
-      nblk = g.nblk;
-      hipLaunchKernelGGL(qh::k_inner_linear<R>, dim3((unsigned)nblk), dim3(256), 0, a->stream, pa, pb, g.cw, g.cpb, slab);
-    } else if (pl.path == QH_INNER_TILES) {
-      const qh::InnerTileArgs t = tile_args(pl, &nblk);
-      hipLaunchKernelGGL(qh::k_inner_tiles<R>, dim3((unsigned)nblk), dim3(256), 0, a->stream, pa, pb, t, slab);
-    } else {
-      const qh::InnerGatherArgs g = gather_args(a->nloc, pl);
-      hipLaunchKernelGGL(qh::k_inner_gather<R>, dim3(1), dim3(256), 0, a->stream, pa, pb, g, slab);
-    }
-  });
-  hipLaunchKernelGGL(qh::k_expect_fold, dim3(2), dim3(256), 0, a->stream, (const double *)slab, (uint32_t)nblk, 2, 1.0, dout);
+  sum.fold(launch_two_state(a, b, pl, qh::InnerOp{}, sum.slab), 2, 2);
   if ((rc = check_launch(a))) return rc;
-  return read_back(a, vals, dout, 2 * sizeof(double), "qh_inner");
+  return sum.get(vals, 2, "qh_inner");
 }
 
 }  // namespace
@@ -2537,46 +2447,20 @@ int qh_axpby(qh_handle dst, const double alpha[2], qh_handle src, const double b
     *norm2 = vals[0];
     return QH_OK;
   }
-  double *slab = nullptr, *dout = nullptr;
-  if (norm2) {
-    qh::ScratchLayout lay;
-    const size_t slab_off = lay.add((size_t)kInnerBlocks * 2 * sizeof(double)), out_off = lay.add(2 * sizeof(double));
-    HIP_TRY(dst->meas.reserve(lay.total));
-    slab = (double *)(dst->meas.as<char>() + slab_off);
-    dout = (double *)(dst->meas.as<char>() + out_off);
-  }
+  SlabSum sum{dst};
+  if (norm2) HIP_TRY(sum.reserve(kInnerBlocks, 2, 2));
   if (rs && (rc = order_after(dst, src))) return rc;      // dst's stream reads src: behind everything src's stream has been given
+  if (!rs) pl.path = QH_INNER_LINEAR;      // (src not read: the layouts do not matter)
   const qh::AxpbyCoef c{alpha[0], alpha[1], beta[0], beta[1], norm2 ? 1 : 0};
-  uint64_t nblk = 1;
-  with_real(dst, [&](auto x) {
-    using R = decltype(x);
-    using A = typename qh::AmpT<R>::type;
-    A *pd = (A *)dst->d_psi;
-    const A *ps = (const A *)src->d_psi;
-    const dim3 thr(256);
-    if (!rs || pl.path == QH_INNER_LINEAR) {      // (src not read: the layouts do not matter)
-      const LinearGeom g = linear_geom(dst->nloc - qh::InnerItem<R>::kAmpBits);
-      nblk = g.nblk;
-      const dim3 grid((unsigned)nblk);
-      if (rd && rs) hipLaunchKernelGGL((qh::k_axpby_linear<R, true, true>), grid, thr, 0, dst->stream, pd, ps, c, g.cw, g.cpb, slab);
-      else if (rs) hipLaunchKernelGGL((qh::k_axpby_linear<R, false, true>), grid, thr, 0, dst->stream, pd, ps, c, g.cw, g.cpb, slab);
-      else if (rd) hipLaunchKernelGGL((qh::k_axpby_linear<R, true, false>), grid, thr, 0, dst->stream, pd, ps, c, g.cw, g.cpb, slab);
-      else hipLaunchKernelGGL((qh::k_axpby_linear<R, false, false>), grid, thr, 0, dst->stream, pd, ps, c, g.cw, g.cpb, slab);
-    } else if (pl.path == QH_INNER_TILES) {
-      const qh::InnerTileArgs t = tile_args(pl, &nblk);
-      const dim3 grid((unsigned)nblk);
-      if (rd) hipLaunchKernelGGL((qh::k_axpby_tiles<R, true>), grid, thr, 0, dst->stream, pd, ps, c, t, slab);
-      else hipLaunchKernelGGL((qh::k_axpby_tiles<R, false>), grid, thr, 0, dst->stream, pd, ps, c, t, slab);
-    } else {
-      const qh::InnerGatherArgs g = gather_args(dst->nloc, pl);
-      if (rd) hipLaunchKernelGGL((qh::k_axpby_gather<R, true>), dim3(1), thr, 0, dst->stream, pd, ps, c, g, slab);
-      else hipLaunchKernelGGL((qh::k_axpby_gather<R, false>), dim3(1), thr, 0, dst->stream, pd, ps, c, g, slab);
-    }
-  });
-  if (norm2) hipLaunchKernelGGL(qh::k_expect_fold, dim3(1), dim3(256), 0, dst->stream, (const double *)slab, (uint32_t)nblk, 2, 1.0, dout);
+  uint64_t nblk;
+  if (rd && rs) nblk = launch_two_state(dst, src, pl, qh::AxpbyOp<true, true>{c}, sum.slab);
+  else if (rs) nblk = launch_two_state(dst, src, pl, qh::AxpbyOp<false, true>{c}, sum.slab);
+  else if (rd) nblk = launch_two_state(dst, src, pl, qh::AxpbyOp<true, false>{c}, sum.slab);
+  else nblk = launch_two_state(dst, src, pl, qh::AxpbyOp<false, false>{c}, sum.slab);
+  if (norm2) sum.fold(nblk, 2, 1);
   if ((rc = check_launch(dst))) return rc;
   // the host waits: on return src may be changed and dst read at once
-  if (norm2) rc = read_back(dst, norm2, dout, sizeof(double), "qh_axpby");
+  if (norm2) rc = sum.get(norm2, 1, "qh_axpby");
   else rc = wait_stream(dst, dst->stream, "qh_axpby");
   if (rc) return rc;
   const uint64_t streams = 1 + (rd ? 1 : 0) + (rs ? 1 : 0), bytes = streams * ((1ull << dst->nloc) * dst->amp_bytes());
@@ -2638,7 +2522,7 @@ int qh_extend(qh_handle src, int k, const double *amps, uint64_t basis, qh_handl
     using R = decltype(x);
     using A = typename qh::AmpT<R>::type;
     qh::ExtendArgs a{};
-    a.ib = src->nloc - qh::InnerItem<R>::kAmpBits;
+    a.ib = src->nloc - qh::Item16<R>::kAmpBits;
     a.cw = std::min(qh::kResizeChunkBits, a.ib);
     a.nj = 1u << k;
     a.nchunks = 1ull << (a.ib - a.cw);
@@ -2694,24 +2578,22 @@ int qh_release(qh_handle src, int k, const int32_t *bits, uint64_t value, double
   a.cw = std::min(qh::kResizeChunkBits, ib);
   a.nchunks = 1ull << (ib - a.cw);
   const uint32_t nblk = (uint32_t)std::min<uint64_t>(a.nchunks, qh::kResizeBlocks);
-  qh::ScratchLayout lay;
-  const size_t slab_off = lay.add((size_t)nblk * 2 * sizeof(double)), out_off = lay.add(2 * sizeof(double));
-  if (src->meas.reserve(lay.total) != hipSuccess) return drop_sibling(h, fail(QH_ERR_NOMEM, "release: no room for %zu bytes of scratch", lay.total));
-  double *slab = (double *)(src->meas.as<char>() + slab_off), *dout = (double *)(src->meas.as<char>() + out_off);
+  SlabSum sum{src};
+  if (sum.reserve(nblk, 2, 2) != hipSuccess) return drop_sibling(h, fail(QH_ERR_NOMEM, "release: no room for %zu bytes of scratch", sum.bytes));
   with_real(src, [&](auto x) {
     using R = decltype(x);
     using A = typename qh::AmpT<R>::type;
     const A *from = (const A *)src->d_psi;
     A *to = (A *)h->d_psi;
-    if (qh::InnerItem<R>::kAmpBits && (pl.drop & 1ull))      // a complex64 item loses one of its halves
-      hipLaunchKernelGGL((qh::k_release<R, true>), dim3(nblk), dim3(256), 0, src->stream, from, to, a, slab);
+    if (qh::Item16<R>::kAmpBits && (pl.drop & 1ull))      // a complex64 item loses one of its halves
+      hipLaunchKernelGGL((qh::k_release<R, true>), dim3(nblk), dim3(256), 0, src->stream, from, to, a, sum.slab);
     else
-      hipLaunchKernelGGL((qh::k_release<R, false>), dim3(nblk), dim3(256), 0, src->stream, from, to, a, slab);
+      hipLaunchKernelGGL((qh::k_release<R, false>), dim3(nblk), dim3(256), 0, src->stream, from, to, a, sum.slab);
   });
-  hipLaunchKernelGGL(qh::k_expect_fold, dim3(2), dim3(256), 0, src->stream, (const double *)slab, nblk, 2, 1.0, dout);
+  sum.fold(nblk, 2, 2);
   double vals[2];
   rc = check_launch(src);
-  if (rc == QH_OK) rc = read_back(src, vals, dout, sizeof vals, "qh_release");
+  if (rc == QH_OK) rc = sum.get(vals, 2, "qh_release");
   if (rc) return drop_sibling(h, rc);
   if (weight) {
     weight[0] = vals[0];
@@ -2767,10 +2649,8 @@ int qh_expect_pauli(qh_handle h, uint64_t nterms, const uint64_t *xmask, const u
   }
   // terms that share a physical x mask share a read of the state, kExpectT at a time
   std::stable_sort(terms.begin(), terms.end(), [](const Term &l, const Term &r) { return l.px < r.px; });
-  qh::ScratchLayout lay;
-  const size_t slab_off = lay.add((size_t)kExpectBlocks * qh::kExpectT * sizeof(double)), out_off = lay.add((size_t)nterms * sizeof(double));
-  HIP_TRY(h->meas.reserve(lay.total));
-  double *slab = (double *)(h->meas.as<char>() + slab_off), *dout = (double *)(h->meas.as<char>() + out_off);
+  SlabSum sum{h};
+  HIP_TRY(sum.reserve(kExpectBlocks, qh::kExpectT, nterms));
   uint64_t batches = 0;
   for (uint64_t first = 0; first < nterms;) {
     uint64_t cnt = 1;
@@ -2798,17 +2678,16 @@ int qh_expect_pauli(qh_handle h, uint64_t nterms, const uint64_t *xmask, const u
     const int tt = cnt <= 4 ? 4 : qh::kExpectT;
     with_real(h, [&](auto x) {
       using R = decltype(x);
-      if (tt == 4) launch_expect<R, 4>(h, pair, (unsigned)nblk, a, slab);
-      else launch_expect<R, qh::kExpectT>(h, pair, (unsigned)nblk, a, slab);
+      if (tt == 4) launch_expect<R, 4>(h, pair, (unsigned)nblk, a, sum.slab);
+      else launch_expect<R, qh::kExpectT>(h, pair, (unsigned)nblk, a, sum.slab);
     });
-    hipLaunchKernelGGL(qh::k_expect_fold, dim3((unsigned)cnt), dim3(256), 0, h->stream, (const double *)slab, (uint32_t)nblk, tt,
-                       pair ? 2.0 : 1.0, dout + first);
+    sum.fold(nblk, tt, (unsigned)cnt, pair ? 2.0 : 1.0, first);
     if ((rc = check_launch(h))) return rc;
     first += cnt;
     ++batches;
   }
   std::vector<double> vals(nterms);
-  if ((rc = read_back(h, vals.data(), dout, (size_t)nterms * sizeof(double)))) return rc;
+  if ((rc = sum.get(vals.data(), nterms))) return rc;
   for (uint64_t k = 0; k < nterms; ++k) out[terms[k].idx] = vals[k];
   h->stats.kernels_launched += batches;      // reads of the state: one per batch
   h->stats.bytes_swept += batches * ((1ull << h->nloc) * h->amp_bytes());

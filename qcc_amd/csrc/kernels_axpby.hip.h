@@ -1,17 +1,11 @@
 // kernels_axpby.hip.h -- dst := alpha * dst + beta * src for two states that both live in HBM (qh_axpby), amplitude by
 // amplitude, matched by LOGICAL index, written in place into dst where it lies.
 //
-// The siblings of the k_inner_* readers (kernels_inner.hip.h) that WRITE: the same plan (inner_plan.h, a = dst, b = src), the
-// same geometry (chunks of 256 * kInnerLoads items, chunks of 2^kInnerChunkBits tiles, at most 4096 blocks), the same three
-// walks.  Every thread stores to the address it loaded dst from, so no thread ever reads what another one writes.
-//   * k_axpby_linear (same layout, or src not read at all): 16 bytes per lane and access at both widths, kInnerLoads loads of
-//     each state in flight per thread, non-temporal loads and non-temporal 16-byte stores.
-//   * k_axpby_tiles (different layouts, >= 8 local bits): thread r loads dst's in-tile index r and src's in-tile index r in
-//     src's enumeration; src's values cross through the XOR-swizzled LDS slots exactly as in k_inner_tiles; the thread
-//     combines and stores one amplitude (16 bytes of complex128, 8 of complex64).  Both states are touched in runs of 16.
-//   * k_axpby_gather (fewer than 8 local bits): one block, src's partner index bit by bit.
+// The operation of the two-state walks (kernels_two_state.hip.h, a = dst, b = src) that WRITES: it combines the pair and
+// stores the new amplitude at dst's address, 16 bytes per lane in the linear walk at both widths, one amplitude (16 bytes of
+// complex128, 8 of complex64) in the other two, non-temporal.
 // RD = false (alpha == 0 exactly): dst's old values are never loaded -- NaN or Inf in them cannot propagate and the pass is
-// two streams.  RS = false (beta == 0 exactly): src is never loaded; layouts then do not matter and the linear kernel runs
+// two streams.  RS = false (beta == 0 exactly): src is never loaded; layouts then do not matter and the linear walk runs
 // whatever the plan says.  Both false: one stream of zeros.
 //
 // Arithmetic: each component of the new amplitude is formed in double from the stored amplitudes, as
@@ -21,13 +15,13 @@
 // rounded to float equals the float sum: 53 >= 2 * 24 + 2 bits).
 //
 // norm (a uniform branch; nothing is summed or written to the slab without it): sum |a|^2 of the values AS STORED, after the
-// rounding, in double and in the fixed order of the readers: thread (its items in order) -> wave (xor tree) -> the four waves
-// in order -> one row per block (inner_block_sum) -> k_expect_fold adds the rows in block order.  No atomics.
+// rounding, in double and in the fixed order of the readers (kernels_common.hip.h), as the first of the walk's two sums.
+// No atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "kernels_inner.hip.h"
+#include "kernels_common.hip.h"
 
 namespace qh {
 
@@ -75,9 +69,9 @@ __device__ __forceinline__ void axpby_round(const AxpbyCoef &c, R dr, R di, R sr
 }
 
 template <bool RD, bool RS>
-__device__ __forceinline__ InnerItem<double>::vec axpby_item(const AxpbyCoef &c, const InnerItem<double>::vec &d, const InnerItem<double>::vec &s,
+__device__ __forceinline__ Item16<double>::vec axpby_item(const AxpbyCoef &c, const Item16<double>::vec &d, const Item16<double>::vec &s,
                                                              double &n2) {
-  InnerItem<double>::vec o;
+  Item16<double>::vec o;
   double re, im;
   axpby_round<double, RD, RS>(c, d.x, d.y, s.x, s.y, re, im, n2);
   o.x = re;
@@ -85,9 +79,9 @@ __device__ __forceinline__ InnerItem<double>::vec axpby_item(const AxpbyCoef &c,
   return o;
 }
 template <bool RD, bool RS>
-__device__ __forceinline__ InnerItem<float>::vec axpby_item(const AxpbyCoef &c, const InnerItem<float>::vec &d, const InnerItem<float>::vec &s,
+__device__ __forceinline__ Item16<float>::vec axpby_item(const AxpbyCoef &c, const Item16<float>::vec &d, const Item16<float>::vec &s,
                                                             double &n2) {
-  InnerItem<float>::vec o;
+  Item16<float>::vec o;
   float re0, im0, re1, im1;
   axpby_round<float, RD, RS>(c, d.x, d.y, s.x, s.y, re0, im0, n2);
   axpby_round<float, RD, RS>(c, d.z, d.w, s.z, s.w, re1, im1, n2);
@@ -100,10 +94,10 @@ __device__ __forceinline__ InnerItem<float>::vec axpby_item(const AxpbyCoef &c, 
 
 // one amplitude out, as one non-temporal store of its full size
 __device__ __forceinline__ void axpby_store(double2 *p, double re, double im) {
-  InnerItem<double>::vec v;
+  Item16<double>::vec v;
   v.x = re;
   v.y = im;
-  __builtin_nontemporal_store(v, (InnerItem<double>::vec *)p);
+  __builtin_nontemporal_store(v, (Item16<double>::vec *)p);
 }
 __device__ __forceinline__ void axpby_store(float2 *p, float re, float im) {
   typedef float half_item __attribute__((ext_vector_type(2)));
@@ -113,127 +107,18 @@ __device__ __forceinline__ void axpby_store(float2 *p, float re, float im) {
   __builtin_nontemporal_store(v, (half_item *)p);
 }
 
-// chunks of 2^cw ITEMS (cw <= 8 + log2 kInnerLoads), cpb chunks per block; thread t takes positions t + 256 u (k_inner_linear)
-template <typename R, bool RD, bool RS>
-__global__ __launch_bounds__(256) void k_axpby_linear(typename AmpT<R>::type *__restrict__ pd, const typename AmpT<R>::type *__restrict__ ps,
-                                                       AxpbyCoef c, int cw, uint32_t cpb, double *__restrict__ slab) {
-  using V = typename InnerItem<R>::vec;
-  V *__restrict__ qd = (V *)pd;
-  const V *__restrict__ qs = (const V *)ps;
-  const uint32_t tid = threadIdx.x, ch = 1u << cw;
-  double n2 = 0.0;
-  const uint64_t q0 = (uint64_t)blockIdx.x * cpb;
-  for (uint64_t q = q0; q < q0 + cpb; ++q) {
-    const uint64_t base = q << cw;
-    V vd[kInnerLoads], vs[kInnerLoads];
-#pragma unroll
-    for (int u = 0; u < kInnerLoads; ++u) {
-      vd[u] = (V)0;
-      vs[u] = (V)0;
-      const uint32_t pos = tid + 256u * u;
-      if (pos < ch) {
-        if constexpr (RD) vd[u] = __builtin_nontemporal_load(qd + (base | pos));
-        if constexpr (RS) vs[u] = __builtin_nontemporal_load(qs + (base | pos));
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < kInnerLoads; ++u) {
-      const uint32_t pos = tid + 256u * u;
-      if (pos < ch) __builtin_nontemporal_store(axpby_item<RD, RS>(c, vd[u], vs[u], n2), qd + (base | pos));
-    }
+template <bool RD_, bool RS_> struct AxpbyOp {
+  static constexpr bool RD = RD_, RS = RS_, kWrites = true;
+  AxpbyCoef c;
+  __device__ __forceinline__ bool sums() const { return c.norm; }
+  template <typename V> __device__ __forceinline__ void item(V *at, const V &d, const V &s, double &n2, double &) const {
+    __builtin_nontemporal_store(axpby_item<RD, RS>(c, d, s, n2), at);
   }
-  if (c.norm) inner_block_sum(n2, 0.0, slab);
-}
-
-// the walk of k_inner_tiles with a = dst, b = src; src is always read here (beta == 0 takes the linear kernel)
-template <typename R, bool RD>
-__global__ __launch_bounds__(256) void k_axpby_tiles(typename AmpT<R>::type *__restrict__ pd, const typename AmpT<R>::type *__restrict__ ps,
-                                                      AxpbyCoef c, InnerTileArgs t, double *__restrict__ slab) {
-  using A = typename AmpT<R>::type;
-  __shared__ A xb[kInnerU][256];
-  __shared__ uint64_t low_a[1 << kInnerChunkBits], low_b[1 << kInnerChunkBits];
-  const uint32_t tid = threadIdx.x, ntc = 1u << t.cbits;
-  // this thread inside any tile: its offset in dst's and in src's enumeration, and the slot that holds its partner
-  uint64_t da = tid & 15u, db = tid & 15u;
-  uint32_t slot = 0;
-#pragma unroll
-  for (int k = 0; k < kInnerTileBits; ++k) {
-    const uint64_t bit = (tid >> k) & 1u;
-    if (k >= 4) {
-      da |= bit << t.tile_a[k];
-      db |= bit << t.tile_b[k];
-    }
-    slot |= (uint32_t)bit << t.shuffle[k];
+  template <typename A> __device__ __forceinline__ void amp(A *at, const A &d, const A &s, double &n2, double &) const {
+    decltype(d.x) outr, outi;
+    axpby_round<decltype(d.x), RD, RS>(c, d.x, d.y, s.x, s.y, outr, outi, n2);
+    axpby_store(at, outr, outi);
   }
-  const uint32_t put = tid ^ (tid >> 4), get = slot ^ (slot >> 4);
-  if (tid < ntc) {
-    uint64_t la = 0, lb = 0;
-    for (int k = 0; k < t.cbits; ++k) {
-      const uint64_t bit = (tid >> k) & 1u;
-      la |= bit << t.rest_a[k];
-      lb |= bit << t.rest_b[k];
-    }
-    low_a[tid] = la;
-    low_b[tid] = lb;
-  }
-  __syncthreads();
-  double n2 = 0.0;
-  const uint64_t q0 = (uint64_t)blockIdx.x * t.cpb;
-  for (uint64_t q = q0; q < q0 + t.cpb; ++q) {
-    uint64_t ha = 0, hb = 0;      // the chunk number, spread to dst's and to src's positions (uniform over the block)
-    for (int k = t.cbits; k < t.nrest; ++k) {
-      const uint64_t bit = (q >> (k - t.cbits)) & 1ull;
-      ha |= bit << t.rest_a[k];
-      hb |= bit << t.rest_b[k];
-    }
-    for (uint32_t j0 = 0; j0 < ntc; j0 += kInnerU) {
-      A vd[kInnerU], vs[kInnerU];
-#pragma unroll
-      for (int u = 0; u < kInnerU; ++u) {
-        vd[u].x = 0; vd[u].y = 0;
-        vs[u].x = 0; vs[u].y = 0;
-        if (j0 + u < ntc) {
-          if constexpr (RD) vd[u] = ld_amp<true>(pd + (ha | low_a[j0 + u] | da));
-          vs[u] = ld_amp<true>(ps + (hb | low_b[j0 + u] | db));
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kInnerU; ++u) xb[u][put] = vs[u];
-      __syncthreads();
-#pragma unroll
-      for (int u = 0; u < kInnerU; ++u) {
-        if (j0 + u < ntc) {
-          const A p = xb[u][get];
-          R outr, outi;
-          axpby_round<R, RD, true>(c, vd[u].x, vd[u].y, p.x, p.y, outr, outi, n2);
-          axpby_store(pd + (ha | low_a[j0 + u] | da), outr, outi);
-        }
-      }
-      __syncthreads();
-    }
-  }
-  if (c.norm) inner_block_sum(n2, 0.0, slab);
-}
-
-// nloc < 8: one block, thread i holds dst_i and fetches src's partner
-template <typename R, bool RD>
-__global__ __launch_bounds__(256) void k_axpby_gather(typename AmpT<R>::type *__restrict__ pd, const typename AmpT<R>::type *__restrict__ ps,
-                                                       AxpbyCoef c, InnerGatherArgs g, double *__restrict__ slab) {
-  using A = typename AmpT<R>::type;
-  const uint32_t i = threadIdx.x;
-  double n2 = 0.0;
-  if (i < (1u << g.nloc)) {
-    uint32_t j = 0;
-    for (int p = 0; p < g.nloc; ++p) j |= ((i >> p) & 1u) << g.pos_b[p];
-    A d;
-    d.x = 0; d.y = 0;
-    if constexpr (RD) d = pd[i];
-    const A s = ps[j];
-    R outr, outi;
-    axpby_round<R, RD, true>(c, d.x, d.y, s.x, s.y, outr, outi, n2);
-    axpby_store(pd + i, outr, outi);
-  }
-  if (c.norm) inner_block_sum(n2, 0.0, slab);
-}
+};
 
 }  // namespace qh

@@ -20,13 +20,14 @@
 // sign bit of the term's coefficient (+-1 or 0, one for Re w and one for Im w) in scalar registers, and the item costs
 // two double FMAs per term.  The thread part is applied once to the thread's accumulator at the end.
 //
-// Reductions are in double and in a fixed order, no atomics: thread (chunks in order, u in order) -> wave (xor tree) ->
-// the four waves in order -> one slab row per block -> k_expect_fold sums the rows in block order.  The same state in
-// the same layout gives bitwise the same values.
+// Reductions are in double and in the fixed order of kernels_common.hip.h, no atomics: thread (chunks in order, u in order)
+// -> block_row_sum, one slab row per block -> k_slab_fold sums the rows in block order.  The same state in the same layout
+// gives bitwise the same values.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernels_common.hip.h"
 #include "kernels_gate.hip.h"
 
 namespace qh {
@@ -60,7 +61,6 @@ __global__ __launch_bounds__(256) void k_expect_batch(const typename AmpT<R>::ty
                                                        double *__restrict__ slab) {
   using A = typename AmpT<R>::type;
   constexpr int PER = PAIR ? kExpectLoads / 2 : kExpectLoads;
-  __shared__ double wpart[4][TT];
   const uint32_t tid = threadIdx.x, ch = 1u << a.cw;
   const int xl = (int)(a.x & 63ull);
   const uint64_t xh = a.x & ~63ull, low = PAIR ? (1ull << a.tb) - 1ull : 0ull;
@@ -106,29 +106,9 @@ __global__ __launch_bounds__(256) void k_expect_batch(const typename AmpT<R>::ty
     }
   }
 #pragma unroll
-  for (int t = 0; t < TT; ++t) {
-    double v = (__builtin_popcount(tid & a.zt[t]) & 1) ? -acc[t] : acc[t];
-    v = wave_sum(v);
-    if ((tid & 63u) == 0) wpart[tid >> 6][t] = v;
-  }
-  __syncthreads();
-  if (tid < TT) slab[(uint64_t)blockIdx.x * TT + tid] = ((wpart[0][tid] + wpart[1][tid]) + wpart[2][tid]) + wpart[3][tid];
-}
-
-// out[t] = scale * (sum of column t of the slab): block t; thread j sums rows j, j + 256, ... in order, then a fixed tree
-__global__ __launch_bounds__(256) void k_expect_fold(const double *__restrict__ slab, uint32_t nblk, int tt, double scale,
-                                                     double *__restrict__ out) {
-  __shared__ double part[256];
-  const uint32_t t = blockIdx.x, j = threadIdx.x;
-  double s = 0.0;
-  for (uint32_t b = j; b < nblk; b += 256) s += slab[(uint64_t)b * tt + t];
-  part[j] = s;
-  __syncthreads();
-  for (uint32_t h = 128; h > 0; h >>= 1) {
-    if (j < h) part[j] += part[j + h];
-    __syncthreads();
-  }
-  if (j == 0) out[t] = part[0] * scale;
+  for (int t = 0; t < TT; ++t)
+    if (__builtin_popcount(tid & a.zt[t]) & 1) acc[t] = -acc[t];
+  block_row_sum(acc, slab);
 }
 
 }  // namespace qh

@@ -26,6 +26,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernels_common.hip.h"
+
 namespace qh {
 
 constexpr int kMaxIns = 15;   // 12 bits a plan may fold into the tile enumeration + 3 slab bits of a launch around an exchange
@@ -356,13 +358,8 @@ __global__ __launch_bounds__(256) void k_permute_bits(const typename AmpT<R>::ty
 }
 
 // ---- readers ----------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// out[0] += sum |a|^2 over indices i with (i & mask) == want (mask==0: all).
+// out[0] += sum |a|^2 over indices i with (i & mask) == want (mask==0: all).  The block's sum is formed in the fixed order
+// of kernels_common.hip.h; the blocks then meet in one atomic add, so the result depends on their order of arrival.
 template <typename R>
 __global__ __launch_bounds__(256) void k_norm2(const typename AmpT<R>::type *__restrict__ psi,
                                                 uint64_t n, uint64_t mask, uint64_t want, double *out) {
@@ -381,18 +378,17 @@ __global__ __launch_bounds__(256) void k_norm2(const typename AmpT<R>::type *__r
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      if (on[k]) acc += (double)a[k].x * (double)a[k].x + (double)a[k].y * (double)a[k].y;
+      if (on[k]) acc += prob_sum(a[k].x, a[k].y);
   }
   for (; i < n; i += stride) {
     if ((i & mask) == want) {
       const auto a = ld_amp<true>(psi + i);
-      acc += (double)a.x * (double)a.x + (double)a.y * (double)a.y;
+      acc += prob_sum(a.x, a.y);
     }
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+  wave_partial(acc, part);
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, part[0] + part[1] + part[2] + part[3]);
+  if (threadIdx.x == 0) atomicAdd(out, four_waves(part));
 }
 
 // zero every amplitude whose bit `bit` differs from `value`.

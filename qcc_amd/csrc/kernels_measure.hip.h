@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernels_common.hip.h"
 #include "kernels_gate.hip.h"
 
 namespace qh {
@@ -58,10 +59,6 @@ __device__ __forceinline__ uint32_t pdep32(uint32_t v, uint32_t mask) {
   return o;
 }
 
-template <typename A> __device__ __forceinline__ double prob2(const A &a) {
-  return (double)a.x * (double)a.x + (double)a.y * (double)a.y;     // (as k_norm2)
-}
-
 // chunk index of the r-th chunk whose outer bits equal o (bits inserted at opos, ascending: as expand_index)
 __device__ __forceinline__ uint64_t outer_chunk(uint64_t r, uint64_t o, const MarginalArgs &a) {
   for (int s = 0; s < a.ko; ++s) {
@@ -89,7 +86,7 @@ __global__ __launch_bounds__(256) void k_marginal_bins(const typename AmpT<R>::t
       if (tid + 256u * u < ch) v[u] = ld_amp<true>(base + tid + 256u * u);
 #pragma unroll
     for (int u = 0; u < kMeasPer; ++u)
-      if (tid + 256u * u < ch) acc[u] += prob2(v[u]);
+      if (tid + 256u * u < ch) acc[u] += prob_sum(v[u].x, v[u].y);
   }
 #pragma unroll
   for (int u = 0; u < kMeasPer; ++u)
@@ -134,11 +131,11 @@ __global__ __launch_bounds__(256) void k_marginal_fold(const double *__restrict_
   }
 }
 
+// the block's sum to every thread, in the readers' fixed order (kernels_common.hip.h); wpart may be used again on return
 __device__ __forceinline__ double block_sum_256(double v, double *wpart) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) wpart[threadIdx.x >> 6] = v;
+  wave_partial(v, wpart);
   __syncthreads();
-  const double s = ((wpart[0] + wpart[1]) + wpart[2]) + wpart[3];
+  const double s = four_waves(wpart);
   __syncthreads();
   return s;
 }
@@ -158,17 +155,11 @@ __global__ __launch_bounds__(256) void k_chunk_sums(const typename AmpT<R>::type
     double acc = 0.0;
 #pragma unroll
     for (int u = 0; u < kMeasPer; ++u)
-      if (tid + 256u * u < ch) acc += prob2(v[u]);
+      if (tid + 256u * u < ch) acc += prob_sum(v[u].x, v[u].y);
     acc = block_sum_256(acc, wpart);
     if (tid == 0) sums[q] = acc;
   }
 }
-
-// physical (local) -> logical index through five byte tables (as k_argmax_logical): bit p of the index goes to bit to[p]
-struct MeasMap {
-  uint8_t to[40];
-  uint64_t shard_logical;    // logical bits the shard index holds, as they are on this shard
-};
 
 // Shot s of the chunk list entry e (chunk ids[e], shots [first[e], first[e + 1])) has target[s] in [0, chunk sum): its
 // amplitude is the first one at which the chunk's running sum exceeds the target (clamped to the chunk's last nonzero
@@ -176,21 +167,16 @@ struct MeasMap {
 template <typename R>
 __global__ __launch_bounds__(256) void k_chunk_locate(const typename AmpT<R>::type *__restrict__ psi, int c,
                                                        const uint64_t *__restrict__ ids, const uint64_t *__restrict__ first,
-                                                       uint64_t nlist, const double *__restrict__ target, MeasMap mm,
+                                                       uint64_t nlist, const double *__restrict__ target, IndexMap mm,
                                                        uint64_t *__restrict__ out) {
   using A = typename AmpT<R>::type;
   __shared__ double S[1 << kMeasChunkBits];
   __shared__ uint64_t nzw[(1 << kMeasChunkBits) / 64];
-  __shared__ uint64_t lut[5 * 256];
+  __shared__ uint64_t lut[kIndexLutWords];      // (read behind the syncs of the scan)
   __shared__ double wtot[4];
   __shared__ int lastnz;
   const uint32_t tid = threadIdx.x, ch = 1u << c;
-  for (int t = 0; t < 5; ++t) {
-    uint64_t o = 0;
-    const uint64_t v = (uint64_t)tid << (8 * t);
-    for (int p = 8 * t; p < 8 * t + 8 && p < 40; ++p) o |= ((v >> p) & 1ull) << mm.to[p];
-    lut[t * 256 + tid] = o;
-  }
+  build_index_lut(lut, mm);
   const uint32_t per = ch >= 256 ? ch / 256 : 1u;        // positions per thread in the scan (contiguous run)
   const bool active = tid * per < ch;
   const uint32_t nwords = (ch + 63) / 64;
@@ -206,7 +192,7 @@ __global__ __launch_bounds__(256) void k_chunk_locate(const typename AmpT<R>::ty
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < kMeasPer; ++u)
-      if (tid + 256u * u < ch) S[tid + 256u * u] = prob2(v[u]);
+      if (tid + 256u * u < ch) S[tid + 256u * u] = prob_sum(v[u].x, v[u].y);
     __syncthreads();
     double run = 0.0;
     int nz = -1;
@@ -260,8 +246,7 @@ __global__ __launch_bounds__(256) void k_chunk_locate(const typename AmpT<R>::ty
       }
       if (i < 0) i = 0;                   // (cannot happen: a chunk with shots has a nonzero amplitude)
       const uint64_t idx = (q << c) | (uint64_t)i;
-      out[s] = lut[idx & 255] | lut[256 + ((idx >> 8) & 255)] | lut[512 + ((idx >> 16) & 255)] |
-               lut[768 + ((idx >> 24) & 255)] | lut[1024 + ((idx >> 32) & 255)] | mm.shard_logical;
+      out[s] = index_lut_logical(lut, idx) | mm.shard_logical;
     }
     __syncthreads();
   }

@@ -16,12 +16,13 @@
 //     item share their fate and land in one item (a 16-byte store); with position 0 released exactly one of them can be
 //     kept, and it goes out as one 8-byte store (SPLIT).  Amplitudes are copied as stored.  Sums are in double, in a fixed
 //     order, no atomics: thread (chunks in order, u in order) -> wave -> the four waves in order -> one (kept, dropped) row
-//     per block (inner_block_sum) -> k_expect_fold adds the rows in block order.
+//     per block (block_row_sum, kernels_common.hip.h) -> k_slab_fold adds the rows in block order.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "kernels_inner.hip.h"
+#include "kernels_common.hip.h"
+#include "kernels_gate.hip.h"
 #include "resize_plan.h"
 
 namespace qh {
@@ -39,14 +40,14 @@ struct ExtendArgs {
   uint64_t nchunks;            // 2^(ib - cw)
 };
 
-__device__ __forceinline__ InnerItem<double>::vec resize_mul(const double2 &f, const InnerItem<double>::vec &v) {
-  InnerItem<double>::vec o;
+__device__ __forceinline__ Item16<double>::vec resize_mul(const double2 &f, const Item16<double>::vec &v) {
+  Item16<double>::vec o;
   o.x = f.x * v.x - f.y * v.y;
   o.y = f.x * v.y + f.y * v.x;
   return o;
 }
-__device__ __forceinline__ InnerItem<float>::vec resize_mul(const float2 &f, const InnerItem<float>::vec &v) {
-  InnerItem<float>::vec o;
+__device__ __forceinline__ Item16<float>::vec resize_mul(const float2 &f, const Item16<float>::vec &v) {
+  Item16<float>::vec o;
   o.x = f.x * v.x - f.y * v.y;
   o.y = f.x * v.y + f.y * v.x;
   o.z = f.x * v.z - f.y * v.w;
@@ -57,7 +58,7 @@ __device__ __forceinline__ InnerItem<float>::vec resize_mul(const float2 &f, con
 template <typename R>
 __global__ __launch_bounds__(256) void k_extend(const typename AmpT<R>::type *__restrict__ src, typename AmpT<R>::type *__restrict__ dst,
                                                  const typename AmpT<R>::type *__restrict__ tab, ExtendArgs a) {
-  using V = typename InnerItem<R>::vec;
+  using V = typename Item16<R>::vec;
   const V *__restrict__ qs = (const V *)src;
   V *__restrict__ qd = (V *)dst;
   const uint32_t tid = threadIdx.x, pmask = (1u << a.cw) - 1u, jstep = 1u << (kResizeChunkBits - a.cw);
@@ -102,19 +103,19 @@ __device__ __forceinline__ uint64_t release_dest(const ReleaseArgs &a, uint64_t 
 
 // one item: where it goes, and its weight to the side it ends on
 template <bool SPLIT>
-__device__ __forceinline__ void release_item(const ReleaseArgs &a, uint64_t item, const InnerItem<double>::vec &v, double2 *__restrict__ dst,
+__device__ __forceinline__ void release_item(const ReleaseArgs &a, uint64_t item, const Item16<double>::vec &v, double2 *__restrict__ dst,
                                              double &kept, double &dropped) {
   const bool keep = (item & a.drop) == a.want;
-  const double w = v.x * v.x + v.y * v.y;
-  if (keep) __builtin_nontemporal_store(v, (InnerItem<double>::vec *)dst + release_dest(a, item));
+  const double w = prob_sum(v.x, v.y);
+  if (keep) __builtin_nontemporal_store(v, (Item16<double>::vec *)dst + release_dest(a, item));
   kept += keep ? w : 0.0;
   dropped += keep ? 0.0 : w;
 }
 template <bool SPLIT>
-__device__ __forceinline__ void release_item(const ReleaseArgs &a, uint64_t item, const InnerItem<float>::vec &v, float2 *__restrict__ dst,
+__device__ __forceinline__ void release_item(const ReleaseArgs &a, uint64_t item, const Item16<float>::vec &v, float2 *__restrict__ dst,
                                              double &kept, double &dropped) {
   const uint64_t p = item << 1;
-  const double w0 = (double)v.x * (double)v.x + (double)v.y * (double)v.y, w1 = (double)v.z * (double)v.z + (double)v.w * (double)v.w;
+  const double w0 = prob_sum(v.x, v.y), w1 = prob_sum(v.z, v.w);
   if constexpr (SPLIT) {      // position 0 is released: the halves of the item part ways
     const bool k0 = (p & a.drop) == a.want, k1 = ((p | 1ull) & a.drop) == a.want;
     typedef float half_item __attribute__((ext_vector_type(2)));
@@ -130,7 +131,7 @@ __device__ __forceinline__ void release_item(const ReleaseArgs &a, uint64_t item
     dropped += k1 ? 0.0 : w1;
   } else {                    // position 0 survives, at position 0: both halves share the predicate and one destination item
     const bool keep = (p & a.drop) == a.want;
-    if (keep) __builtin_nontemporal_store(v, (InnerItem<float>::vec *)dst + (release_dest(a, p) >> 1));
+    if (keep) __builtin_nontemporal_store(v, (Item16<float>::vec *)dst + (release_dest(a, p) >> 1));
     kept += keep ? w0 : 0.0;
     kept += keep ? w1 : 0.0;
     dropped += keep ? 0.0 : w0;
@@ -141,7 +142,7 @@ __device__ __forceinline__ void release_item(const ReleaseArgs &a, uint64_t item
 template <typename R, bool SPLIT>
 __global__ __launch_bounds__(256) void k_release(const typename AmpT<R>::type *__restrict__ src, typename AmpT<R>::type *__restrict__ dst,
                                                   ReleaseArgs a, double *__restrict__ slab) {
-  using V = typename InnerItem<R>::vec;
+  using V = typename Item16<R>::vec;
   const V *__restrict__ qs = (const V *)src;
   const uint32_t tid = threadIdx.x, ch = 1u << a.cw;
   double kept = 0.0, dropped = 0.0;
@@ -160,7 +161,8 @@ __global__ __launch_bounds__(256) void k_release(const typename AmpT<R>::type *_
       if (pos < ch) release_item<SPLIT>(a, base | pos, v[u], dst, kept, dropped);
     }
   }
-  inner_block_sum(kept, dropped, slab);
+  const double row[2] = {kept, dropped};
+  block_row_sum(row, slab);
 }
 
 }  // namespace qh

@@ -2,7 +2,7 @@
 // reduction.  qh_select (everything at or above a threshold), qh_topk (the k most probable) and qh_amplitudes (the entries
 // at given indices).
 //
-// A probability is fma(im, im, re * re) in double (as qh_argmax and the sweep islands compute it); its bit pattern, the
+// A probability is prob_fma (kernels_common.hip.h: as qh_argmax and the sweep islands compute it); its bit pattern, the
 // KEY, orders like the probability because it is never negative (the remark k_tmax_reduce relies on).  Every selection is
 // a range of keys.
 //
@@ -13,7 +13,7 @@
 //     and a wave that has seen the counter at or past `cap` stops asking: the counter only grows, so none of its later
 //     hits could be written.  It counts them in a register and adds them once when it leaves (the dense case -- every
 //     amplitude a hit, count only -- starts there and makes one atomic per wave, not one per chunk).  The physical -> logical map is
-//     applied to hits only, through the five LDS byte tables of k_chunk_locate.  The order of the entries depends on
+//     applied to hits only, through the LDS byte tables of kernels_common.hip.h.  The order of the entries depends on
 //     the order in which waves reach the counter: the host sorts.  The weight (sum of the hits' probabilities) is summed
 //     per thread over its chunks in order, then over the block in the fixed order of block_sum_256, one partial per block:
 //     no float atomics, the same bits for the same state, layout and grid.
@@ -28,6 +28,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernels_common.hip.h"
+#include "kernels_gate.hip.h"
 #include "kernels_measure.hip.h"
 
 namespace qh {
@@ -37,8 +39,6 @@ struct SelEntry {            // == qh_entry (include/qcc_hip.h)
   double re, im;
 };
 
-__device__ __forceinline__ double sel_prob(double2 a) { return __builtin_fma(a.y, a.y, a.x * a.x); }
-__device__ __forceinline__ double sel_prob(float2 a) { return __builtin_fma((double)a.y, (double)a.y, (double)a.x * (double)a.x); }
 __device__ __forceinline__ uint64_t sel_key(double p) { return (uint64_t)__double_as_longlong(p); }
 
 // One 16-byte non-temporal load per thread and slot at either width: one complex128 amplitude, or two consecutive complex64
@@ -67,31 +67,18 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t ballot) {      // set bit
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
 }
 
-__device__ __forceinline__ void build_meas_lut(uint64_t *lut, const MeasMap &mm) {
-  for (int t = 0; t < 5; ++t) {
-    uint64_t o = 0;
-    const uint64_t v = (uint64_t)threadIdx.x << (8 * t);
-    for (int p = 8 * t; p < 8 * t + 8 && p < 40; ++p) o |= ((v >> p) & 1ull) << mm.to[p];
-    lut[t * 256 + threadIdx.x] = o;
-  }
-}
-__device__ __forceinline__ uint64_t lut_logical(const uint64_t *lut, uint64_t idx) {
-  return lut[idx & 255] | lut[256 + ((idx >> 8) & 255)] | lut[512 + ((idx >> 16) & 255)] | lut[768 + ((idx >> 24) & 255)] |
-         lut[1024 + ((idx >> 32) & 255)];
-}
-
 // Hits: klo <= key <= khi.  counter: the running number of hits (u64, zeroed by the host).  out: cap entries (may be
 // null with cap == 0).  wpart: one weight partial per block.
 template <typename R>
 __global__ __launch_bounds__(256) void k_select(const typename AmpT<R>::type *__restrict__ psi, int c, uint64_t nchunks, uint64_t klo,
-                                                 uint64_t khi, MeasMap mm, unsigned long long *__restrict__ counter,
+                                                 uint64_t khi, IndexMap mm, unsigned long long *__restrict__ counter,
                                                  SelEntry *__restrict__ out, uint64_t cap, double *__restrict__ wpart) {
   using A = typename AmpT<R>::type;
   constexpr int PACK = sizeof(double2) / sizeof(A);
-  __shared__ uint64_t lut[5 * 256];
+  __shared__ uint64_t lut[kIndexLutWords];
   __shared__ double wsum[4];
   const uint32_t tid = threadIdx.x, ch = 1u << c, lane = tid & 63;
-  build_meas_lut(lut, mm);
+  build_index_lut(lut, mm);
   __syncthreads();
   double weight = 0.0;
   unsigned long long late = 0;      // this wave's hits after it has seen the counter at or past cap (the same in every lane)
@@ -105,7 +92,7 @@ __global__ __launch_bounds__(256) void k_select(const typename AmpT<R>::type *__
     for (int u = 0; u < kMeasPer; ++u) {
       bool hit = false;
       if (sel_pos<PACK>(u) < ch) {
-        const double p = sel_prob(v[u]);
+        const double p = prob_fma(v[u]);
         const uint64_t key = sel_key(p);
         hit = key >= klo && key <= khi;
         if (hit) weight += p;
@@ -134,17 +121,16 @@ __global__ __launch_bounds__(256) void k_select(const typename AmpT<R>::type *__
       if (pos >= cap) continue;
       const uint64_t idx = (q << c) | (uint64_t)sel_pos<PACK>(u);
       SelEntry e;
-      e.index = lut_logical(lut, idx) | mm.shard_logical;
+      e.index = index_lut_logical(lut, idx) | mm.shard_logical;
       e.re = (double)v[u].x;
       e.im = (double)v[u].y;
       out[pos] = e;
     }
   }
   if (late && lane == 0) atomicAdd(counter, late);
-  weight = wave_sum(weight);
-  if (lane == 0) wsum[tid >> 6] = weight;
+  wave_partial(weight, wsum);
   __syncthreads();
-  if (tid == 0) wpart[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+  if (tid == 0) wpart[blockIdx.x] = four_waves(wsum);
 }
 
 // ghist[b] += the number of keys k != 0 with (k >> (shift + bits)) == prefix and ((k >> shift) & (2^bits - 1)) == b
@@ -166,7 +152,7 @@ __global__ __launch_bounds__(256) void k_key_hist(const typename AmpT<R>::type *
       bool valid = false;
       uint32_t bin = 0;
       if (sel_pos<PACK>(u) < ch) {
-        const uint64_t key = sel_key(sel_prob(v[u]));
+        const uint64_t key = sel_key(prob_fma(v[u]));
         valid = key != 0 && ((key >> shift) >> bits) == prefix;
         bin = (uint32_t)(key >> shift) & (nb - 1u);
       }
@@ -206,7 +192,7 @@ __global__ __launch_bounds__(256) void k_tie_scan(const A *__restrict__ psi, uin
       l |= bit << tm.log[j];
     }
     const A a = ld_amp<false>(psi + p);
-    if (sel_key(sel_prob(a)) != want) continue;
+    if (sel_key(prob_fma(a)) != want) continue;
     const unsigned long long at = atomicAdd(counter, 1ull);
     if (at < cap) {
       SelEntry e;

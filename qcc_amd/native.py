@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB_PATH = os.environ.get('QCC_HIP_LIB') or os.path.join(PKG, 'libqcc_hip.so')  # env: A/B builds only
 SOURCES = [os.path.join(PKG, 'csrc', f) for f in
-           ('engine.hip', 'buffers.hip.h', 'kernels_gate.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_perm.hip.h', 'perm_plan.h', 'kernels_measure.hip.h', 'kernels_select.hip.h', 'select_plan.h', 'kernels_expect.hip.h', 'kernels_inner.hip.h', 'kernels_axpby.hip.h', 'inner_plan.h', 'kernels_resize.hip.h', 'resize_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h', 'exchange_plan.h',
+           ('engine.hip', 'buffers.hip.h', 'kernels_common.hip.h', 'kernels_gate.hip.h', 'kernels_argmax.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_perm.hip.h', 'perm_plan.h', 'kernels_measure.hip.h', 'kernels_select.hip.h', 'select_plan.h', 'kernels_expect.hip.h', 'kernels_two_state.hip.h', 'kernels_inner.hip.h', 'kernels_axpby.hip.h', 'inner_plan.h', 'kernels_resize.hip.h', 'resize_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h', 'exchange_plan.h',
             'sweep_island_rb2.inc', 'sweep_island_rb3.inc', 'sweep_island_rb4.inc',
             'sweep_island_rb5.inc', 'sweep_island_f32_rb2.inc', 'sweep_island_f32_rb3.inc',
             'sweep_island_f32_rb4.inc', 'sweep_island_f32_rb5.inc', 'sweep_island_f32_rb6.inc', 'sweep_handlers.inc',

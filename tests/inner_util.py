@@ -1,5 +1,5 @@
 """Shared by tests/test_inner_cpu.py and tests/test_gpu_inner.py: the hand-made layout pairs for qh_inner and a NumPy model
-of how k_inner_tiles walks two states from a qh_inner_tiles plan."""
+of how k_two_tiles walks two states from a qh_inner_tiles plan."""
 import numpy as np
 
 

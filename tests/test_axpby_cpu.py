@@ -1,7 +1,7 @@
 """CPU tests of the linear combination of two states: the C-ABI symbol and its argument checks (NULL, planner-only handles),
 qc.combine / qc.project_out over the NumPy stand-in device, which has no axpby (the host route), and a NumPy model of the
 write walk: scattering alpha * d[ia] + beta * s[ib] to ia over the pairs of the tile walk must give the combination in
-logical order -- the index contract k_axpby_tiles implements."""
+logical order -- the index contract k_two_tiles implements for qh_axpby."""
 import ctypes
 
 import numpy as np

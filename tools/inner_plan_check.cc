@@ -3,7 +3,7 @@
 //       tools/inner_plan_check.cc -o inner_plan_check
 // (the sanitizer runtimes linked statically: the program then runs as it is, in any environment).
 // For hand-made bit maps and `count` random pairs of permutations per size (8..14 local bits, default 200) it walks the
-// tiles as k_inner_tiles does and checks that the (a index, b index) pairs cover every index of both states exactly once
+// tiles as k_two_tiles does and checks that the (a index, b index) pairs cover every index of both states exactly once
 // and are the pairs the bit maps define; then shard bits that differ must be reported.  Exit status 0 = all good.
 #include <algorithm>
 #include <cstdio>
