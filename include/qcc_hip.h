@@ -439,6 +439,50 @@ int qh_inner_plan(qh_handle a, qh_handle b, qh_inner_tiles *out);
  * or a logical bit one handle keeps in the shard index and the other elsewhere; exchange first).                          */
 int qh_axpby(qh_handle dst, const double alpha[2], qh_handle src, const double beta[2], double *norm2);
 
+/* ---- Pauli-sum operators (kernels_pauli.hip.h, pauli_plan.h) ------------------ */
+/* dst := (sum_t c_t P_t) src, out of place.  Term t is a coefficient coeffs[2t], coeffs[2t+1] = (re, im) and two masks over
+ * LOGICAL bits as in qh_expect_pauli (xmask: X or Y on the bit, zmask: Z or Y), nY = popcount(x & z):
+ *   (P a)_i = (-i)^nY (-1)^popcount(i & z) a_{i ^ x},   dst_i = sum_t c_t (P_t src)_i.
+ * Any coefficients are accepted (Hermitian or not is the caller's business); terms are taken as given, never merged or dropped.
+ * Handles: what src has queued runs first and src is read only (state, bit map, relayout mode and pointer as before).  dst is
+ * replaced whole, as by qh_copy: what it has queued is dropped, a poisoned flag is cleared, its exchange arrivals and stream
+ * are waited for; the result goes into dst's CURRENT buffer (attached and host-mapped handles too; relayout mode and second
+ * buffer stay) in src's physical layout, so dst takes src's bit map.  dst's stream waits for src's flushed work (an event),
+ * the kernels run on dst's stream and the host waits: on return both handles are free.
+ * Batches: masks go through the bit map as in qh_expect_pauli; a z bit held by the shard index is a sign folded into the
+ * coefficient on the host, an x bit there is QH_ERR_NONLOCAL (nothing runs, dst untouched).  c'_t = c_t (-i)^nY (shard sign)
+ * is formed on the host by exact swaps and negations.  The terms are stably sorted by physical x mask and cut every
+ * QH_PAULI_SUM_BATCH terms (a batch may hold several x masks; G_b = the distinct ones in batch b); one kernel per batch, the
+ * first writes dst without reading it, the later ones read dst and add to it.  Within a batch every component is formed in
+ * double from the stored amplitudes (complex64 widened unrounded; plus dst's stored value after the first batch) and rounded
+ * once to the handle's width.  A batch of one term with c' = 1 stores the source amplitude bit for bit; c' in {-1, i, -i}
+ * gives it exactly as a number.  nterms == 0: dst becomes zeros in one kernel.
+ * norm2 (may be NULL): sum |a|^2 of dst's FINAL amplitudes as stored, over this shard, in double, in a fixed order without
+ * atomics: bitwise reproducible for given states, layout and terms.
+ * dst's qh_stats (src's are unchanged): kernels_launched + the number of batches (+ 1 for nterms == 0); bytes_swept + the sum
+ * over batches of (G_b + 1 + [b > 0]) x the shard's bytes -- what the kernels request, an upper bound on HBM traffic;
+ * bytes_algorithmic + 2 x the shard's bytes (1 x for nterms == 0).  Works from 1 local bit up, at either width.
+ * Errors, nothing runs and nothing changes: QH_ERR_ARG (null handle, null arrays with nterms > 0, dry handle, dst == src,
+ * another device, different nbits (local or global), width or shard index), QH_ERR_BAD_QUBIT (mask bits >= nbits_global),
+ * QH_ERR_NONLOCAL as above.                                                                                                */
+#define QH_PAULI_SUM_BATCH 16
+int qh_apply_pauli_sum(qh_handle dst, qh_handle src, uint64_t nterms, const double *coeffs /* 2 per term */,
+                       const uint64_t *xmask, const uint64_t *zmask, double *norm2 /* may be NULL */);
+/* The same into a NEW handle made beside src as qh_clone makes its own (without the copy): it owns HBM memory and a stream,
+ * starts with zeroed stats -- which then count this call -- and takes src's bit map.  QH_ERR_NOMEM: nothing is created.    */
+int qh_pauli_sum_new(qh_handle src, uint64_t nterms, const double *coeffs, const uint64_t *xmask,
+                     const uint64_t *zmask, double *norm2, qh_handle *out);
+/* How qh_apply_pauli_sum would batch these terms on src right now: runs nothing, flushes nothing, planner-only handles too.
+ * terms (may be NULL): the nterms terms in sorted order -- index of the caller's term, physical local masks, the sign the
+ * shard index gives (1: negative) and nY mod 4.  batches: at most cap are written, *nbatches is always set; batch b holds
+ * terms [first, first + count), ngroups distinct x masks, and asks for streams = ngroups + 1 + [b > 0] passes over the shard.
+ * The engine launches from this very function.  Errors: QH_ERR_ARG (null), QH_ERR_BAD_QUBIT, QH_ERR_NONLOCAL as above.      */
+typedef struct { uint64_t index, px, pz; uint32_t neg, ny; } qh_pauli_term;
+typedef struct { uint64_t first, count, ngroups, streams; } qh_pauli_batch;
+int qh_pauli_sum_plan(qh_handle src, uint64_t nterms, const uint64_t *xmask, const uint64_t *zmask,
+                      qh_pauli_term *terms /* nterms, sorted order; may be NULL */,
+                      qh_pauli_batch *batches, uint64_t cap, uint64_t *nbatches);
+
 /* ---- growing and shrinking a state (kernels_resize.hip.h) ----------------- */
 /* Both calls make a NEW handle and leave src as qh_clone leaves it: what src has queued runs first (exchange arrivals are
  * waited for); src keeps its amplitudes, bit map, relayout mode and device pointer.  The new handle lives on src's device with

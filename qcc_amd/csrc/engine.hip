@@ -33,6 +33,8 @@
 #include "kernels_select.hip.h"
 #include "select_plan.h"
 #include "kernels_expect.hip.h"
+#include "kernels_pauli.hip.h"
+#include "pauli_plan.h"
 #include "kernels_two_state.hip.h"
 #include "kernels_inner.hip.h"
 #include "kernels_axpby.hip.h"
@@ -757,7 +759,7 @@ int select_device(int device) {
 extern "C" {
 
 const char *qh_last_error(void) { return g_err.c_str(); }
-int qh_version(void) { return 114; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
+int qh_version(void) { return 115; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
 
 int qh_device_count(int *count) {
   if (!count) return fail(QH_ERR_ARG, "null");
@@ -2691,6 +2693,168 @@ int qh_expect_pauli(qh_handle h, uint64_t nterms, const uint64_t *xmask, const u
   for (uint64_t k = 0; k < nterms; ++k) out[terms[k].idx] = vals[k];
   h->stats.kernels_launched += batches;      // reads of the state: one per batch
   h->stats.bytes_swept += batches * ((1ull << h->nloc) * h->amp_bytes());
+  return QH_OK;
+}
+
+}  // extern "C"
+
+// ---- Pauli-sum operators: qh_apply_pauli_sum, qh_pauli_sum_new, qh_pauli_sum_plan (kernels_pauli.hip.h, pauli_plan.h) ------
+namespace {
+
+// The terms on h's bit map as it is now, sorted: masks checked against nglob, local bits as physical masks, a z bit the
+// shard index holds as a sign, an x bit there refused.  Host arithmetic only: valid on dry handles.
+int plan_pauli(const qh_state_s *h, const char *who, uint64_t nterms, const uint64_t *xmask, const uint64_t *zmask,
+               std::vector<qh_pauli_term> *terms) {
+  if (h->nglob < 64)
+    for (uint64_t t = 0; t < nterms; ++t)
+      if ((xmask[t] | zmask[t]) >> h->nglob)
+        return fail(QH_ERR_BAD_QUBIT, "%s: term %llu (x 0x%llx, z 0x%llx) has bits >= %d", who, (unsigned long long)t,
+                    (unsigned long long)xmask[t], (unsigned long long)zmask[t], h->nglob);
+  terms->resize(nterms);
+  for (uint64_t t = 0; t < nterms; ++t) {
+    const Placed x = place(h, to_phys(h, xmask[t])), z = place(h, to_phys(h, zmask[t]));
+    if (x.held) {
+      const int b = __builtin_ctzll(to_logical(h, x.held << h->nloc));     // the first of them
+      return fail(QH_ERR_NONLOCAL, "%s: term %llu has X or Y on logical bit %d, held by the shard index (physical bit %d, "
+                  "local bits: %d); exchange first", who, (unsigned long long)t, b, h->perm[b], h->nloc);
+    }
+    (*terms)[t] = qh_pauli_term{t, x.local, z.local, (uint32_t)__builtin_popcountll(h->shard & z.held) & 1u,
+                                (uint32_t)__builtin_popcountll(xmask[t] & zmask[t]) & 3u};
+  }
+  qh::pauli_sort(terms->data(), nterms);
+  return QH_OK;
+}
+
+// one batch (count == 0: the kernel of zeros) on dst's stream
+void launch_pauli_batch(qh_state_s *dst, const qh_state_s *src, const qh_pauli_term *terms, const double *coeffs, uint64_t count,
+                        bool acc, bool norm, double *slab, uint64_t *nblk) {
+  qh::PauliArgs a{};
+  const int ab = dst->bw == 128 ? 0 : 1;
+  for (uint64_t k = 0; k < count; ++k) {
+    const qh_pauli_term &tm = terms[k];
+    double c[2];
+    qh::pauli_coef(coeffs[2 * tm.index], coeffs[2 * tm.index + 1], tm.ny, tm.neg, c);
+    const qh::PauliZSplit z = qh::pauli_split_z(tm.pz, ab);
+    a.px[k] = tm.px;
+    a.pz[k] = tm.pz;
+    a.zc[k] = (uint32_t)z.chunk;
+    a.cre[k] = c[0];
+    a.cim[k] = c[1];
+    a.zu[k] = (uint16_t)z.reg;
+    a.zt[k] = (uint8_t)z.thread;
+    a.zh |= z.half << k;
+    if (k == 0 || tm.px != terms[k - 1].px) a.start |= 1u << k;
+    if (count == 1 && !acc) a.unit = 1 + qh::pauli_unit(c);
+  }
+  a.count = (int)count;
+  a.acc = acc ? 1 : 0;
+  a.norm = norm ? 1 : 0;
+  with_real(dst, [&](auto x) {
+    using R = decltype(x);
+    if (qh::pauli_main_shape(dst->nloc, ab)) {
+      using V = typename qh::Item16<R>::vec;
+      const qh::PauliGrid g = qh::pauli_grid(dst->nloc, ab);
+      a.cpb = g.cpb;
+      *nblk = g.nblk;
+      const bool few = count <= (uint64_t)qh::kPauliSmallT, one = (a.start & ~1u) == 0;      // (one x mask, or no term at all)
+      const V *ps = (const V *)src->d_psi;
+      V *pd = (V *)dst->d_psi;
+      const dim3 grid((unsigned)g.nblk), block(256);
+      if (few && one) hipLaunchKernelGGL((qh::k_pauli_batch<R, qh::kPauliSmallT, 1>), grid, block, 0, dst->stream, ps, pd, a, slab);
+      else if (few) hipLaunchKernelGGL((qh::k_pauli_batch<R, qh::kPauliSmallT, qh::kPauliSmallT>), grid, block, 0, dst->stream, ps, pd, a, slab);
+      else if (one) hipLaunchKernelGGL((qh::k_pauli_batch<R, qh::kPauliT, 1>), grid, block, 0, dst->stream, ps, pd, a, slab);
+      else hipLaunchKernelGGL((qh::k_pauli_batch<R, qh::kPauliT, qh::kPauliT>), grid, block, 0, dst->stream, ps, pd, a, slab);
+    } else {
+      using A = typename qh::AmpT<R>::type;
+      const uint64_t n = 1ull << dst->nloc;
+      *nblk = (n + 255) / 256;
+      hipLaunchKernelGGL((qh::k_pauli_small<R>), dim3((unsigned)*nblk), dim3(256), 0, dst->stream, (const A *)src->d_psi, (A *)dst->d_psi, a, n,
+                         slab);
+    }
+  });
+}
+
+int check_pauli_arrays(const char *who, uint64_t nterms, const double *coeffs, const uint64_t *xmask, const uint64_t *zmask) {
+  if (nterms && (!coeffs || !xmask || !zmask)) return fail(QH_ERR_ARG, "%s: null coefficients or masks with %llu terms", who, (unsigned long long)nterms);
+  return QH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qh_pauli_sum_plan(qh_handle src, uint64_t nterms, const uint64_t *xmask, const uint64_t *zmask, qh_pauli_term *terms,
+                      qh_pauli_batch *batches, uint64_t cap, uint64_t *nbatches) {
+  if (!src || !nbatches || (nterms && (!xmask || !zmask)) || (cap && !batches))
+    return fail(QH_ERR_ARG, "pauli_sum_plan: null handle, masks, batches or nbatches");
+  std::vector<qh_pauli_term> tv;
+  const int rc = plan_pauli(src, "pauli_sum_plan", nterms, xmask, zmask, &tv);
+  if (rc) return rc;
+  if (terms && nterms) memcpy(terms, tv.data(), nterms * sizeof(qh_pauli_term));
+  *nbatches = qh::pauli_cut(tv.data(), nterms, batches, cap);
+  return QH_OK;
+}
+
+int qh_apply_pauli_sum(qh_handle dst, qh_handle src, uint64_t nterms, const double *coeffs, const uint64_t *xmask,
+                       const uint64_t *zmask, double *norm2) {
+  int rc = check_pair(dst, src, "apply_pauli_sum");
+  if (rc) return rc;
+  if ((rc = check_pauli_arrays("apply_pauli_sum", nterms, coeffs, xmask, zmask))) return rc;
+  if (dst == src) return fail(QH_ERR_ARG, "apply_pauli_sum: dst == src (the operator is applied out of place)");
+  if (dst->shard != src->shard)
+    return fail(QH_ERR_ARG, "apply_pauli_sum: shard %llu against shard %llu", (unsigned long long)dst->shard, (unsigned long long)src->shard);
+  std::vector<qh_pauli_term> terms;
+  // which bits the shard index holds is not something a flush changes: refused before anything runs
+  if ((rc = plan_pauli(src, "apply_pauli_sum", nterms, xmask, zmask, &terms))) return rc;
+  if ((rc = enter(src))) return rc;
+  if ((rc = plan_pauli(src, "apply_pauli_sum", nterms, xmask, zmask, &terms))) return rc;      // the layout the flush left
+  std::vector<qh_pauli_batch> batches(qh::pauli_cut(terms.data(), nterms, nullptr, 0));
+  qh::pauli_cut(terms.data(), nterms, batches.data(), batches.size());
+  // dst is replaced whole, as by qh_copy
+  dst->queue.clear();
+  dst->poisoned = false;
+  if (dst->comm) qh::wait_all_arrivals(&dst->comm->arrivals, dst->stream);
+  if ((rc = wait_stream(dst, dst->stream, "qh_apply_pauli_sum"))) return rc;
+  SlabSum sum{dst};
+  if (norm2) HIP_TRY(sum.reserve(std::max<uint64_t>(qh::kPauliBlocks, 8), 1, 1));
+  if ((rc = order_after(dst, src))) return rc;      // dst's stream reads src: behind everything src's stream has been given
+  uint64_t nblk = 1, streams = 0;
+  if (batches.empty()) {
+    launch_pauli_batch(dst, src, nullptr, coeffs, 0, false, norm2 != nullptr, sum.slab, &nblk);
+    streams = 1;
+  }
+  for (size_t b = 0; b < batches.size(); ++b) {
+    launch_pauli_batch(dst, src, terms.data() + batches[b].first, coeffs, batches[b].count, b > 0, norm2 && b + 1 == batches.size(), sum.slab,
+                       &nblk);
+    streams += batches[b].streams;
+  }
+  if (norm2) sum.fold(nblk, 1, 1);
+  if ((rc = check_launch(dst))) return rc;
+  // the host waits: on return src may be changed and dst read at once
+  if (norm2) rc = sum.get(norm2, 1, "qh_apply_pauli_sum");
+  else rc = wait_stream(dst, dst->stream, "qh_apply_pauli_sum");
+  if (rc) return rc;
+  memcpy(dst->perm, src->perm, sizeof dst->perm);      // written in src's physical layout
+  const uint64_t shard_bytes = (1ull << dst->nloc) * dst->amp_bytes();
+  dst->stats.kernels_launched += batches.empty() ? 1 : batches.size();      // (the fold is not counted, as in qh_axpby)
+  dst->stats.bytes_swept += streams * shard_bytes;
+  dst->stats.bytes_algorithmic += (batches.empty() ? 1 : 2) * shard_bytes;
+  return QH_OK;
+}
+
+int qh_pauli_sum_new(qh_handle src, uint64_t nterms, const double *coeffs, const uint64_t *xmask, const uint64_t *zmask,
+                     double *norm2, qh_handle *out) {
+  if (!src || !out) return fail(QH_ERR_ARG, "pauli_sum_new: null handle or out");
+  if (src->dry) return fail(QH_ERR_ARG, "pauli_sum_new: not on a dry (planner-only) handle");
+  int rc = check_pauli_arrays("pauli_sum_new", nterms, coeffs, xmask, zmask);
+  if (rc) return rc;
+  std::vector<qh_pauli_term> terms;
+  if ((rc = plan_pauli(src, "pauli_sum_new", nterms, xmask, zmask, &terms))) return rc;      // refused before anything is made
+  if ((rc = use_device(src))) return rc;
+  qh_state_s *h = nullptr;
+  if ((rc = make_sibling(src, src->nloc, src->nglob, "pauli_sum_new", &h))) return rc;
+  if ((rc = qh_apply_pauli_sum(h, src, nterms, coeffs, xmask, zmask, norm2))) return drop_sibling(h, rc);
+  *out = h;
   return QH_OK;
 }
 

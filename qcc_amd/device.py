@@ -499,6 +499,44 @@ class DeviceState:
                                    ctypes.byref(out) if norm else None))
     return out.value if norm else None
 
+  # -- Pauli-sum operators ------------------------------------------------------
+  @staticmethod
+  def _pauli_arrays(coeffs, xmasks, zmasks):
+    c = np.ascontiguousarray([complex(v) for v in coeffs], dtype=np.complex128)
+    x = np.ascontiguousarray([int(v) for v in xmasks], dtype=np.uint64)
+    z = np.ascontiguousarray([int(v) for v in zmasks], dtype=np.uint64)
+    if not c.size == x.size == z.size:
+      raise ValueError(f'apply_pauli_sum: {c.size} coefficients, {x.size} x masks, {z.size} z masks')
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    return (c, x, z), c.view(np.float64).ctypes.data_as(_dp), x.ctypes.data_as(u64p), z.ctypes.data_as(u64p)
+
+  def apply_pauli_sum(self, coeffs, xmasks, zmasks, out=None, norm=False):
+    """(sum_t c_t P_t) self as a state of its own (qh_apply_pauli_sum): complex coefficients and Pauli strings as LOGICAL
+    bit masks (x: X or Y on the bit, z: Z or Y), as in expect_pauli.  This state is read only (queued gates run first).
+    out=None: a new DeviceState (qh_pauli_sum_new); otherwise the result replaces out's state, which takes this state's
+    bit map, and out is returned.  norm=True returns (state, sum |a|^2 of the result over this shard)."""
+    keep, cp, xp, zp = self._pauli_arrays(coeffs, xmasks, zmasks)
+    n = int(keep[0].size)
+    n2 = ctypes.c_double() if norm else None
+    n2p = ctypes.byref(n2) if norm else None
+    if out is None:
+      out = self._sibling(lambda h: self.lib.qh_pauli_sum_new(self.h, n, cp, xp, zp, n2p, h), 0)
+    else:
+      native.check(self.lib.qh_apply_pauli_sum(out.h, self.h, n, cp, xp, zp, n2p))
+    return (out, n2.value) if norm else out
+
+  def pauli_sum_plan(self, xmasks, zmasks):
+    """How apply_pauli_sum would batch these strings right now (qh_pauli_sum_plan): (terms, batches), lists of dicts."""
+    keep, _cp, xp, zp = self._pauli_arrays([0] * len(xmasks), xmasks, zmasks)
+    n = int(keep[0].size)
+    terms = (native.QhPauliTerm * max(n, 1))()
+    cap = n // native.QH_PAULI_SUM_BATCH + 1
+    batches = (native.QhPauliBatch * cap)()
+    nb = ctypes.c_uint64()
+    native.check(self.lib.qh_pauli_sum_plan(self.h, n, xp, zp, terms, batches, cap, ctypes.byref(nb)))
+    tl = [{k: int(getattr(terms[j], k)) for k, _ in native.QhPauliTerm._fields_} for j in range(n)]
+    return tl, [batches[b].as_dict() for b in range(nb.value)]
+
   def inner_plan(self, other):
     """How inner(other) would walk the two states right now (qh_inner_plan), as a dict."""
     t = native.QhInnerTiles()

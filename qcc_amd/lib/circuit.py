@@ -1137,6 +1137,93 @@ class qc:
         total = complex(np.dot(c, vals)) if len(coeffs) else 0j
         return total if np.any(c.imag != 0) else float(total.real)
 
+    # Pauli-sum operators (extensions; the reference applies an operator as a dense matrix, ops.Operator.__call__).  With a
+    # device that cannot apply_pauli_sum (and in aliased mode) the same formula runs over qc.psi on the host.
+    def _pauli_terms(self, terms, what):
+        coeffs, xs, zs = [], [], []
+        for term in terms:
+            try:
+                c, paulis = term
+            except (TypeError, ValueError):
+                raise ValueError(f'{what}: term {term!r} is not a (coefficient, paulis) pair') from None
+            x, z = self._pauli_masks(paulis)
+            coeffs.append(complex(c))
+            xs.append(x)
+            zs.append(z)
+        return coeffs, xs, zs
+
+    def _pauli_sum_host(self, coeffs, xs, zs):
+        """H|psi> from qc.psi: complex128 sums, rounded once to the state's width."""
+        amps = np.asarray(self.psi).reshape(-1)
+        a = amps.astype(np.complex128)
+        idx = np.arange(a.size, dtype=np.uint64)
+        out = np.zeros(a.size, dtype=np.complex128)
+        for c, x, z in zip(coeffs, xs, zs):
+            par = np.zeros(a.size, dtype=np.uint64)
+            for b in range(self._nbits):
+                if (z >> b) & 1:
+                    par ^= (idx >> np.uint64(b)) & np.uint64(1)
+            out += (c * (-1j) ** (bin(x & z).count('1') % 4)) * (1.0 - 2.0 * par.astype(np.float64)) * a[idx ^ np.uint64(x)]
+        return out.astype(amps.dtype)
+
+    def _pauli_on_device(self, dev):
+        return hasattr(dev, 'apply_pauli_sum') and not self._alias
+
+    def apply_hamiltonian(self, terms, *, normalize=False):
+        """self := H self for H = sum_t c_t P_t, terms = [(c_t, paulis_t), ...] as in expectation(), on the device
+        (qh_pauli_sum_new: the result is a device state of its own that takes this circuit's place).  Gates queued run
+        first.  Returns the norm^2 of the result, before any normalisation; normalize=True follows with
+        scale(1 / sqrt(norm^2)) and raises ValueError where the result is 0 (the state is then that result).  Not recorded
+        in the IR, like combine."""
+        coeffs, xs, zs = self._pauli_terms(terms, 'apply_hamiltonian')
+        dev = self._ensure_device()
+        if self._pauli_on_device(dev):
+            new, norm2 = dev.apply_pauli_sum(coeffs, xs, zs, norm=True)
+            norm2 = float(norm2)
+            self._dev = new
+            backend.release_device_state(dev)
+            self._host, self._host_ok = None, False
+            self._factors = []
+            self._product_flag = False
+            if normalize:
+                if not norm2 > 0:
+                    raise ValueError('apply_hamiltonian: the result is 0, nothing to normalise')
+                new.scale(1.0 / math.sqrt(norm2))
+                self._gate_done()
+            return norm2
+        new = self._pauli_sum_host(coeffs, xs, zs)
+        norm2 = float(np.vdot(new.astype(np.complex128), new.astype(np.complex128)).real)      # of the values as stored
+        if normalize and not norm2 > 0:
+            self.psi = new
+            raise ValueError('apply_hamiltonian: the result is 0, nothing to normalise')
+        self.psi = new / math.sqrt(norm2) if normalize else new
+        return norm2
+
+    def hamiltonian_times(self, terms):
+        """A Snapshot holding H|self> (terms as in apply_hamiltonian); this circuit's state is unchanged.  For overlap,
+        combine, project_out and restore: a Krylov step, a residual, a variance."""
+        coeffs, xs, zs = self._pauli_terms(terms, 'hamiltonian_times')
+        dev = self._ensure_device()
+        if self._pauli_on_device(dev):
+            return Snapshot(self._nbits, self._width(), dev=dev.apply_pauli_sum(coeffs, xs, zs))
+        return Snapshot(self._nbits, self._width(), host=self._pauli_sum_host(coeffs, xs, zs))
+
+    def variance(self, terms):
+        """<H^2> - <H>^2 = norm2(H psi) - expectation(terms)^2 for real coefficients (ValueError otherwise).  Not divided
+        by the norm: exact for a normalised state."""
+        terms = list(terms)
+        coeffs, xs, zs = self._pauli_terms(terms, 'variance')
+        if any(c.imag != 0 for c in coeffs):
+            raise ValueError('variance: real coefficients only (H must be Hermitian)')
+        dev = self._ensure_device()
+        if self._pauli_on_device(dev):
+            w, norm2 = dev.apply_pauli_sum(coeffs, xs, zs, norm=True)
+            w.close()
+        else:
+            new = self._pauli_sum_host(coeffs, xs, zs).astype(np.complex128)
+            norm2 = float(np.vdot(new, new).real)
+        return float(norm2) - float(self.expectation(terms)) ** 2
+
     # Two states (extensions; the reference compares states on the host: State.diff, the swap and Hadamard tests).  With a
     # device that cannot clone / copy_from / inner, the amplitudes go through qc.psi on the host instead.
     def snapshot(self):

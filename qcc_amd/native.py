@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB_PATH = os.environ.get('QCC_HIP_LIB') or os.path.join(PKG, 'libqcc_hip.so')  # env: A/B builds only
 SOURCES = [os.path.join(PKG, 'csrc', f) for f in
-           ('engine.hip', 'buffers.hip.h', 'kernels_common.hip.h', 'kernels_gate.hip.h', 'kernels_argmax.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_perm.hip.h', 'perm_plan.h', 'kernels_measure.hip.h', 'kernels_select.hip.h', 'select_plan.h', 'kernels_expect.hip.h', 'kernels_two_state.hip.h', 'kernels_inner.hip.h', 'kernels_axpby.hip.h', 'inner_plan.h', 'kernels_resize.hip.h', 'resize_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h', 'exchange_plan.h',
+           ('engine.hip', 'buffers.hip.h', 'kernels_common.hip.h', 'kernels_gate.hip.h', 'kernels_argmax.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_perm.hip.h', 'perm_plan.h', 'kernels_measure.hip.h', 'kernels_select.hip.h', 'select_plan.h', 'kernels_expect.hip.h', 'kernels_pauli.hip.h', 'pauli_plan.h', 'kernels_two_state.hip.h', 'kernels_inner.hip.h', 'kernels_axpby.hip.h', 'inner_plan.h', 'kernels_resize.hip.h', 'resize_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h', 'exchange_plan.h',
             'sweep_island_rb2.inc', 'sweep_island_rb3.inc', 'sweep_island_rb4.inc',
             'sweep_island_rb5.inc', 'sweep_island_f32_rb2.inc', 'sweep_island_f32_rb3.inc',
             'sweep_island_f32_rb4.inc', 'sweep_island_f32_rb5.inc', 'sweep_island_f32_rb6.inc', 'sweep_handlers.inc',
@@ -73,6 +73,22 @@ class QhEntry(ctypes.Structure):
   _fields_ = [('index', _u64), ('re', ctypes.c_double), ('im', ctypes.c_double)]
 
 
+QH_PAULI_SUM_BATCH = 16
+
+
+class QhPauliTerm(ctypes.Structure):
+  """include/qcc_hip.h qh_pauli_term: one term of qh_pauli_sum_plan, in sorted order."""
+  _fields_ = [('index', _u64), ('px', _u64), ('pz', _u64), ('neg', ctypes.c_uint32), ('ny', ctypes.c_uint32)]
+
+
+class QhPauliBatch(ctypes.Structure):
+  """include/qcc_hip.h qh_pauli_batch: one kernel of qh_apply_pauli_sum."""
+  _fields_ = [('first', _u64), ('count', _u64), ('ngroups', _u64), ('streams', _u64)]
+
+  def as_dict(self):
+    return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 # name -> (restype, argtypes); every symbol declared in include/qcc_hip.h
 SIGNATURES = {
     'qh_last_error': (ctypes.c_char_p, []),
@@ -130,6 +146,10 @@ SIGNATURES = {
     'qh_inner': (_i32, [_vp, _vp, _dp]),
     'qh_inner_plan': (_i32, [_vp, _vp, ctypes.POINTER(QhInnerTiles)]),
     'qh_axpby': (_i32, [_vp, _dp, _vp, _dp, _dp]),
+    'qh_apply_pauli_sum': (_i32, [_vp, _vp, _u64, _dp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _dp]),
+    'qh_pauli_sum_new': (_i32, [_vp, _u64, _dp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _dp, ctypes.POINTER(_vp)]),
+    'qh_pauli_sum_plan': (_i32, [_vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(QhPauliTerm),
+                                 ctypes.POINTER(QhPauliBatch), _u64, ctypes.POINTER(_u64)]),
     'qh_extend': (_i32, [_vp, _i32, _dp, _u64, ctypes.POINTER(_vp)]),
     'qh_release': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _u64, _dp, ctypes.POINTER(_vp)]),
     'qh_get_stats': (_i32, [_vp, ctypes.POINTER(QhStats)]),
