@@ -16,14 +16,15 @@ two logical bits whose positions are exchanged, the runner looks the positions u
 References are imported, not copied: tests/oracle_lib (gates), fake_device.np_marginal / np_keep, resize_util.np_extend /
 np_release, select_util.np_select / np_topk / fma_probs, test_dense_cpu.dense_reference, test_mux_cpu.mux_reference_fast /
 diag_reference, test_expect_cpu.np_expect, test_perm_cpu.perm_reference (and the tile rule of qh_perm_plan it states),
-shard_util.check_exact_cdf (the inverse CDF of qh_sample in physical order)."""
+pauli_util.np_pauli_sum and pauli_util.bound (qh_apply_pauli_sum and its derived error bound), shard_util.check_exact_cdf
+(the inverse CDF of qh_sample in physical order)."""
 import os
 import sys
 
 import numpy as np
 
 from qcc_amd import native
-from tests import oracle_lib, shard_util
+from tests import oracle_lib, pauli_util, shard_util
 from tests.fake_device import np_keep, np_marginal
 from tests.resize_util import np_extend, np_release
 from tests.select_util import fma_probs, np_select, np_topk
@@ -46,15 +47,17 @@ BARRIERS = ('matrix', 'mux', 'diag', 'perm', 'scale', 'project_bit', 'project_bi
 READERS = ('norm2', 'prob_bit', 'marginal', 'sample', 'expect', 'argmax', 'amplitude', 'amplitudes', 'select', 'topk')
 HANDLE_STEPS = ('clone', 'copy', 'extend', 'release', 'close')
 TWO_STATE = ('inner', 'axpby')
+OPERATOR_STEPS = ('pauli_sum',)     # reads one handle and replaces another whole (or makes a new one)
 LAYOUT_STEPS = ('flush', 'set_relayout', 'remap')
-KINDS = ('gates',) + BARRIERS + READERS + HANDLE_STEPS + TWO_STATE + LAYOUT_STEPS + ('refused',)
+KINDS = ('gates',) + BARRIERS + READERS + HANDLE_STEPS + TWO_STATE + OPERATOR_STEPS + LAYOUT_STEPS + ('refused',)
 
 
 # the fixed programs of the suite (tests/test_program_fuzz_cpu.py on NumpyDevice, tests/test_gpu_program_fuzz.py on the GPU),
 # each at both widths; the coverage table of the CPU test is what this seed list was chosen by
-# (re-chosen when 'perm' became a kind: one stream draws the kinds, so a new kind changes every program of every seed)
-FIXED = [('own', seed) for seed in list(range(21)) + [42, 48, 60, 88, 92, 139]] + [('shard', seed) for seed in list(range(6)) + [15, 34, 54]] + \
-        [('attached', seed) for seed in list(range(4)) + [7]] + [('mapped', seed) for seed in range(4)]
+# (re-chosen when 'perm' and then 'pauli_sum' became kinds: one stream draws the kinds, so a new kind changes every program of
+# every seed; no seed has left the list)
+FIXED = [('own', seed) for seed in list(range(21)) + [42, 48, 60, 88, 92, 139]] + [('shard', seed) for seed in list(range(6)) + [15, 22, 24, 34, 54]] + \
+        [('attached', seed) for seed in list(range(4)) + [5, 7, 11]] + [('mapped', seed) for seed in list(range(4)) + [15, 42]]
 # planner variants of tests/test_gpu_fuzz.py, each on 'own' programs whose first handle is large enough for sweeps
 ENV_VARIANTS = [{'QH_RELAYOUT': '0'}, {'QH_WAVE_BITS': '2', 'QH_LANE_VALU': '2'}, {'QH_SEATS': '2', 'QH_WAVE_BITS': '1'}]
 
@@ -97,6 +100,67 @@ def perm_tiles(nloc, bw, bm, shard, bits, ctl_mask):
   path = native.QH_PERM_LDS if ((16 if bw == 128 else 8) << tile_bits) <= LDS_BUDGET else native.QH_PERM_GATHER
   held = sum(1 << (bm[b] - nloc) for b in range(len(bm)) if (ctl_mask >> b) & 1 and bm[b] >= nloc)
   return {'path': path, 'tile_bits': tile_bits, 'ctl_met': int((shard & held) == held), 'k': len(bits), 'reg_pos': reg_pos}
+
+
+# ---- Pauli-sum operators: what qh_pauli_sum_plan must say of a bit map (plan_pauli / pauli_cut of the engine) ---------------------
+PAULI_BATCH = native.QH_PAULI_SUM_BATCH
+PAULI_FEW = 4                 # kPauliSmallT of pauli_plan.h: a batch of up to 4 terms takes the instantiation with 4 term slots
+PAULI_CHUNK_BITS = 11         # kPauliChunkBits: the main shape needs nloc - amp_bits >= 11, smaller states take k_pauli_small
+
+
+def _popcount(v):
+  return bin(int(v)).count('1')
+
+
+def pauli_main_shape(nloc, bw):
+  return nloc - (0 if bw == 128 else 1) >= PAULI_CHUNK_BITS
+
+
+def pauli_plan_rule(nloc, bm, shard, xmasks, zmasks):
+  """(terms, batches) of qh_pauli_sum_plan from a bit map, as include/qcc_hip.h states it: px / pz are the logical masks
+  mapped through the map and cut to the local bits, neg is the parity of shard & the held z bits, ny = popcount(x & z) & 3;
+  the terms are stably sorted by px and cut every 16; a batch counts its distinct x masks and asks for that many + 1 streams,
+  + 1 more behind the first batch"""
+  def local(mask):
+    return sum(1 << bm[b] for b in range(len(bm)) if (mask >> b) & 1 and bm[b] < nloc)
+  def held(mask):
+    return sum(1 << (bm[b] - nloc) for b in range(len(bm)) if (mask >> b) & 1 and bm[b] >= nloc)
+  terms = [{'index': t, 'px': local(x), 'pz': local(z), 'neg': _popcount(shard & held(z)) & 1, 'ny': _popcount(int(x) & int(z)) & 3}
+           for t, (x, z) in enumerate(zip(xmasks, zmasks))]
+  terms.sort(key=lambda t: t['px'])                         # (list.sort is stable)
+  batches = []
+  for first in range(0, len(terms), PAULI_BATCH):
+    part = terms[first:first + PAULI_BATCH]
+    groups = 1 + sum(part[k]['px'] != part[k - 1]['px'] for k in range(1, len(part)))
+    batches.append({'first': first, 'count': len(part), 'ngroups': groups, 'streams': groups + 1 + (first > 0)})
+  return terms, batches
+
+
+def pauli_coef(c, ny, neg):
+  """c' = c (-i)^ny (shard sign), by swaps and negations only (pauli_coef of pauli_plan.h)"""
+  re, im = complex(c).real, complex(c).imag
+  for _ in range(ny & 3):
+    re, im = im, -re
+  return complex(-re, -im) if neg else complex(re, im)
+
+
+def pauli_unit(c):
+  """k with c == i^k exactly, or None"""
+  return {(1.0, 0.0): 0, (0.0, 1.0): 1, (-1.0, 0.0): 2, (0.0, -1.0): 3}.get((complex(c).real, complex(c).imag))
+
+
+def pauli_rotated(vec, n, x, z, k):
+  """i^k (-1)^popcount(i & z) vec[i ^ x] by negations and swaps of the stored components alone: the bits a batch of one unit
+  term stores (k = 0 and z = 0: the source's bits; a zero that is negated becomes a negative zero)"""
+  idx = np.arange(1 << n, dtype=np.uint64)
+  p = np.asarray(vec, dtype=np.complex128)[(idx ^ np.uint64(x)).astype(np.int64)]
+  re, im = p.real.copy(), p.imag.copy()
+  if k & 1:
+    re, im = -im, re
+  neg = (pauli_util.parity(idx, z) == 1) ^ bool(k & 2)
+  out = np.empty(1 << n, dtype=np.complex128)
+  out.real, out.imag = np.where(neg, -re, re), np.where(neg, -im, im)
+  return out
 
 
 TOL = 1e-12                   # TOL of tests/test_gpu_inner.py: readers that accumulate in double from the stored amplitudes
@@ -393,6 +457,22 @@ class ModelState:
     self.put(h, axpby_ref(self.wide(h), s['alpha'], self.wide(s['other']), s['beta']))
     return self.norm(h)
 
+  def _pauli_sum(self, s):
+    """h is the SOURCE; the result goes into the existing handle `dst` (whose queue is dropped, never run, and whose relayout
+    mode stays) or into the new slot `new`.  x masks are local, so partners stay on the shard and the vector of the global
+    size needs nothing more: a held z bit is the plain sign of the global index."""
+    src = s['h']
+    self.run(src)
+    out = pauli_util.np_pauli_sum(self.wide(src), s['coeffs'], s['x'], s['z'])
+    if s['dst'] is None:
+      d = s['new']
+      self.put(d, out, self.n[src], self.held[src])
+    else:
+      d = s['dst']
+      self.drop(d)
+      self.put(d, out)
+    return self.norm(d)
+
   # -- layout -------------------------------------------------------------------------------------------------------------------
   def _flush(self, s):
     self.run(s['h'])
@@ -466,7 +546,7 @@ class _Gen:
     out = self.m.step(s)
     if s['op'] in ('gates', 'close', 'refused', 'init') or s.get('poison'):
       return out
-    for h in [x for x in (s.get('new'), s.get('h')) if x is not None and x in self.m.v]:
+    for h in [x for x in (s.get('new'), s.get('dst'), s.get('h')) if x is not None and x in self.m.v]:
       nv = self.m.norm(h)
       if self.m.q[h] == 0 and np.isfinite(nv) and nv > 0 and not 0.25 <= nv <= 4:      # norm control
         z = {'op': 'scale', 'h': h, 'z': complex(1 / np.sqrt(nv))}
@@ -882,6 +962,63 @@ class _Gen:
       self.emit({'op': 'copy', 'h': h, 'src': o})
     return True
 
+  def k_pauli_sum(self):
+    """dst := (sum_t c_t P_t) src into a new slot or into a partner of src in whatever condition the program left it"""
+    rng, m = self.rng, self.m
+    src = self.pick(self.usable)
+    if src is None:
+      return False
+    dst = None
+    if not self.room() or rng.random() < 0.5:
+      c = sorted((x for x in self.live() if x != src and m.n[x] == m.n[src] and m.held[x] == m.held[src]), key=lambda x: -m.q[x])
+      if not c:
+        return False
+      dst = c[0] if m.q[c[0]] and rng.random() < 0.7 else c[int(rng.integers(len(c)))]      # prefer a destination with gates queued
+    n, loc, held = m.n[src], m.local_bits(src), m.held[src]
+    lo, hi = ((0, 0), (1, 1), (2, 4), (5, 16), (17, 40))[int(rng.choice(5, p=[0.08, 0.27, 0.2, 0.2, 0.25]))]
+    nt = int(rng.integers(lo, hi + 1))
+    def xmask():                                             # local bits only, of any weight from 0 to all of them
+      return sum(1 << int(b) for b in rng.choice(loc, size=int(rng.integers(0, len(loc) + 1)), replace=False))
+    shape = int(rng.integers(3))
+    if shape == 0:
+      x = [xmask()] * nt                                     # one shared mask
+    elif shape == 1:                                         # 2-3 masks in runs, given unsorted
+      pool = [xmask() for _ in range(int(rng.integers(2, 4)))]
+      x = [pool[(int(k) * len(pool)) // nt] for k in rng.permutation(nt)]
+    else:
+      x = [xmask() for _ in range(nt)]                       # all drawn apart
+    z = [int(rng.integers(1 << n)) if rng.random() < 0.8 else 0 for _ in range(nt)]      # all global bits, held ones included
+    kind = int(rng.choice(3, p=[0.6, 0.2, 0.2] if nt == 1 else [0.2, 0.3, 0.5]))
+    if kind == 0:
+      coeffs = [(1, -1, 1j, -1j)[int(k)] for k in rng.integers(4, size=nt)]      # one term: the exact paths
+      if nt == 1 and rng.random() < 0.4:                     # the c that makes c' = c (-i)^nY (shard sign) == 1: the source's bits
+        neg = sum(v for b, v in held.items() if (z[0] >> b) & 1) & 1
+        coeffs = [c for c in (1, -1, 1j, -1j) if pauli_coef(c, _popcount(x[0] & z[0]), neg) == 1]
+    elif kind == 1:
+      coeffs = [float(v) for v in rng.uniform(-1, 1, nt)]
+    else:
+      coeffs = [complex(a, b) for a, b in rng.uniform(-1, 1, (nt, 2))]
+    coeffs = np.asarray(coeffs, dtype=np.complex128).reshape(nt)
+    csum = float(np.sum(np.abs(coeffs)))
+    if csum > 4:
+      coeffs = coeffs * (4 / csum)                           # C = sum |c_t| <= 4
+    self.unalign(src if dst is None else dst, None if dst is None else src)      # (a remap relabels: the trial comes after it)
+    if nt:
+      trial = pauli_util.np_pauli_sum(m.wide(src), coeffs, x, z)
+      if not 1e-3 <= float(np.vdot(trial, trial).real) <= 100:
+        return False
+    s = {'op': 'pauli_sum', 'h': src, 'dst': dst, 'coeffs': coeffs, 'x': x, 'z': z, 'poisoned': False}
+    if dst is None:
+      s['new'] = self.new_slot()
+    else:
+      if rng.random() < (0.15 if m.q[dst] else 0.35):        # the header: batch 0 does not read dst
+        self.emit({'op': 'scale', 'h': dst, 'z': complex(np.nan, 0), 'poison': True})
+        s['poisoned'] = True
+    self.emit(s)
+    if nt == 0:                                              # a state of zeros: give it content again
+      self.emit({'op': 'copy', 'h': s['new'] if dst is None else dst, 'src': src})
+    return True
+
   def k_flush(self):
     h = self.pick(lambda x: self.m.q[x] > 0) or self.pick()
     self.emit({'op': 'flush', 'h': h})
@@ -911,20 +1048,28 @@ class _Gen:
       return False
     loc = m.local_bits(h)
     whats = ['matrix_twice', 'mux_target_selected', 'marginal_twice', 'sample_descending', 'copy_self', 'axpby_self',
-             'extend_basis', 'release_value', 'perm_not_bijection', 'perm_control_in_register']
+             'extend_basis', 'release_value', 'perm_not_bijection', 'perm_control_in_register', 'pauli_sum_self', 'pauli_sum_bad_qubit']
     if m.held[h]:
       whats.append('perm_register_held')                     # (a register bit on the shard index: nothing is flushed)
+      whats.append('pauli_sum_x_held')                       # (an x bit there: nothing runs, no handle comes into being)
     what = whats[int(rng.integers(len(whats)))]
     code = native.QH_ERR_SAME_QUBIT if what in ('matrix_twice', 'mux_target_selected', 'marginal_twice', 'perm_control_in_register') \
-        else native.QH_ERR_NONLOCAL if what == 'perm_register_held' else native.QH_ERR_ARG
+        else native.QH_ERR_NONLOCAL if what in ('perm_register_held', 'pauli_sum_x_held') \
+        else native.QH_ERR_BAD_QUBIT if what == 'pauli_sum_bad_qubit' else native.QH_ERR_ARG
     s = {'op': 'refused', 'h': h, 'what': what, 'code': code, 'bits': [int(loc[0]), int(loc[1])]}
-    if what == 'perm_register_held':
+    if what in ('perm_register_held', 'pauli_sum_x_held'):
       s['held'] = int(sorted(m.held[h])[int(rng.integers(len(m.held[h])))])
+    if what.startswith('pauli_sum_'):
+      s['nbits'] = m.n[h]
+      o = self.partner(h) if what != 'pauli_sum_self' else None
+      if o is not None:
+        s['other'] = o                                       # also through an existing destination, which stays as it is
     self.refused += 1
     self.emit(s)
     return True
 
-  WEIGHTS = {'gates': 9.0, 'close': 0.6, 'refused': 0.8, 'remap': 1.6, 'flush': 0.7, 'clone': 1.3, 'inner': 1.8, 'axpby': 1.8, 'copy': 1.3}
+  WEIGHTS = {'gates': 9.0, 'close': 0.6, 'refused': 0.8, 'remap': 1.6, 'flush': 0.7, 'clone': 1.3, 'inner': 1.8, 'axpby': 1.8, 'copy': 1.3,
+             'pauli_sum': 2.5}
 
   def run(self):
     self.start()
@@ -950,14 +1095,16 @@ def describe(s):
   """a step as a short JSON-able dict (tables and matrices by shape)"""
   out = {}
   for k, v in s.items():
-    if isinstance(v, np.ndarray):
+    if isinstance(v, np.ndarray) and np.iscomplexobj(v) and v.ndim == 1 and v.size <= 40:
+      out[k] = [[float(c.real), float(c.imag)] for c in v]   # (the coefficients of a Pauli sum: enough to replay the step)
+    elif isinstance(v, np.ndarray):
       out[k] = v.tolist() if v.size <= 8 else f'<{v.dtype} {list(v.shape)}>'
     elif k == 'gates' and s['op'] == 'gates':
       out[k] = f'<{len(v)} gates>'
     elif k == 'factors':
       out[k] = [(n, x if isinstance(x, int) else f'<table {len(x)}>') for n, x in v]
     elif isinstance(v, complex):
-      out[k] = [v.real, v.imag]
+      out[k] = ['nan' if np.isnan(x) else x for x in (v.real, v.imag)]      # (a poison step: NaN does not equal itself)
     else:
       out[k] = v
   return out
@@ -977,7 +1124,8 @@ class Check:
   def __init__(self, bw):
     self.bw = bw
     # (index, op, local bits out of canonical order, a queued burst ran in the step, inner path or None, the record of a
-    # 'perm' step or None: what qh_perm_plan said of the layout the call worked on, and what kind of handle it was)
+    # 'perm' step or None: what qh_perm_plan said of the layout the call worked on, and what kind of handle it was; for a
+    # 'pauli_sum' step the record of _Runner.run_pauli_sum: what qh_pauli_sum_plan said, and what src and dst were)
     self.events = []
     self.relaid = 0             # barrier / reader steps whose own flush re-laid the handle out
     self.chain_err = self.chain_d = self.chain_tol = None
@@ -1210,18 +1358,26 @@ class _Runner:
         'perm_not_bijection': lambda: st.apply_perm([0, 1, 1, 3], [a, b]),
         'perm_control_in_register': lambda: st.apply_perm([0, 1, 2, 3], [a, b], 1 << b),
         'perm_register_held': lambda: st.apply_perm([0, 1, 2, 3], [a, s.get('held')]),
+        'pauli_sum_self': lambda out: st.apply_pauli_sum([1.0], [1 << a], [1 << b], out=st),
+        'pauli_sum_bad_qubit': lambda out: st.apply_pauli_sum([1.0, 0.5], [1 << a, 0], [0, 1 << s.get('nbits', 0)], out=out),
+        'pauli_sum_x_held': lambda out: st.apply_pauli_sum([0.5, 1.0], [1 << a, (1 << s.get('held', 0)) | (1 << b)], [0, 0], out=out),
     }
-    try:
-      calls[s['what']]()
-    except native.QhError as e:
-      self.need(e.code == s['code'], f'error code {e.code}, expected {s["code"]}')
-      return
-    self.fail('the call was not refused')
+    # a refused Pauli sum: into a new handle (none may come into being) and, where the pool has one, into an existing one
+    outs = [None] + ([self.dev[s['other']]] if s.get('other') is not None else []) if s['what'].startswith('pauli_sum_') else [()]
+    for out in outs:
+      try:
+        made = calls[s['what']](*(() if out == () else (out,)))
+      except native.QhError as e:
+        self.need(e.code == s['code'], f'error code {e.code}, expected {s["code"]}')
+        continue
+      if s['what'].startswith('pauli_sum_') and made is not None and made is not out and hasattr(made, 'close'):
+        made.close()                                         # (the handle that should not exist)
+      self.fail('the call was not refused')
 
   # -- one step ------------------------------------------------------------------------------------------------------------------
   def run_step(self, s):
     op, h, bw, m = s['op'], s['h'], self.bw, self.m
-    involved = [x for x in (h, s.get('other'), s.get('src')) if x is not None]
+    involved = [x for x in (h, s.get('other'), s.get('src'), s.get('dst')) if x is not None]
     involved = list(dict.fromkeys(involved))
     for x in involved:
       self.need(_pending(self.dev[x]) == m.q[x], f'handle {x}: {_pending(self.dev[x])} gates pending before the step, expected {m.q[x]}')
@@ -1238,17 +1394,21 @@ class _Runner:
       self.check.events.append((self.i, op, not _canonical(bm_before[h], self.dev[h].nbits), False, None, None))
       return
     if op == 'refused':
-      k0 = self.kernels(h)
+      k0 = {x: self.kernels(x) for x in involved}
       self.refused(s)
-      self.need(_pending(self.dev[h]) == q_before[h] and _bitmap(self.dev[h]) == bm_before[h] and self.kernels(h) == k0,
-                'a refused call changed the queue, the bit map or launched a kernel')
-      if quiet:
-        self.need(self.read(h).tobytes() == m.wide(h).tobytes(), 'a refused call changed the state')
+      for x in involved:                                     # (the handle, and the destination a refused Pauli sum was given)
+        self.need(_pending(self.dev[x]) == q_before[x] and _bitmap(self.dev[x]) == bm_before[x] and self.kernels(x) == k0[x],
+                  f'handle {x}: a refused call changed the queue, the bit map or launched a kernel')
+        if q_before[x] == 0:
+          self.need(self.read(x).tobytes() == m.wide(x).tobytes(), f'handle {x}: a refused call changed the state')
       self.check.events.append((self.i, op, False, False, None, None))
       return
     for x in involved:                                     # the mode, read without changing it, where a plan exists to show it
       if q_before[x] and self.dev[x].nbits >= SWEEPS_FROM and not m.wanted(x):
         self.need(not _plans_relayout(self.dev[x]), f'handle {x}: the queued burst is planned with relayout sweeps, its relayout mode is off')
+    if op == 'pauli_sum':
+      self.run_pauli_sum(s, q_before, bm_before)
+      return
     k_before = {x: self.kernels(x) for x in involved}
     n0 = {x: self.dev[x].marginal([]).tobytes() for x in involved} if quiet and op in READERS + ('inner',) else {}
     if n0:
@@ -1352,6 +1512,9 @@ class _Runner:
       for x, b in n0.items():
         self.need(self.dev[x].marginal([]).tobytes() == b, f'handle {x}: marginal([]) changed its bits across a reader')
     elif op == 'release':
+      # from what src holds now (release leaves src as it is), as the readers' answers: behind a queued burst the model's own
+      # weights carry the burst's rounding, which _amp_tol allows per amplitude and _close does not allow for a sum
+      _, *want = np_release(after[h], s['bits'], s['value'])
       for name, g_, w_ in (('kept', got[0], want[0]), ('dropped', got[1], want[1])):
         miss = close(g_, w_, bw)                           # _close
         self.need(miss is None, f'release: weight {name} {miss}')
@@ -1387,6 +1550,125 @@ class _Runner:
           self.need(dk[x] == e, f'handle {x}: kernels_launched grew by {dk[x]}, the header says {e}')
     local_perm = not _canonical(bm_after[h], self.dev[h].nbits)
     self.check.events.append((self.i, op, local_perm, bool(q_before[h]), path, perm))
+
+  PAULI_STATS = ('kernels_launched', 'bytes_swept', 'bytes_algorithmic')
+
+  def run_pauli_sum(self, s, q_before, bm_before):
+    """One 'pauli_sum' step: h is the source, the result replaces the handle `dst` or becomes the new handle `new`.  A step
+    is QUIET where the source has nothing queued (what the destination has queued is dropped and runs nothing): then the
+    source, the amplitudes, the plan and norm2 are held exactly.  The destination's stats are held on every step -- the
+    source's flush is not counted there."""
+    m, bw = self.m, self.bw
+    src, dst, new = s['h'], s['dst'], s.get('new')
+    st = self.dev[src]
+    coeffs, xs, zs = s['coeffs'], s['x'], s['z']
+    nt, n = len(xs), m.n[src]
+    quiet = q_before[src] == 0
+    csum = float(np.sum(np.abs(coeffs)))
+    mine = mine_of(n, m.held[src]).astype(np.int64)
+    if s['poisoned']:
+      self.need(bool(np.all(np.isnan(m.wide(dst)[mine]))), 'the destination of this step was to hold NaN')
+    plan0 = st.pauli_sum_plan(xs, zs) if quiet else None    # asked on src right before the call
+    src_stats0 = st.stats()
+    d_stats0 = self.dev[dst].stats() if dst is not None else dict.fromkeys(self.PAULI_STATS, 0)
+    try:
+      out, n2 = st.apply_pauli_sum(coeffs, xs, zs, out=None if dst is None else self.dev[dst], norm=True)
+    except native.QhError as e:
+      self.fail(f'the engine refused a valid step: {e}')
+    d = new if dst is None else dst
+    if dst is None:
+      self.dev[new], self.shard[new] = out, self.shard[src]
+    dv = self.dev[d]
+    self.need(out is dv, 'apply_pauli_sum did not return the destination it was given')
+    terms, batches = st.pauli_sum_plan(xs, zs)              # right behind the call: the layout the call's own flush left
+    bm_src, bm_dst = _bitmap(st), _bitmap(dv)
+    want_n2 = m.step(s)
+    for mdl in (self.chain, self.chain_r):
+      if mdl is not None:
+        mdl.step(s)
+    for x in (src, d):                                      # src's queue ran, dst's was dropped
+      self.need(_pending(self.dev[x]) == 0, f'handle {x}: {_pending(self.dev[x])} gates pending behind a Pauli sum')
+    # -- bit maps: dst takes src's; src's moves only behind a flush whose relayout mode is on --------------------------------
+    self.need(bm_dst == bm_src, f'the destination\'s bit map {bm_dst} is not the source\'s {bm_src}')
+    moved = bm_src != bm_before[src]
+    if quiet:
+      self.need(not moved, 'the source\'s bit map moved in a step that had nothing to flush')
+    elif moved:
+      self.need(m.mode[src] == 1, f'a flush re-laid the source out, its relayout mode is {m.mode[src]}')
+      self.check.relaid += 1
+    for x in (src, d):
+      self.need({b for b, p in enumerate(_bitmap(self.dev[x])) if p >= self.dev[x].nbits} == set(m.held[x]), 'the held bits changed')
+      self.check_ptr(x)
+    # -- the plan, held to the bit map by the rule stated in Python ----------------------------------------------------------------
+    want_plan = pauli_plan_rule(st.nbits, bm_src, self.shard[src], xs, zs)
+    self.need((terms, batches) == want_plan, f'qh_pauli_sum_plan says {(terms, batches)}, the rule on bit map {bm_src} gives {want_plan}')
+    if quiet:
+      self.need(plan0 == (terms, batches), 'the plan asked before a quiet call differs from the plan asked behind it')
+    # -- norm2 twice on a quiet step: the same bits --------------------------------------------------------------------------------
+    calls = 1
+    if quiet:
+      _, again = st.apply_pauli_sum(coeffs, xs, zs, out=dv, norm=True)
+      calls = 2
+      self.need(again == n2, f'norm2 {n2!r}, from the same call repeated {again!r}')
+      self.need(_bitmap(dv) == bm_src and _bitmap(st) == bm_src and _pending(dv) == 0, 'the repeated call moved a bit map or queued something')
+      self.need(st.stats() == src_stats0, 'the source\'s stats changed')
+    # -- stats of the destination, as the header gives them from the plan ---------------------------------------------------------
+    sb = (1 << st.nbits) * (16 if bw == 128 else 8)
+    grow = {'kernels_launched': max(1, len(batches)), 'bytes_swept': (sum(b['streams'] for b in batches) if batches else 1) * sb,
+            'bytes_algorithmic': (2 if nt else 1) * sb}
+    d_stats = dv.stats()
+    for k in self.PAULI_STATS:
+      self.need(d_stats[k] - d_stats0[k] == calls * grow[k], f'the destination\'s {k} grew by {d_stats[k] - d_stats0[k]}, the header says {calls} x {grow[k]}')
+    if dst is None:                                         # a new handle starts with zeroed stats, which then count this call
+      self.need(all(v == calls * grow.get(k, 0) for k, v in d_stats.items()), f'a new handle whose stats are not those of this call: {d_stats}')
+    # -- amplitudes -------------------------------------------------------------------------------------------------------------------
+    after_src, after_d = self.read(src), self.read(d)
+    w_src = m.wide(src)
+    if quiet:
+      self.need(np.array_equal(after_src, w_src), 'the source\'s amplitudes changed')
+    else:
+      err = float(np.max(np.abs(after_src - w_src)))
+      self.need(err <= amp_tol(bw), f'the source behind its queue: amplitudes off by {err:.3e} (limit {amp_tol(bw):.1e})')      # _amp_tol
+    m.put(src, after_src)
+    want = m.wide(d)                                        # the model's step from what src held
+    amax = float(np.max(np.abs(after_src)))                 # src as stored
+    b = pauli_util.bound(bw, coeffs, amax, len(batches))
+    if not quiet:
+      b += csum * amp_tol(bw)                               # the burst's own error passes through at most C
+    cps = [pauli_coef(coeffs[t['index']], t['ny'], t['neg']) for t in terms]
+    unit = pauli_unit(cps[0]) if nt == 1 else None
+    if nt == 0:
+      self.need(not np.any(after_d), 'no terms: the destination is not all zeros')
+    elif unit is not None and quiet:
+      self.need(np.array_equal(after_d, want), f'one term with c\' = i^{unit}: the amplitudes are not exact (max diff {float(np.max(np.abs(after_d - want))):.3e})')
+      if unit == 0:                                         # the same bytes, the sign of a zero included
+        local = sum(1 << b_ for b_ in m.local_bits(src))
+        exp = np.zeros(1 << n, dtype=np.complex128)
+        exp[mine] = pauli_rotated(w_src, n, xs[0], zs[0] & local, 0)[mine]
+        self.need(after_d.tobytes() == exp.tobytes(), f'one term with c\' = 1: not the source\'s bits '
+                  f'({int(np.sum(np.signbit(after_d.view(np.float64)) != np.signbit(exp.view(np.float64))))} signs differ)')
+    else:
+      err = float(max(np.max(np.abs(after_d.real - want.real)), np.max(np.abs(after_d.imag - want.imag))))
+      self.need(err <= b, f'amplitudes off by {err:.3e} per component (bound {b:.3e}, {len(batches)} batches, C = {csum:.3g})')
+    m.put(d, after_d)
+    self.check_raw(src, after_src, bm_src)
+    self.check_raw(d, after_d, bm_dst)
+    # -- norm2 --------------------------------------------------------------------------------------------------------------------------
+    n2_np = float(np.vdot(after_d, after_d).real)
+    self.need(abs(n2 - n2_np) <= 1e-12 * n2_np, f'norm2 {n2!r}, the amplitudes read back give {n2_np!r}')
+    n2_tol = 4 * csum * amax * b * (1 << st.nbits)          # (as _apply_checked of tests/test_gpu_pauli_sum.py)
+    self.need(abs(n2 - want_n2) <= n2_tol, f'norm2 {n2!r}, the model gives {want_n2!r} (tolerance {n2_tol:.3e})')
+    # -- the record ---------------------------------------------------------------------------------------------------------------------
+    ab = 0 if bw == 128 else 1
+    rec = {'nloc': st.nbits, 'main': pauli_main_shape(st.nbits, bw), 'nbatches': len(batches), 'zero': nt == 0, 'unit': unit,
+           'classes': [('few' if bt['count'] <= PAULI_FEW else 'many', 'one' if bt['ngroups'] == 1 else 'several') for bt in batches],
+           'changed': unit is not None and cps[0] != complex(coeffs[0]),
+           'shard': bool(m.held[src]), 'held_z': any((z >> hb) & 1 for z in zs for hb in m.held[src]), 'neg': any(t['neg'] for t in terms),
+           'new': dst is None, 'dst_queued': dst is not None and bool(q_before[dst]), 'poisoned': bool(s['poisoned']),
+           'dst_fixed': d in self.fixed_ptr, 'queued': not quiet, 'relayout_on': m.mode[src] == 1,
+           'relaid': not quiet and moved and not _canonical(bm_src, st.nbits),
+           'px0': bool(ab) and any(t['px'] & 1 for t in terms), 'pz0': bool(ab) and any(t['pz'] & 1 for t in terms)}
+    self.check.events.append((self.i, 'pauli_sum', not _canonical(bm_src, st.nbits), not quiet, None, rec))
 
   def perm_record(self, s, queued, bm_before):
     """What qh_perm_plan says of the step's bits right behind the call: the call does not move the bit map, so this is the
@@ -1543,6 +1825,7 @@ class NumpyDevice:
     self.kind = kind
     self.relayout = -1                                     # undecided: the first fused flush decides (attached / mapped: off)
     self.kernels = self.submitted = self.noop = 0          # (submitted / noop: counted for apply_perm only)
+    self.swept = self.algorithmic = 0                      # (bytes: counted for apply_pauli_sum only)
     NumpyDevice._serial[0] += 1
     self.device_ptr = 0x1000 * NumpyDevice._serial[0]
     self.rng = np.random.default_rng(NumpyDevice._serial[0])
@@ -1581,7 +1864,8 @@ class NumpyDevice:
     return len(self.queue)
 
   def stats(self):
-    return {'kernels_launched': self.kernels, 'gates_submitted': self.submitted, 'gates_noop': self.noop}
+    return {'kernels_launched': self.kernels, 'gates_submitted': self.submitted, 'gates_noop': self.noop,
+            'bytes_swept': self.swept, 'bytes_algorithmic': self.algorithmic}
 
   def host_array(self):
     if not hasattr(self, '_host'):
@@ -1888,3 +2172,83 @@ class NumpyDevice:
 
   def _axpby(self, d, alpha, s, beta):
     return axpby_ref(d, alpha, s, beta)
+
+  # -- Pauli-sum operators: batch by batch as the header describes them, through hooks a mutant overrides one at a time ----------
+  def _pauli_check(self, who, out, xmasks, zmasks):
+    if out is self:
+      raise native.QhError(native.QH_ERR_ARG, f'{who}: dst == src')
+    if any((x | z) >> self.nbits_global for x, z in zip(xmasks, zmasks)):
+      raise native.QhError(native.QH_ERR_BAD_QUBIT, f'{who}: a mask bit >= nbits_global')
+    if any((x >> b) & 1 for x in xmasks for b in self.held()):
+      raise native.QhError(native.QH_ERR_NONLOCAL, f'{who}: X or Y on a bit held by the shard index')
+
+  def pauli_sum_plan(self, xmasks, zmasks):
+    xs, zs = [int(x) for x in xmasks], [int(z) for z in zmasks]
+    self._pauli_check('pauli_sum_plan', None, xs, zs)
+    return pauli_plan_rule(self.nbits, self.bm, self.shard, xs, zs)
+
+  def apply_pauli_sum(self, coeffs, xmasks, zmasks, out=None, norm=False):
+    cs, xs, zs = [complex(c) for c in coeffs], [int(x) for x in xmasks], [int(z) for z in zmasks]
+    self._pauli_check('apply_pauli_sum', out, xs, zs)
+    self._pauli_enter()
+    terms, batches = self.pauli_sum_plan(xs, zs)
+    if out is None:
+      out = self._sibling(self.nbits, self.nbits_global, self.bm, np.zeros(1 << self.nbits_global))
+    out._pauli_drop_queue()
+    n, src = self.nbits_global, self.to_logical()
+    mine = self._lidx()
+    local = sum(1 << b for b in range(n) if self.bm[b] < self.nbits)
+    old = out.to_logical()                                   # (read by the batches behind the first alone)
+    exact = new = np.zeros(1 << n, dtype=np.complex128)
+    for b, bt in enumerate(batches):
+      tl = terms[bt['first']:bt['first'] + bt['count']]
+      cps = [pauli_coef(cs[t['index']], self._pauli_ny(t), self._pauli_neg(t)) for t in tl]
+      unit = pauli_unit(cps[0]) if len(tl) == 1 and b == 0 else None
+      if unit is not None:                                  # stored as it is, negated and / or with its components swapped
+        part = self._pauli_unit(pauli_rotated(src, n, xs[tl[0]['index']], zs[tl[0]['index']] & local, unit))
+      else:
+        part = np.zeros(1 << n, dtype=np.complex128)
+        for t, c in zip(tl, cps):
+          part += c * pauli_rotated(src, n, xs[t['index']], zs[t['index']] & local, 0)
+      exact = new = out._pauli_accumulate(b, old, part)
+      old = new = self._round(new)                          # rounded once per batch to the handle's width
+    out.bm = self._pauli_bitmap(out)                        # written in src's physical layout: dst takes src's bit map
+    keep = np.zeros(1 << n, dtype=np.complex128)
+    keep[mine] = new[mine]
+    out.store(keep)
+    out.kernels += len(batches) if batches else self._pauli_zero_kernels()
+    sb = (1 << self.nbits) * (16 if self.bit_width == 128 else 8)
+    out.swept += (sum(bt['streams'] for bt in batches) if batches else 1) * sb
+    out.algorithmic += (2 if batches else 1) * sb
+    n2 = self._pauli_norm2(out.phys.astype(np.complex128), exact[mine])
+    return (out, n2) if norm else out
+
+  def _round(self, vec):
+    return vec.astype(self.dtype).astype(np.complex128)
+
+  def _pauli_enter(self):
+    self.flush()                                             # what src has queued runs first
+
+  def _pauli_drop_queue(self):
+    self.queue = []                                          # dst is replaced whole: what it has queued is dropped
+
+  def _pauli_ny(self, term):
+    return term['ny']
+
+  def _pauli_neg(self, term):
+    return term['neg']
+
+  def _pauli_unit(self, part):
+    return part
+
+  def _pauli_accumulate(self, b, old, part):
+    return part if b == 0 else old + part                   # the first batch does not read dst
+
+  def _pauli_bitmap(self, out):
+    return list(self.bm)
+
+  def _pauli_zero_kernels(self):
+    return 1
+
+  def _pauli_norm2(self, stored, unrounded):
+    return float(np.vdot(stored, stored).real)

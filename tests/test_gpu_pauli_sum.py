@@ -405,6 +405,106 @@ def test_shard_handles(bw):
       assert err <= b
 
 
+@pytest.mark.parametrize('bw', [128, 64])
+def test_shard_handles_on_the_main_shape(bw):
+  """13 local bits of 15: k_pauli_batch at both widths, with the sign the shard index gives folded into the coefficients.
+  20 terms over three x masks: the first batch holds several x masks, the second accumulates; the z masks span the thread,
+  register-index and chunk parts of the index and both held bits.  Then single terms with c = 1 whose shard sign gives
+  c' = -1 on one shard and +1 on the other (the unit path entered through the shard sign), and a Y string whose nY makes c' a
+  power of i: == NumPy."""
+  nloc, nglob = 13, 15
+  ab = _amp_bits(bw)
+  dt = np.complex128 if bw == 128 else np.complex64
+  full = _random_state(nglob, 72).astype(dt).astype(np.complex128)      # as stored
+  rng = np.random.default_rng(73 + bw)
+  thread, reg, chunk = 1 << (ab + 5), 1 << (ab + 9), 1 << (ab + CHUNK_BITS)      # (logical = physical but for bits 2 and 7)
+  assert chunk < 1 << nloc
+  xpool = [0, (1 << 12) | (1 << 7) | 1, (1 << 10) | (1 << 4) | 2]
+  xs = [xpool[int(k) % 3] for k in rng.permutation(20)]      # given unsorted
+  zs = [int(v) for v in rng.integers(0, 1 << nglob, size=20)]
+  zs[0], zs[1], zs[2], zs[3] = thread | reg | chunk | (3 << nloc), chunk | (1 << nloc), reg | (2 << nloc) | 1, thread | 1
+  coeffs = [complex(a, b) for a, b in rng.normal(size=(20, 2))]
+  ystring = (0b111 << 3, (0b111 << 3) | (2 << nloc))        # nY = 3: (-i)^3 = i
+  singles = [('c = 1, z on held bit 0', [1.0], [(1 << 11) | 5], [(1 << nloc) | chunk | 1]),
+             ('c = 1, z on both held bits', [1.0], [1 << 9], [(3 << nloc) | thread]),
+             ('a Y string with nY = 3', [1.0], [ystring[0]], [ystring[1]]),
+             ('a Y string with nY = 3, c = -i', [-1j], [ystring[0]], [ystring[1]])]
+  for shard in (1, 2):
+    with device.DeviceState(nloc, bw) as s, device.DeviceState(nloc, bw) as d:
+      for st in (s, d):
+        st.set_shard(nglob, shard)
+      s.upload(full[shard << nloc:(shard + 1) << nloc])
+      s.remap_swap(2, 7)                                    # local bits anywhere (this relabels the state: read it back)
+      with s.clone() as c:
+        lo_s, phys_s = _logical_state(c, shard, nglob)
+      held_src = np.zeros(1 << nglob, dtype=np.complex128)    # the global state with this shard's amplitudes only
+      held_src[lo_s] = phys_s
+      amax = float(np.max(np.abs(held_src)))
+      terms, batches = s.pauli_sum_plan(xs, zs)
+      assert len(batches) == 2 and batches[0]['ngroups'] > 1 and batches[1]['count'] == 4
+      assert {t['neg'] for t in terms} == {0, 1}
+      d.upload(np.full(1 << nloc, np.nan + 1j * np.nan))      # batch 0 does not read dst
+      cases = [('20 terms', coeffs, xs, zs)] + singles
+      for what, co, x, z in cases:
+        s.apply_pauli_sum(co, x, z, out=d)
+        assert shard_util.bitmap(d, nglob) == shard_util.bitmap(s, nglob)
+        with d.clone() as c:
+          lo, phys = _logical_state(c, shard, nglob)
+        assert np.all(lo >> nloc == shard)
+        want = pauli_util.np_pauli_sum(held_src, co, x, z)[lo]
+        if len(co) == 1:
+          tm = s.pauli_sum_plan(x, z)[0][0]
+          print(f'shard {shard}, bw = {bw}, {what}: neg = {tm["neg"]}, ny = {tm["ny"]}')
+          assert np.array_equal(phys, want.astype(dt).astype(np.complex128)), (what, shard)
+        else:
+          b = pauli_util.bound(bw, co, amax, len(batches))
+          err = float(max(np.max(np.abs(phys.real - want.real)), np.max(np.abs(phys.imag - want.imag))))
+          print(f'shard {shard}, bw = {bw}, {what}: error {err:.3e} (bound {b:.3e})')
+          assert err <= b
+      negs = [s.pauli_sum_plan(x, z)[0][0]['neg'] for _, _, x, z in singles[:2]]
+      assert negs == ([1, 1] if shard == 1 else [0, 1])      # held bit 0 is 1 on shard 1 alone, held bit 1 on shard 2 alone
+
+
+def test_blocks_that_walk_two_chunks_complex64():
+  """n = 25 at complex64: an item is two amplitudes, so this is the walk of the complex128 case (2^13 chunks over 4096 blocks,
+  every block walks two chunks) in the same 256 MiB per state.  The masks are those of that case moved up by the amplitude bit;
+  x and z both hold amplitude bit 0 as well (the two halves of an item trade places, and the sign differs between them), and a
+  z bit sits on the chunk number's lowest bit, which changes INSIDE a block.  NumPy checks 2^16 random amplitudes and the first
+  and last two chunks."""
+  n = CHUNK_BITS + BLOCK_CAP_BITS + 2
+  cb = CHUNK_BITS + 1                                        # the chunk number's lowest bit, as an amplitude-index bit
+  rng = np.random.default_rng(25)
+  def sumsq(flat):                                           # sum of squares in double, a slice at a time
+    return float(sum(np.dot(part, part) for part in (flat[k:k + (1 << 22)].astype(np.float64) for k in range(0, flat.size, 1 << 22))))
+  host = (rng.random(2 << n, dtype=np.float32) - np.float32(0.5)).view(np.complex64)
+  host *= np.float32(1.0 / np.sqrt(sumsq(host.view(np.float32))))
+  xs = [1 << (n - 1), (1 << cb) | (5 << 1) | 1, (1 << cb) | (5 << 1) | 1, 0]
+  zs = [(1 << cb) | (1 << (cb + 1)), (1 << cb) | 1, (1 << (n - 1)) | (1 << 10), (1 << cb) | (1 << 8) | 1]
+  coeffs = [0.5 - 0.25j, 1.5, -0.75j, 0.3]
+  with device.DeviceState(n, 64) as src:
+    src.upload(host)
+    terms, _ = src.pauli_sum_plan(xs, zs)
+    assert any(t['px'] & 1 for t in terms) and any(t['pz'] & 1 for t in terms) and any((t['pz'] >> cb) & 1 for t in terms)
+    grow, nbatches = _predict(src, xs, zs)
+    new, n2 = src.apply_pauli_sum(coeffs, xs, zs, norm=True)
+    with new:
+      assert {k: new.stats()[k] for k in grow} == grow
+      _, n2b = src.apply_pauli_sum(coeffs, xs, zs, out=new, norm=True)
+      assert n2b == n2
+      got = new.download()
+  edge = 2 << cb                                             # two chunks of amplitudes
+  at = np.concatenate([rng.integers(0, 1 << n, size=1 << 16), np.arange(0, edge), np.arange((1 << n) - edge, 1 << n)])
+  want = pauli_util.np_pauli_sum(host, coeffs, xs, zs, at=at)
+  amax = float(np.max(np.abs(host)))
+  b = pauli_util.bound(64, coeffs, amax, nbatches)
+  g = got[at].astype(np.complex128)
+  err = float(max(np.max(np.abs(g.real - want.real)), np.max(np.abs(g.imag - want.imag))))
+  n2_np = sumsq(got.view(np.float32))
+  print(f'25 qubits complex64: error {err:.3e} (bound {b:.3e}); norm2 {n2:.17g}, NumPy on the stored values {n2_np:.17g}')
+  assert err <= b
+  assert abs(n2 - n2_np) <= 1e-12 * n2_np
+
+
 # ---- 5. composition through qc ----------------------------------------------------------------------------------------------------
 @pytest.fixture(params=[128, 64])
 def width(request):

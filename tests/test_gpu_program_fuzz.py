@@ -7,25 +7,34 @@ permuted local map in front of a barrier step or a reader in at least a third of
 bits or more, and all three paths of the two-state kernels were taken.  Of the register permutations it reads what the real
 qh_perm_plan said right behind each call: at both widths the LDS path and the gather path ran, the gather path on a handle
 that keeps a relayout buffer (which it borrows), on one that keeps none (a temporary) and on a shard, and a permutation ran on a
-non-identity local map that its own flush had left.  The CPU table (tests/test_program_fuzz_cpu.py) only predicts this.
+non-identity local map that its own flush had left.  Of the Pauli-sum operators it reads what the real qh_pauli_sum_plan and
+qh_get_bitmap said right behind each call: at both widths k_pauli_small and k_pauli_batch ran, the latter in all four
+instantiation classes (few or many term slots, one x mask or several) and with an accumulating batch, on a shard with the shard
+sign set, on a non-identity local map that the call's own flush had left, into a destination whose queue was dropped and into
+one that held NaN; at complex64 with physical bit 0 in an x mask and in a z mask.  The CPU table
+(tests/test_program_fuzz_cpu.py) only predicts this.
 
 The figures recorded when the file was added (time, chain errors per program) are in HISTORY.md, section T1; those of the
-register permutations in section T2.
+register permutations in section T2, those of the Pauli-sum operators in section T3.
 """
 import pytest
 
 from qcc_amd import native
 from tests import program_model as pm
+from tests.test_program_fuzz_cpu import pauli_counts
 
 pytestmark = pytest.mark.gpu
 
 SEEN = {'own': 0, 'own_big': 0, 'own_big_relaid': 0, 'paths': set(), 'gather_relayout_0': 0}
 PERMS = []                    # (mode, width, the record of a 'perm' step: program_model._Runner.perm_record), fixed programs only
+PAULIS = []                   # (mode, width, non-identity local map, the record of a 'pauli_sum' step: _Runner.run_pauli_sum), likewise
+VARIANT_PAULIS = {}           # planner variant (its index in pm.ENV_VARIANTS) -> 'pauli_sum' steps on the main shape under it
 # the 'own' programs that run again under a planner variant: (seed, width) whose first handle has sweeps that re-lay out and
 # which hold a register permutation (checked below, so that a change of the generator cannot quietly empty the list); of
 # the four under QH_RELAYOUT=0 the last two were added for a register wide enough for the gather path, there through a
-# temporary on a handle that owns its memory
-VARIANT_PROGRAMS = [(env, seed, bw) for env, pair in zip(pm.ENV_VARIANTS, ([(1, 128), (4, 64), (8, 128), (15, 64)], [(15, 128), (18, 64)], [(6, 128), (8, 64)]))
+# temporary on a handle that owns its memory.  Under each variant at least one program holds a Pauli sum on the main shape
+# (checked by the closing item): own-18 at complex64 no longer holds a 'perm' step and gave way to own-92.
+VARIANT_PROGRAMS = [(env, seed, bw) for env, pair in zip(pm.ENV_VARIANTS, ([(1, 128), (4, 64), (8, 128), (15, 64)], [(15, 128), (92, 64)], [(6, 128), (8, 64)]))
                     for seed, bw in pair]
 
 
@@ -41,6 +50,7 @@ def _run(mode, seed, bw):
 def test_program(mode, seed, bw):
   prog, check = _run(mode, seed, bw)
   PERMS.extend((mode, bw, e[5]) for e in check.events if e[1] == 'perm')
+  PAULIS.extend((mode, bw, e[2], e[5]) for e in check.events if e[1] == 'pauli_sum')
   if mode == 'own':
     SEEN['own'] += 1
     SEEN['paths'] |= {e[4] for e in check.events if e[4] is not None}
@@ -56,6 +66,8 @@ def test_program_under_planner_variants(env, seed, bw, monkeypatch):
     monkeypatch.setenv(k, v)                                # (the planner reads its switches at every flush)
   prog, check = _run('own', seed, bw)
   assert prog[0]['nloc'] >= pm.PERMUTED_FROM and any(s['op'] == 'perm' for s in prog)
+  which = pm.ENV_VARIANTS.index(env)
+  VARIANT_PAULIS[which] = VARIANT_PAULIS.get(which, 0) + sum(1 for e in check.events if e[1] == 'pauli_sum' and e[5]['main'])
   if env.get('QH_RELAYOUT') == '0':
     assert check.relaid == 0                                # no flush re-laid a handle out: clones and siblings decide as told
     perms = [e[5] for e in check.events if e[1] == 'perm']
@@ -86,3 +98,14 @@ def test_zz_relayout_and_inner_paths_were_met():
     assert n['permuted map behind its own flush'] and n['gather on a shard'], n
   print(f"gather-path perm steps under QH_RELAYOUT=0 (a temporary on a handle that owns its memory): {SEEN['gather_relayout_0']}")
   assert SEEN['gather_relayout_0']
+  # the Pauli-sum operators, from what the real qh_pauli_sum_plan and qh_get_bitmap said right behind each call
+  for bw in (128, 64):
+    n = pauli_counts([(mode, permuted, r) for mode, w, permuted, r in PAULIS if w == bw], bw)
+    print(f'pauli_sum steps at complex{bw}: {n}')
+    for k in ('k_pauli_small shape', 'main shape', 'main shape: few term slots, one x mask', 'main shape: few term slots, several x masks',
+              'main shape: many term slots, one x mask', 'main shape: many term slots, several x masks', 'an accumulating batch on the main shape',
+              'shard: main shape with neg set', 'on a non-identity local map its own flush left', 'dst with a queue dropped', 'dst poisoned') + \
+             (('complex64: px bit 0 set', 'complex64: pz bit 0 set') if bw == 64 else ()):
+      assert n.get(k, 0) >= 1, (bw, k, n)
+  print(f'pauli_sum steps on the main shape under the planner variants: {VARIANT_PAULIS}')
+  assert all(VARIANT_PAULIS.get(which, 0) >= 1 for which in range(len(pm.ENV_VARIANTS))), VARIANT_PAULIS

@@ -221,11 +221,94 @@ class PermBeforeItsQueue(pm.NumpyDevice):
       del self._barrier
 
 
+# -- Pauli-sum operators.  Which check of _Runner.run_pauli_sum catches which (the mutants named "only" pass every fixed program
+#    once that one check is deleted; each deletion was tried once, HISTORY.md T3)
+#      21, 22  the amplitudes of the destination: exact for one unit term, within pauli_util.bound otherwise (21 on a shard whose
+#              held z bits have odd parity, 22 where x & z has an odd number of bits); norm2 cannot see a sign or a phase
+#      23      only the bit map: "the destination's bit map is not the source's" -- the amplitudes lie in the map dst kept, so
+#              every value read through that map is right
+#      24      only the pending count behind the step (the queue that survives holds gates the model has dropped; the
+#              amplitudes are read through a clone, which would run them -- the count is asked first)
+#      25      the amplitudes behind a step with a queue on src (bound + C _amp_tol), then norm2 against the model
+#      26      the amplitudes of a step with 17 terms or more; norm2 against the model where the first batch weighs enough
+#      27      the amplitudes (NaN) and norm2 (NaN) of a step on a poisoned destination
+#      28      only the stats: kernels_launched + 1 for no terms (on a new handle also the totals)
+#      29      only the BYTES of a quiet one-term step with c' = 1: equal as numbers, array_equal and norm2 see nothing
+#      30      only norm2 against the amplitudes read back, 1e-12 relative (complex64; the model's norm is 1e-7 away and passes)
+class PauliIgnoresHeldZ(pm.NumpyDevice):
+  """21. apply_pauli_sum ignores the z bits the shard index holds (no shard sign)"""
+  def _pauli_neg(self, term):
+    return 0
+
+
+class PauliPlusI(pm.NumpyDevice):
+  """22. apply_pauli_sum multiplies by (+i)^nY instead of (-i)^nY"""
+  def _pauli_ny(self, term):
+    return -term['ny'] & 3
+
+
+class PauliDstKeepsBitmap(pm.NumpyDevice):
+  """23. apply_pauli_sum writes the result in the layout dst had: dst keeps its own bit map"""
+  def _pauli_bitmap(self, out):
+    return list(out.bm)
+
+
+class PauliDstKeepsQueue(pm.NumpyDevice):
+  """24. apply_pauli_sum leaves what dst has queued in place"""
+  def _pauli_drop_queue(self):
+    pass
+
+
+class PauliBeforeSrcQueue(pm.NumpyDevice):
+  """25. apply_pauli_sum reads src before what src has queued has run (the queue runs behind the call)"""
+  def apply_pauli_sum(self, coeffs, xmasks, zmasks, out=None, norm=False):
+    self._pauli_enter = lambda: None
+    try:
+      res = super().apply_pauli_sum(coeffs, xmasks, zmasks, out, norm)
+    finally:
+      del self._pauli_enter
+    self.flush()
+    return res
+
+
+class PauliLaterBatchOverwrites(pm.NumpyDevice):
+  """26. a later batch of apply_pauli_sum overwrites dst instead of adding to it"""
+  def _pauli_accumulate(self, b, old, part):
+    return part
+
+
+class PauliFirstBatchReadsDst(pm.NumpyDevice):
+  """27. the first batch of apply_pauli_sum adds 0 * dst's old value (NaN stays NaN)"""
+  def _pauli_accumulate(self, b, old, part):
+    return (0.0 * old if b == 0 else old) + part
+
+
+class PauliZeroTermsCountNothing(pm.NumpyDevice):
+  """28. apply_pauli_sum with no terms counts no kernel"""
+  def _pauli_zero_kernels(self):
+    return 0
+
+
+class PauliUnitComputes(pm.NumpyDevice):
+  """29. a one-term batch with c' = 1 passes the amplitudes through arithmetic (x + 0): a negative zero loses its sign"""
+  def _pauli_unit(self, part):
+    return part + 0.0
+
+
+class PauliNormUnrounded(pm.NumpyDevice):
+  """30. at complex64 norm2 is summed from the double values before they are rounded to the handle's width"""
+  def _pauli_norm2(self, stored, unrounded):
+    return float(np.vdot(unrounded, unrounded).real) if self.dtype == np.complex64 else super()._pauli_norm2(stored, unrounded)
+
+
 MUTANTS = [QueueBehindBarrier, CopyKeepsQueue, CopyDropsBitmap, ReleaseKeepsLogicalNumbers, ExtendOnTop, MuxSelectorsReversed,
            TopkTiesByPhysicalIndex, AxpbyReadsDstAnyway, SelectInPhysicalOrder, ReaderCanonicalises, MarginalIgnoresHeldBits,
            RoundsTwice, ReaderTurnsRelayoutOn, PermTableBackwards, PermBitsAscending, PermHeldControlMet, PermCanonicalises,
-           PermNoopCountsAKernel, PermComputes, PermBeforeItsQueue]
-PERM_MUTANTS = MUTANTS[13:]
+           PermNoopCountsAKernel, PermComputes, PermBeforeItsQueue, PauliIgnoresHeldZ, PauliPlusI, PauliDstKeepsBitmap,
+           PauliDstKeepsQueue, PauliBeforeSrcQueue, PauliLaterBatchOverwrites, PauliFirstBatchReadsDst, PauliZeroTermsCountNothing,
+           PauliUnitComputes, PauliNormUnrounded]
+PERM_MUTANTS = MUTANTS[13:20]
+PAULI_MUTANTS = MUTANTS[20:]
 
 
 @pytest.mark.parametrize('mutant', MUTANTS, ids=[m.__name__ for m in MUTANTS])
@@ -235,6 +318,12 @@ def test_the_runner_fails_on_a_broken_device(mutant):
     order = [key for key in order if any(s['op'] == 'perm' for s in program(*key))]
     if mutant in (PermHeldControlMet, PermNoopCountsAKernel):                       # ... and these on a shard alone
       order = [key for key in order if key[0] == 'shard']
+  if mutant in PAULI_MUTANTS:                                 # (they differ from NumpyDevice in apply_pauli_sum alone)
+    order = [key for key in order if any(s['op'] == 'pauli_sum' for s in program(*key))]
+    if mutant is PauliIgnoresHeldZ:
+      order = [key for key in order if key[0] == 'shard']
+    if mutant is PauliNormUnrounded:
+      order = [key for key in order if key[2] == 64]
   for key in order:
     try:
       run_on(mutant, *key)
@@ -243,6 +332,8 @@ def test_the_runner_fails_on_a_broken_device(mutant):
       assert f'step {e.index} ' in str(e) and 0 <= e.index <= len(program(*key))      # the assertion names the step
       if mutant in PERM_MUTANTS:                                                      # ... and it is a permutation that breaks them
         assert e.step['op'] == 'perm', e.step['op']
+      if mutant in PAULI_MUTANTS:                                                     # ... or a Pauli sum
+        assert e.step['op'] == 'pauli_sum', e.step['op']
       return
   raise AssertionError(f'{mutant.__name__} ({mutant.__doc__}) passes every fixed program')
 
@@ -251,7 +342,7 @@ def test_the_runner_fails_on_a_broken_device(mutant):
 def coverage(bw):
   kinds = dict.fromkeys(pm.KINDS, 0)
   permuted = dict.fromkeys(pm.BARRIERS + pm.READERS, 0)
-  queued = dict.fromkeys(pm.BARRIERS + pm.READERS + ('clone', 'copy', 'extend', 'release', 'inner', 'axpby', 'remap'), 0)
+  queued = dict.fromkeys(pm.BARRIERS + pm.READERS + ('clone', 'copy', 'extend', 'release', 'inner', 'axpby', 'pauli_sum', 'remap'), 0)
   paths = {(op, p): 0 for op in pm.TWO_STATE for p in (pm.LINEAR, pm.TILES, pm.GATHER)}
   for (mode, seed, w), c in checks().items():
     if w != bw:
@@ -306,6 +397,63 @@ PERM_AT_LEAST = {'lds': 3, 'gather': 2, 'gather, relayout buffer': 1, 'gather, t
                  'refused: perm_control_in_register': 1, 'refused: perm_register_held': 1}
 
 
+def pauli_counts(records, bw):
+  """what 'pauli_sum' steps met, from (mode, non-identity local map, record of _Runner.run_pauli_sum); shared with the closing
+  item of tests/test_gpu_program_fuzz.py, which counts what the real qh_pauli_sum_plan and qh_get_bitmap said"""
+  n = {}
+  def count(name, cond):
+    n[name] = n.get(name, 0) + bool(cond)
+  for mode, permuted, r in records:
+    classes = set(r['classes']) if r['main'] else set()
+    count('k_pauli_small shape', not r['main'])
+    count('main shape', r['main'])
+    for slots in ('few', 'many'):
+      for groups in ('one', 'several'):
+        count(f'main shape: {slots} term slots, {groups} x mask{"s" if groups == "several" else ""}', (slots, groups) in classes)
+    count('an accumulating batch (17 or more terms)', r['nbatches'] >= 2)
+    count('an accumulating batch on the main shape', r['nbatches'] >= 2 and r['main'])
+    count('zero terms', r['zero'])
+    count("a unit term with c' == 1", r['unit'] == 0)
+    count("a unit term with c' != c", r['unit'] is not None and r['changed'])
+    count('into a new handle', r['new'])
+    count('into an existing handle', not r['new'])
+    count('dst with a queue dropped', r['dst_queued'])
+    count('dst poisoned', r['poisoned'])
+    count('src with a burst queued and relayout on, at 14 or more local bits', r['queued'] and r['relayout_on'] and r['nloc'] >= 14)
+    count("on a non-identity local map its own flush left", r['relaid'])
+    count('on a non-identity local map', permuted)
+    count('shard: a held z bit with neg set', r['shard'] and r['held_z'] and r['neg'])
+    count('shard: main shape', r['shard'] and r['main'])
+    count('shard: main shape with neg set', r['shard'] and r['main'] and r['neg'])
+    count("'attached' programs: dst the attached handle", mode == 'attached' and r['dst_fixed'])
+    count("'mapped' programs: dst the mapped handle", mode == 'mapped' and r['dst_fixed'])
+    if bw == 64:
+      count('complex64: px bit 0 set', r['px0'])
+      count('complex64: pz bit 0 set', r['pz0'])
+  return n
+
+
+def pauli_coverage(bw):
+  """what the 'pauli_sum' steps of the fixed programs met, from the plan NumpyDevice.pauli_sum_plan gives on its own bit map"""
+  n = pauli_counts([(mode, e[2], e[5]) for (mode, seed, w), c in checks().items() if w == bw for e in c.events if e[1] == 'pauli_sum'], bw)
+  for (mode, seed, w) in checks():                             # the refusals of apply_pauli_sum, from the programs themselves
+    for s in program(mode, seed, w):
+      if w == bw and s['op'] == 'refused' and s['what'].startswith('pauli_sum_'):
+        n['refused: ' + s['what']] = n.get('refused: ' + s['what'], 0) + 1
+  return n
+
+
+PAULI_AT_LEAST = {'k_pauli_small shape': 2, 'main shape': 3, 'main shape: few term slots, one x mask': 1,
+                  'main shape: few term slots, several x masks': 1, 'main shape: many term slots, one x mask': 1,
+                  'main shape: many term slots, several x masks': 1, 'an accumulating batch (17 or more terms)': 2, 'zero terms': 1,
+                  "a unit term with c' == 1": 1, "a unit term with c' != c": 1, 'into a new handle': 2, 'into an existing handle': 2,
+                  'dst with a queue dropped': 1, 'dst poisoned': 1, 'src with a burst queued and relayout on, at 14 or more local bits': 1,
+                  'on a non-identity local map': 3, 'shard: a held z bit with neg set': 1, 'shard: main shape': 1,
+                  "'attached' programs: dst the attached handle": 1, "'mapped' programs: dst the mapped handle": 1,
+                  'refused: pauli_sum_self': 1, 'refused: pauli_sum_bad_qubit': 1, 'refused: pauli_sum_x_held': 1}
+PAULI_AT_LEAST_64 = {'complex64: px bit 0 set': 2, 'complex64: pz bit 0 set': 2}
+
+
 @pytest.mark.parametrize('bw', WIDTHS)
 def test_coverage_of_the_fixed_programs(bw):
   kinds, permuted, queued, paths = coverage(bw)
@@ -321,6 +469,10 @@ def test_coverage_of_the_fixed_programs(bw):
   perms = perm_coverage(bw)
   print('  perm steps: ' + ', '.join(f'{k} {n}' + (f' (>= {PERM_AT_LEAST[k]})' if k in PERM_AT_LEAST else '') for k, n in perms.items()))
   assert all(perms.get(k, 0) >= least for k, least in PERM_AT_LEAST.items()), perms
+  least = dict(PAULI_AT_LEAST, **(PAULI_AT_LEAST_64 if bw == 64 else {}))
+  paulis = pauli_coverage(bw)
+  print('  pauli_sum steps: ' + ', '.join(f'{k} {n}' + (f' (>= {least[k]})' if k in least else '') for k, n in paulis.items()))
+  assert all(paulis.get(k, 0) >= v for k, v in least.items()), {k: paulis.get(k, 0) for k, v in least.items() if paulis.get(k, 0) < v}
 
 
 def test_the_long_running_tool_ends_at_the_first_failure(monkeypatch, capsys):
