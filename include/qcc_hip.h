@@ -483,6 +483,49 @@ int qh_pauli_sum_plan(qh_handle src, uint64_t nterms, const uint64_t *xmask, con
                       qh_pauli_term *terms /* nterms, sorted order; may be NULL */,
                       qh_pauli_batch *batches, uint64_t cap, uint64_t *nbatches);
 
+/* ---- Pauli products (kernels_pauli_product.hip.h, pauli_product_plan.h) -------- */
+/* state := F_{n-1} ... F_1 F_0 state in place, F_t = a_t I + b_t P_t: term 0 is applied first and the caller's order is never
+ * changed.  ab holds (a.re, a.im, b.re, b.im) per term; the masks and P are those of qh_expect_pauli and qh_apply_pauli_sum,
+ *   (P v)_i = (-i)^nY (-1)^popcount(i & z) v_{i ^ x}   over LOGICAL bits.
+ * Any finite complex a, b: a rotation exp(-i t P) is (cos t, -i sin t), imaginary time (cosh t, -sinh t), a projector
+ * (1/2, +-1/2), the string itself (0, 1).
+ * A barrier, as qh_apply_mux and qh_apply_perm: what is queued runs first and the call works on the layout it finds; bit map,
+ * relayout mode and device pointer are as before.  Attached, host-mapped and shard handles, from 1 local bit up, at either
+ * width.  The caller's arrays are not referenced after the call returns.
+ * Shards: a z bit held by the shard index is a sign, folded into b on the host together with (-i)^nY (b', swaps and negations
+ * only); an x bit there is QH_ERR_NONLOCAL.  The WHOLE term list is checked before anything is flushed or run.
+ * Runs: the terms are walked in order, keeping the current run's pair mask X (physical, local; 0 while every term so far is
+ * diagonal).  Term t (physical x mask px_t) joins the run if the run has fewer than QH_PAULI_PRODUCT_BATCH terms and px_t == 0,
+ * X == 0 or px_t == X; otherwise a new run starts.  One kernel per run: one read and one write of the state, whatever the
+ * weight of the strings.  (The batch is 8: measured at 30 qubits, a 16-term run cost more per term than two of 8;
+ * DESIGN.md "Pauli products".)  kind: QH_PAULI_RUN_DIAG (every px == 0), QH_PAULI_RUN_HALF (complex64 and X == 1: the pair lies
+ * inside one 16-byte item), QH_PAULI_RUN_PAIR (otherwise).
+ * Arithmetic: every term of a run is applied in registers, in double, to the amplitudes as stored (complex64 widened
+ * unrounded); the result is rounded once per run to the handle's width.  A run of ONE term with a == 0 and b' a power of i
+ * moves the stored bits (negated and / or with the components swapped): exact at both widths.  A run of one term with a == 1,
+ * b == 0 leaves every bit as it was.
+ * norm2 (may be NULL): sum |v|^2 of the FINAL amplitudes as stored, over this shard, summed by the last run in the readers'
+ * fixed order without atomics: bitwise reproducible.  nterms == 0 flushes and launches no kernel; norm2 is then qh_norm2's.
+ * qh_stats: gates_submitted + nterms, kernels_launched + the number of runs, bytes_swept and bytes_algorithmic + 2 x the
+ * shard's bytes per run.
+ * Errors, nothing runs, nothing changes, nothing is flushed: QH_ERR_ARG (null handle, null arrays with nterms > 0, dry handle,
+ * a non-finite coefficient: qh_last_error names the first offending term), QH_ERR_BAD_QUBIT (mask bits >= nbits_global),
+ * QH_ERR_NONLOCAL as above.                                                                                                 */
+#define QH_PAULI_PRODUCT_BATCH 8
+#define QH_PAULI_RUN_DIAG 0
+#define QH_PAULI_RUN_PAIR 1
+#define QH_PAULI_RUN_HALF 2
+int qh_apply_pauli_product(qh_handle h, uint64_t nterms, const double *ab /* 4 per term: a.re a.im b.re b.im */,
+                           const uint64_t *xmask, const uint64_t *zmask, double *norm2 /* may be NULL */);
+/* How qh_apply_pauli_product would cut these terms into runs on h right now: runs nothing, flushes nothing, planner-only
+ * handles too.  terms (may be NULL): the nterms terms in the caller's order, as qh_pauli_sum_plan reports them.  runs: at most
+ * cap are written, *nruns is always set; run r holds terms [first, first + count), pair mask px (0: diagonal) and its kind.
+ * The engine launches from this very function.  Errors: QH_ERR_ARG (null), QH_ERR_BAD_QUBIT, QH_ERR_NONLOCAL as above.      */
+typedef struct { uint64_t first, count, px; uint32_t kind, pad; } qh_pauli_run;
+int qh_pauli_product_plan(qh_handle h, uint64_t nterms, const uint64_t *xmask, const uint64_t *zmask,
+                          qh_pauli_term *terms /* nterms, caller's order; may be NULL */,
+                          qh_pauli_run *runs, uint64_t cap, uint64_t *nruns);
+
 /* ---- growing and shrinking a state (kernels_resize.hip.h) ----------------- */
 /* Both calls make a NEW handle and leave src as qh_clone leaves it: what src has queued runs first (exchange arrivals are
  * waited for); src keeps its amplitudes, bit map, relayout mode and device pointer.  The new handle lives on src's device with

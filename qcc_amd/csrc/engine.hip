@@ -35,6 +35,8 @@
 #include "kernels_expect.hip.h"
 #include "kernels_pauli.hip.h"
 #include "pauli_plan.h"
+#include "kernels_pauli_product.hip.h"
+#include "pauli_product_plan.h"
 #include "kernels_two_state.hip.h"
 #include "kernels_inner.hip.h"
 #include "kernels_axpby.hip.h"
@@ -759,7 +761,7 @@ int select_device(int device) {
 extern "C" {
 
 const char *qh_last_error(void) { return g_err.c_str(); }
-int qh_version(void) { return 115; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
+int qh_version(void) { return 116; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
 
 int qh_device_count(int *count) {
   if (!count) return fail(QH_ERR_ARG, "null");
@@ -2701,10 +2703,11 @@ int qh_expect_pauli(qh_handle h, uint64_t nterms, const uint64_t *xmask, const u
 // ---- Pauli-sum operators: qh_apply_pauli_sum, qh_pauli_sum_new, qh_pauli_sum_plan (kernels_pauli.hip.h, pauli_plan.h) ------
 namespace {
 
-// The terms on h's bit map as it is now, sorted: masks checked against nglob, local bits as physical masks, a z bit the
-// shard index holds as a sign, an x bit there refused.  Host arithmetic only: valid on dry handles.
+// The terms on h's bit map as it is now, sorted (qh_apply_pauli_product: in the caller's order): masks checked against nglob,
+// local bits as physical masks, a z bit the shard index holds as a sign, an x bit there refused.  Host arithmetic only: valid
+// on dry handles.
 int plan_pauli(const qh_state_s *h, const char *who, uint64_t nterms, const uint64_t *xmask, const uint64_t *zmask,
-               std::vector<qh_pauli_term> *terms) {
+               std::vector<qh_pauli_term> *terms, bool sorted = true) {
   if (h->nglob < 64)
     for (uint64_t t = 0; t < nterms; ++t)
       if ((xmask[t] | zmask[t]) >> h->nglob)
@@ -2721,7 +2724,7 @@ int plan_pauli(const qh_state_s *h, const char *who, uint64_t nterms, const uint
     (*terms)[t] = qh_pauli_term{t, x.local, z.local, (uint32_t)__builtin_popcountll(h->shard & z.held) & 1u,
                                 (uint32_t)__builtin_popcountll(xmask[t] & zmask[t]) & 3u};
   }
-  qh::pauli_sort(terms->data(), nterms);
+  if (sorted) qh::pauli_sort(terms->data(), nterms);
   return QH_OK;
 }
 
@@ -2855,6 +2858,144 @@ int qh_pauli_sum_new(qh_handle src, uint64_t nterms, const double *coeffs, const
   if ((rc = make_sibling(src, src->nloc, src->nglob, "pauli_sum_new", &h))) return rc;
   if ((rc = qh_apply_pauli_sum(h, src, nterms, coeffs, xmask, zmask, norm2))) return drop_sibling(h, rc);
   *out = h;
+  return QH_OK;
+}
+
+}  // extern "C"
+
+// ---- Pauli products: qh_apply_pauli_product, qh_pauli_product_plan (kernels_pauli_product.hip.h, pauli_product_plan.h) ------
+namespace {
+
+// the terms in the caller's order on h's bit map as it is now, and their runs
+int plan_pauli_product(const qh_state_s *h, const char *who, uint64_t nterms, const uint64_t *xmask, const uint64_t *zmask,
+                       std::vector<qh_pauli_term> *terms, std::vector<qh_pauli_run> *runs) {
+  const int rc = plan_pauli(h, who, nterms, xmask, zmask, terms, false);
+  if (rc) return rc;
+  const int ab = h->bw == 128 ? 0 : 1;
+  runs->resize(qh::pauli_product_cut(terms->data(), nterms, ab, nullptr, 0));
+  qh::pauli_product_cut(terms->data(), nterms, ab, runs->data(), runs->size());
+  return QH_OK;
+}
+
+// kind: QH_PAULI_RUN_* of the plan, or qh::kPauliWalkLane for a PAIR run whose pairs lie inside a wave
+template <typename R, int TT>
+void launch_pauli_product_kind(qh_state_s *h, uint32_t kind, unsigned nblk, const qh::PauliProdArgs &a, double *slab) {
+  using V = typename qh::Item16<R>::vec;
+  V *psi = (V *)h->d_psi;
+  const dim3 grid(nblk), block(256);
+  if (kind == QH_PAULI_RUN_DIAG) hipLaunchKernelGGL((qh::k_pauli_product<R, TT, QH_PAULI_RUN_DIAG>), grid, block, 0, h->stream, psi, a, slab);
+  else if (kind == QH_PAULI_RUN_PAIR) hipLaunchKernelGGL((qh::k_pauli_product<R, TT, QH_PAULI_RUN_PAIR>), grid, block, 0, h->stream, psi, a, slab);
+  else if (kind == (uint32_t)qh::kPauliWalkLane) hipLaunchKernelGGL((qh::k_pauli_product<R, TT, qh::kPauliWalkLane>), grid, block, 0, h->stream, psi, a, slab);
+  else if constexpr (qh::Item16<R>::kAmpBits == 1)
+    hipLaunchKernelGGL((qh::k_pauli_product<R, TT, QH_PAULI_RUN_HALF>), grid, block, 0, h->stream, psi, a, slab);
+}
+
+// one run on h's stream
+void launch_pauli_run(qh_state_s *h, const qh_pauli_run &run, const qh_pauli_term *terms, const double *coef, bool norm, double *slab,
+                      uint64_t *nblk) {
+  qh::PauliProdArgs a{};
+  qh::PauliProdZ zs{};      // (k_pauli_product_small alone)
+  const int ab = h->bw == 128 ? 0 : 1;
+  const bool main_shape = qh::pauli_product_main_shape(h->nloc, ab);
+  const bool lane = run.kind == QH_PAULI_RUN_PAIR && qh::pauli_pair_in_wave(run.px, ab);      // walks items; the partner by a lane exchange
+  const bool pair = run.kind == QH_PAULI_RUN_PAIR && !lane;                                     // walks pair numbers
+  a.X = run.px;
+  if (main_shape) a.pivot = pair ? qh::pauli_pair_pivot(run.px, ab) : 0;
+  else a.pivot = run.px ? 63 - __builtin_clzll(run.px) : 0;
+  for (uint64_t k = 0; k < run.count; ++k) {
+    const qh_pauli_term &tm = terms[run.first + k];
+    const double *c = coef + 4 * tm.index;
+    double b[2];
+    qh::pauli_coef(c[2], c[3], tm.ny, tm.neg, b);
+    // PAIR walks pair numbers: the z mask over them (the pivot bit, clear in item0, removed)
+    const qh::PauliZSplit z = qh::pauli_split_z(main_shape && pair ? qh::pauli_pair_z(tm.pz, a.pivot, ab) : tm.pz, ab);
+    a.are[k] = c[0];
+    a.aim[k] = c[1];
+    a.bre[k] = b[0];
+    a.bim[k] = b[1];
+    zs.pz[k] = tm.pz;
+    a.zc[k] = (uint32_t)z.chunk;
+    a.zu[k] = (uint16_t)z.reg;
+    a.zt[k] = (uint8_t)z.thread;
+    a.zh |= z.half << k;
+    if (tm.px) a.offd |= 1u << k;
+    a.flip |= qh::pauli_pair_flip(run.px, tm.pz) << k;
+    if (run.count == 1) {
+      if (c[0] == 0.0 && c[1] == 0.0) a.unit = 1 + qh::pauli_unit(b);
+      else if (c[0] == 1.0 && c[1] == 0.0 && c[2] == 0.0 && c[3] == 0.0) a.unit = 5;
+    }
+  }
+  a.count = (int)run.count;
+  a.norm = norm ? 1 : 0;
+  with_real(h, [&](auto x) {
+    using R = decltype(x);
+    if (main_shape) {
+      const qh::PauliGrid g = qh::pauli_product_grid(h->nloc, ab, pair);
+      const uint32_t kind = lane ? (uint32_t)qh::kPauliWalkLane : run.kind;
+      a.cpb = g.cpb;
+      *nblk = g.nblk;
+      if (run.count <= (uint64_t)qh::kPauliProdSmallT) launch_pauli_product_kind<R, qh::kPauliProdSmallT>(h, kind, (unsigned)g.nblk, a, slab);
+      else if (qh::kPauliProdT > qh::kPauliProdMidT && run.count <= (uint64_t)qh::kPauliProdMidT)      // (A/B builds with 16 slots)
+        launch_pauli_product_kind<R, qh::kPauliProdMidT>(h, kind, (unsigned)g.nblk, a, slab);
+      else launch_pauli_product_kind<R, qh::kPauliProdT>(h, kind, (unsigned)g.nblk, a, slab);
+    } else {
+      using A = typename qh::AmpT<R>::type;
+      const uint64_t nwork = 1ull << (run.px ? h->nloc - 1 : h->nloc);
+      *nblk = (nwork + 255) / 256;
+      hipLaunchKernelGGL((qh::k_pauli_product_small<R>), dim3((unsigned)*nblk), dim3(256), 0, h->stream, (A *)h->d_psi, a, zs, nwork, slab);
+    }
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int qh_pauli_product_plan(qh_handle h, uint64_t nterms, const uint64_t *xmask, const uint64_t *zmask, qh_pauli_term *terms,
+                          qh_pauli_run *runs, uint64_t cap, uint64_t *nruns) {
+  if (!h || !nruns || (nterms && (!xmask || !zmask)) || (cap && !runs))
+    return fail(QH_ERR_ARG, "pauli_product_plan: null handle, masks, runs or nruns");
+  std::vector<qh_pauli_term> tv;
+  std::vector<qh_pauli_run> rv;
+  const int rc = plan_pauli_product(h, "pauli_product_plan", nterms, xmask, zmask, &tv, &rv);
+  if (rc) return rc;
+  if (terms && nterms) memcpy(terms, tv.data(), nterms * sizeof(qh_pauli_term));
+  for (uint64_t r = 0; r < rv.size() && r < cap; ++r) runs[r] = rv[r];
+  *nruns = rv.size();
+  return QH_OK;
+}
+
+int qh_apply_pauli_product(qh_handle h, uint64_t nterms, const double *ab, const uint64_t *xmask, const uint64_t *zmask, double *norm2) {
+  if (!h) return fail(QH_ERR_ARG, "apply_pauli_product: null handle");
+  if (nterms && (!ab || !xmask || !zmask))
+    return fail(QH_ERR_ARG, "apply_pauli_product: null coefficients or masks with %llu terms", (unsigned long long)nterms);
+  for (uint64_t t = 0; t < nterms; ++t)
+    for (int j = 0; j < 4; ++j)
+      if (!std::isfinite(ab[4 * t + j]))
+        return fail(QH_ERR_ARG, "apply_pauli_product: term %llu has a non-finite coefficient (a = %g%+gi, b = %g%+gi)", (unsigned long long)t,
+                    ab[4 * t], ab[4 * t + 1], ab[4 * t + 2], ab[4 * t + 3]);
+  std::vector<qh_pauli_term> terms;
+  std::vector<qh_pauli_run> runs;
+  // which bits the shard index holds is not something a flush changes: the whole list is refused before anything runs
+  int rc = plan_pauli_product(h, "apply_pauli_product", nterms, xmask, zmask, &terms, &runs);
+  if (rc) return rc;
+  if (h->dry) return fail(QH_ERR_ARG, "apply_pauli_product: not on a dry (planner-only) handle");
+  if ((rc = enter(h))) return rc;          // a barrier: what is queued runs first, on whatever layout it leaves
+  if (nterms == 0) return norm2 ? masked_norm2(h, 0ull, 0ull, norm2) : QH_OK;
+  if ((rc = plan_pauli_product(h, "apply_pauli_product", nterms, xmask, zmask, &terms, &runs))) return rc;
+  SlabSum sum{h};
+  if (norm2) HIP_TRY(sum.reserve(std::max<uint64_t>(qh::kPauliBlocks, 8), 1, 1));
+  uint64_t nblk = 1;
+  for (size_t r = 0; r < runs.size(); ++r)
+    launch_pauli_run(h, runs[r], terms.data(), ab, norm2 && r + 1 == runs.size(), sum.slab, &nblk);
+  if (norm2) sum.fold(nblk, 1, 1);
+  if ((rc = check_launch(h))) return rc;
+  if (norm2 && (rc = sum.get(norm2, 1, "qh_apply_pauli_product"))) return rc;
+  const uint64_t shard_bytes = (1ull << h->nloc) * h->amp_bytes();
+  h->stats.gates_submitted += nterms;
+  h->stats.kernels_launched += runs.size();      // (the fold is not counted, as in qh_axpby)
+  h->stats.bytes_swept += 2 * runs.size() * shard_bytes;
+  h->stats.bytes_algorithmic += 2 * runs.size() * shard_bytes;
   return QH_OK;
 }
 

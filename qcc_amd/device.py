@@ -537,6 +537,39 @@ class DeviceState:
     tl = [{k: int(getattr(terms[j], k)) for k, _ in native.QhPauliTerm._fields_} for j in range(n)]
     return tl, [batches[b].as_dict() for b in range(nb.value)]
 
+  # -- Pauli products -------------------------------------------------------------
+  @staticmethod
+  def _pauli_product_arrays(a, b, xmasks, zmasks):
+    ab = np.ascontiguousarray([[complex(u), complex(v)] for u, v in zip(a, b)], dtype=np.complex128).reshape(-1, 2)
+    x = np.ascontiguousarray([int(v) for v in xmasks], dtype=np.uint64)
+    z = np.ascontiguousarray([int(v) for v in zmasks], dtype=np.uint64)
+    if not len(a) == len(b) == x.size == z.size:
+      raise ValueError(f'apply_pauli_product: {len(a)} a, {len(b)} b, {x.size} x masks, {z.size} z masks')
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    return (ab, x, z), ab.view(np.float64).ctypes.data_as(_dp), x.ctypes.data_as(u64p), z.ctypes.data_as(u64p)
+
+  def apply_pauli_product(self, a, b, xmasks, zmasks, norm=False):
+    """state := F_{n-1} ... F_0 state in place, F_t = a[t] I + b[t] P_t (qh_apply_pauli_product): complex a, b and Pauli
+    strings as LOGICAL bit masks (x: X or Y on the bit, z: Z or Y), as in expect_pauli.  Term 0 is applied first.  Queued
+    gates run first.  norm=True returns sum |a|^2 of the result over this shard, otherwise None."""
+    keep, abp, xp, zp = self._pauli_product_arrays(list(a), list(b), xmasks, zmasks)
+    n2 = ctypes.c_double() if norm else None
+    native.check(self.lib.qh_apply_pauli_product(self.h, int(keep[1].size), abp, xp, zp, ctypes.byref(n2) if norm else None))
+    return n2.value if norm else None
+
+  def pauli_product_plan(self, xmasks, zmasks):
+    """How apply_pauli_product would cut these strings into runs right now (qh_pauli_product_plan): (terms, runs), lists of
+    dicts; the terms are in the caller's order."""
+    keep, _abp, xp, zp = self._pauli_product_arrays([0] * len(xmasks), [0] * len(xmasks), xmasks, zmasks)
+    n = int(keep[1].size)
+    terms = (native.QhPauliTerm * max(n, 1))()
+    cap = max(n, 1)
+    runs = (native.QhPauliRun * cap)()
+    nr = ctypes.c_uint64()
+    native.check(self.lib.qh_pauli_product_plan(self.h, n, xp, zp, terms, runs, cap, ctypes.byref(nr)))
+    tl = [{k: int(getattr(terms[j], k)) for k, _ in native.QhPauliTerm._fields_} for j in range(n)]
+    return tl, [runs[r].as_dict() for r in range(nr.value)]
+
   def inner_plan(self, other):
     """How inner(other) would walk the two states right now (qh_inner_plan), as a dict."""
     t = native.QhInnerTiles()

@@ -1224,6 +1224,106 @@ class qc:
             norm2 = float(np.vdot(new, new).real)
         return float(norm2) - float(self.expectation(terms)) ** 2
 
+    # Pauli products (eager extensions with the standing of diagonal and permutation: not recorded in the IR).  A product of
+    # factors a_t I + b_t P_t is applied in place, term 0 first (qh_apply_pauli_product: consecutive factors that act on the
+    # same amplitude pairs share one pass over the state).  With a device that cannot apply_pauli_product (and in aliased
+    # mode) the same factors run over qc.psi on the host.
+    def _pauli_product_host(self, a, b, xs, zs):
+        """prod_t (a_t I + b_t P_t) |psi> from qc.psi: complex128, rounded once to the state's width."""
+        amps = np.asarray(self.psi).reshape(-1)
+        v = amps.astype(np.complex128)
+        idx = np.arange(v.size, dtype=np.uint64)
+        for at, bt, x, z in zip(a, b, xs, zs):
+            par = np.zeros(v.size, dtype=np.uint64)
+            for bit in range(self._nbits):
+                if (z >> bit) & 1:
+                    par ^= (idx >> np.uint64(bit)) & np.uint64(1)
+            v = at * v + (bt * (-1j) ** (bin(x & z).count('1') % 4)) * (1.0 - 2.0 * par.astype(np.float64)) * v[idx ^ np.uint64(x)]
+        return v.astype(amps.dtype)
+
+    def _pauli_product(self, a, b, xs, zs, norm=False):
+        """Applies the factors; norm=True returns the norm^2 of the result as stored (the device then sums it in the last
+        pass and the host waits for it; without it the call is queued on the stream like a gate)."""
+        dev = self._ensure_device()
+        if hasattr(dev, 'apply_pauli_product') and not self._alias:
+            norm2 = dev.apply_pauli_product(a, b, xs, zs, norm=norm)
+            self._gate_done()
+            return float(norm2) if norm else None
+        new = self._pauli_product_host(a, b, xs, zs)
+        self.psi = new
+        return float(np.vdot(new.astype(np.complex128), new.astype(np.complex128)).real) if norm else None
+
+    def _rescale(self, norm2, what):
+        if not norm2 > 0:
+            raise ValueError(f'{what}: the result is 0, nothing to normalise')
+        dev = self._ensure_device()
+        if hasattr(dev, 'scale') and not self._alias:
+            dev.scale(1.0 / math.sqrt(norm2))
+            self._gate_done()
+        else:
+            self.psi = np.asarray(self.psi).reshape(-1) / math.sqrt(norm2)
+
+    def pauli_rot(self, paulis, theta):
+        """exp(-i theta/2 P) for one Pauli string (see _pauli_masks), the convention of rx / ry / rz:
+        pauli_rot({q: 'X'}, t) is rx(q, t).  One pass over the state whatever the weight of the string."""
+        x, z = self._pauli_masks(paulis)
+        theta = float(theta)
+        self._pauli_product([math.cos(theta / 2)], [-1j * math.sin(theta / 2)], [x], [z])
+
+    def apply_pauli(self, paulis):
+        """The Pauli string itself: amplitudes are moved, negated and multiplied by +-i only, so the result is exact."""
+        x, z = self._pauli_masks(paulis)
+        self._pauli_product([0.0], [1.0], [x], [z])
+
+    def evolve(self, terms, t, *, steps=1, order=1):
+        """prod_t exp(-i (t / steps) c_t P_t), repeated `steps` times, for terms = [(c_t, paulis_t), ...] with real c_t: a
+        Trotter step of H = sum_t c_t P_t.  The terms stay in the caller's order (the first is applied first); order=2 is
+        the palindromic sequence with half angles.  All steps go to the device in one call."""
+        coeffs, xs, zs = self._pauli_terms(terms, 'evolve')
+        if any(c.imag != 0 for c in coeffs):
+            raise ValueError('evolve: real coefficients only (H must be Hermitian)')
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 1:
+            raise ValueError(f'evolve: steps = {steps!r} (want an int >= 1)')
+        if order not in (1, 2):
+            raise ValueError(f'evolve: order = {order!r} (want 1 or 2)')
+        dt = float(t) / int(steps)
+        seq = list(range(len(coeffs)))
+        if order == 2:
+            seq, dt = seq + seq[::-1], dt / 2
+        seq = seq * int(steps)
+        a = [math.cos(dt * coeffs[k].real) for k in seq]
+        b = [-1j * math.sin(dt * coeffs[k].real) for k in seq]
+        self._pauli_product(a, b, [xs[k] for k in seq], [zs[k] for k in seq])
+
+    def imaginary_time(self, terms, tau, *, steps=1, normalize=True):
+        """prod_t exp(-(tau / steps) c_t P_t), repeated `steps` times (factors cosh - sinh P; real c_t).  Returns the
+        norm^2 of the result before any normalisation; normalize=True follows with scale(1 / sqrt(norm^2)) and raises
+        ValueError where the result is 0."""
+        coeffs, xs, zs = self._pauli_terms(terms, 'imaginary_time')
+        if any(c.imag != 0 for c in coeffs):
+            raise ValueError('imaginary_time: real coefficients only (H must be Hermitian)')
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 1:
+            raise ValueError(f'imaginary_time: steps = {steps!r} (want an int >= 1)')
+        dt = float(tau) / int(steps)
+        seq = list(range(len(coeffs))) * int(steps)
+        norm2 = self._pauli_product([math.cosh(dt * coeffs[k].real) for k in seq], [-math.sinh(dt * coeffs[k].real) for k in seq],
+                                    [xs[k] for k in seq], [zs[k] for k in seq], norm=True)
+        if normalize:
+            self._rescale(norm2, 'imaginary_time')
+        return norm2
+
+    def pauli_project(self, paulis, eigenvalue=+1, *, normalize=True):
+        """The projector (I + eigenvalue P) / 2 onto an eigenspace of one Pauli string: a stabiliser measurement with a
+        chosen outcome.  Returns the norm^2 of the projected state -- the probability of that outcome for a normalised
+        state; normalize=True then rescales to norm 1 and raises ValueError where the probability is 0."""
+        if eigenvalue not in (1, -1):
+            raise ValueError(f'pauli_project: eigenvalue = {eigenvalue!r} (want +1 or -1)')
+        x, z = self._pauli_masks(paulis)
+        norm2 = self._pauli_product([0.5], [0.5 * int(eigenvalue)], [x], [z], norm=True)
+        if normalize:
+            self._rescale(norm2, 'pauli_project')
+        return norm2
+
     # Two states (extensions; the reference compares states on the host: State.diff, the swap and Hadamard tests).  With a
     # device that cannot clone / copy_from / inner, the amplitudes go through qc.psi on the host instead.
     def snapshot(self):

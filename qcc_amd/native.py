@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB_PATH = os.environ.get('QCC_HIP_LIB') or os.path.join(PKG, 'libqcc_hip.so')  # env: A/B builds only
 SOURCES = [os.path.join(PKG, 'csrc', f) for f in
-           ('engine.hip', 'buffers.hip.h', 'kernels_common.hip.h', 'kernels_gate.hip.h', 'kernels_argmax.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_perm.hip.h', 'perm_plan.h', 'kernels_measure.hip.h', 'kernels_select.hip.h', 'select_plan.h', 'kernels_expect.hip.h', 'kernels_pauli.hip.h', 'pauli_plan.h', 'kernels_two_state.hip.h', 'kernels_inner.hip.h', 'kernels_axpby.hip.h', 'inner_plan.h', 'kernels_resize.hip.h', 'resize_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h', 'exchange_plan.h',
+           ('engine.hip', 'buffers.hip.h', 'kernels_common.hip.h', 'kernels_gate.hip.h', 'kernels_argmax.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_perm.hip.h', 'perm_plan.h', 'kernels_measure.hip.h', 'kernels_select.hip.h', 'select_plan.h', 'kernels_expect.hip.h', 'kernels_pauli.hip.h', 'pauli_plan.h', 'kernels_pauli_product.hip.h', 'pauli_product_plan.h', 'kernels_two_state.hip.h', 'kernels_inner.hip.h', 'kernels_axpby.hip.h', 'inner_plan.h', 'kernels_resize.hip.h', 'resize_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h', 'exchange_plan.h',
             'sweep_island_rb2.inc', 'sweep_island_rb3.inc', 'sweep_island_rb4.inc',
             'sweep_island_rb5.inc', 'sweep_island_f32_rb2.inc', 'sweep_island_f32_rb3.inc',
             'sweep_island_f32_rb4.inc', 'sweep_island_f32_rb5.inc', 'sweep_island_f32_rb6.inc', 'sweep_handlers.inc',
@@ -89,6 +89,18 @@ class QhPauliBatch(ctypes.Structure):
     return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+QH_PAULI_PRODUCT_BATCH = 8
+QH_PAULI_RUN_DIAG, QH_PAULI_RUN_PAIR, QH_PAULI_RUN_HALF = 0, 1, 2
+
+
+class QhPauliRun(ctypes.Structure):
+  """include/qcc_hip.h qh_pauli_run: one kernel of qh_apply_pauli_product."""
+  _fields_ = [('first', _u64), ('count', _u64), ('px', _u64), ('kind', ctypes.c_uint32), ('pad', ctypes.c_uint32)]
+
+  def as_dict(self):
+    return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != 'pad'}
+
+
 # name -> (restype, argtypes); every symbol declared in include/qcc_hip.h
 SIGNATURES = {
     'qh_last_error': (ctypes.c_char_p, []),
@@ -150,6 +162,9 @@ SIGNATURES = {
     'qh_pauli_sum_new': (_i32, [_vp, _u64, _dp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _dp, ctypes.POINTER(_vp)]),
     'qh_pauli_sum_plan': (_i32, [_vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(QhPauliTerm),
                                  ctypes.POINTER(QhPauliBatch), _u64, ctypes.POINTER(_u64)]),
+    'qh_apply_pauli_product': (_i32, [_vp, _u64, _dp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _dp]),
+    'qh_pauli_product_plan': (_i32, [_vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(QhPauliTerm),
+                                     ctypes.POINTER(QhPauliRun), _u64, ctypes.POINTER(_u64)]),
     'qh_extend': (_i32, [_vp, _i32, _dp, _u64, ctypes.POINTER(_vp)]),
     'qh_release': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _u64, _dp, ctypes.POINTER(_vp)]),
     'qh_get_stats': (_i32, [_vp, ctypes.POINTER(QhStats)]),
