@@ -16,15 +16,16 @@ two logical bits whose positions are exchanged, the runner looks the positions u
 References are imported, not copied: tests/oracle_lib (gates), fake_device.np_marginal / np_keep, resize_util.np_extend /
 np_release, select_util.np_select / np_topk / fma_probs, test_dense_cpu.dense_reference, test_mux_cpu.mux_reference_fast /
 diag_reference, test_expect_cpu.np_expect, test_perm_cpu.perm_reference (and the tile rule of qh_perm_plan it states),
-pauli_util.np_pauli_sum and pauli_util.bound (qh_apply_pauli_sum and its derived error bound), shard_util.check_exact_cdf
-(the inverse CDF of qh_sample in physical order)."""
+pauli_util.np_pauli_sum and pauli_util.bound (qh_apply_pauli_sum and its derived error bound),
+pauli_product_util.np_pauli_product, bound and greedy_runs (qh_apply_pauli_product, its derived bound and its run rule),
+shard_util.check_exact_cdf (the inverse CDF of qh_sample in physical order)."""
 import os
 import sys
 
 import numpy as np
 
 from qcc_amd import native
-from tests import oracle_lib, pauli_util, shard_util
+from tests import oracle_lib, pauli_product_util as ppu, pauli_util, shard_util
 from tests.fake_device import np_keep, np_marginal
 from tests.resize_util import np_extend, np_release
 from tests.select_util import fma_probs, np_select, np_topk
@@ -47,7 +48,8 @@ BARRIERS = ('matrix', 'mux', 'diag', 'perm', 'scale', 'project_bit', 'project_bi
 READERS = ('norm2', 'prob_bit', 'marginal', 'sample', 'expect', 'argmax', 'amplitude', 'amplitudes', 'select', 'topk')
 HANDLE_STEPS = ('clone', 'copy', 'extend', 'release', 'close')
 TWO_STATE = ('inner', 'axpby')
-OPERATOR_STEPS = ('pauli_sum',)     # reads one handle and replaces another whole (or makes a new one)
+# pauli_sum reads one handle and replaces another whole (or makes a new one); pauli_product works in place, in runs of kernels
+OPERATOR_STEPS = ('pauli_sum', 'pauli_product')
 LAYOUT_STEPS = ('flush', 'set_relayout', 'remap')
 KINDS = ('gates',) + BARRIERS + READERS + HANDLE_STEPS + TWO_STATE + OPERATOR_STEPS + LAYOUT_STEPS + ('refused',)
 
@@ -55,9 +57,11 @@ KINDS = ('gates',) + BARRIERS + READERS + HANDLE_STEPS + TWO_STATE + OPERATOR_ST
 # the fixed programs of the suite (tests/test_program_fuzz_cpu.py on NumpyDevice, tests/test_gpu_program_fuzz.py on the GPU),
 # each at both widths; the coverage table of the CPU test is what this seed list was chosen by
 # (re-chosen when 'perm' and then 'pauli_sum' became kinds: one stream draws the kinds, so a new kind changes every program of
-# every seed; no seed has left the list)
-FIXED = [('own', seed) for seed in list(range(21)) + [42, 48, 60, 88, 92, 139]] + [('shard', seed) for seed in list(range(6)) + [15, 22, 24, 34, 54]] + \
-        [('attached', seed) for seed in list(range(4)) + [5, 7, 11]] + [('mapped', seed) for seed in list(range(4)) + [15, 42]]
+# every seed; no seed has left the list.  With 'pauli_product': own 44, 82, shard 25, 32, 64, attached 176 and mapped 56, 73 joined, each for
+# a condition of the coverage tables that the other programs no longer or never met -- HISTORY.md T4 names them)
+FIXED = [('own', seed) for seed in list(range(21)) + [42, 44, 48, 60, 82, 88, 92, 139]] + \
+        [('shard', seed) for seed in list(range(6)) + [15, 22, 24, 25, 32, 34, 54, 64]] + \
+        [('attached', seed) for seed in list(range(4)) + [5, 7, 11, 176]] + [('mapped', seed) for seed in list(range(4)) + [15, 42, 56, 73]]
 # planner variants of tests/test_gpu_fuzz.py, each on 'own' programs whose first handle is large enough for sweeps
 ENV_VARIANTS = [{'QH_RELAYOUT': '0'}, {'QH_WAVE_BITS': '2', 'QH_LANE_VALU': '2'}, {'QH_SEATS': '2', 'QH_WAVE_BITS': '1'}]
 
@@ -161,6 +165,45 @@ def pauli_rotated(vec, n, x, z, k):
   out = np.empty(1 << n, dtype=np.complex128)
   out.real, out.imag = np.where(neg, -re, re), np.where(neg, -im, im)
   return out
+
+
+# ---- Pauli products: what qh_pauli_product_plan must say of a bit map (plan_pauli_product / pauli_product_cut of the engine) ------
+PAULI_PRODUCT_BATCH = native.QH_PAULI_PRODUCT_BATCH
+PAULI_PRODUCT_FEW = 4         # kPauliProdSmallT of pauli_product_plan.h: a run of up to 4 terms takes the instantiation with 4 slots
+PAULI_LANE_PIVOT_MAX = 2      # kPauliLanePivotMax: a PAIR run whose pivot is an item bit <= 2 (inside a 128-byte line) walks items
+PAULI_RUN_KINDS = (native.QH_PAULI_RUN_DIAG, native.QH_PAULI_RUN_PAIR, native.QH_PAULI_RUN_HALF)
+
+
+def pauli_product_main_shape(nloc, bw):
+  """pauli_product_main_shape: a whole chunk of PAIRS; smaller states take k_pauli_product_small"""
+  return nloc - (0 if bw == 128 else 1) - 1 >= PAULI_CHUNK_BITS
+
+
+def pauli_product_rule(nloc, bw, bm, shard, xmasks, zmasks, batch=PAULI_PRODUCT_BATCH):
+  """(terms, runs) of qh_pauli_product_plan from a bit map, as include/qcc_hip.h states it: the terms of pauli_plan_rule in the
+  CALLER'S order, cut into runs by the greedy rule (pauli_product_util.greedy_runs)"""
+  def local(mask):
+    return sum(1 << bm[b] for b in range(len(bm)) if (mask >> b) & 1 and bm[b] < nloc)
+  def held(mask):
+    return sum(1 << (bm[b] - nloc) for b in range(len(bm)) if (mask >> b) & 1 and bm[b] >= nloc)
+  terms = [{'index': t, 'px': local(x), 'pz': local(z), 'neg': _popcount(shard & held(z)) & 1, 'ny': _popcount(int(x) & int(z)) & 3}
+           for t, (x, z) in enumerate(zip(xmasks, zmasks))]
+  runs = [{'first': f, 'count': c, 'px': X, 'kind': k}
+          for f, c, X, k in ppu.greedy_runs([t['px'] for t in terms], batch, 0 if bw == 128 else 1, PAULI_RUN_KINDS)]
+  return terms, runs
+
+
+def pauli_product_walk(nloc, bw, run):
+  """how launch_pauli_run walks a run: 'small' below the main shape; on it 'diag' and 'half' walk items, a PAIR run walks items
+  too ('lane': the partner comes by a lane exchange) where the top bit of its PHYSICAL X >> amp_bits is an item bit <=
+  kPauliLanePivotMax (pauli_pair_in_wave), and pair numbers otherwise ('pair').  The plan does not say which: it says PAIR."""
+  ab = 0 if bw == 128 else 1
+  if not pauli_product_main_shape(nloc, bw):
+    return 'small'
+  if run['kind'] != native.QH_PAULI_RUN_PAIR:
+    return 'diag' if run['kind'] == native.QH_PAULI_RUN_DIAG else 'half'
+  xi = run['px'] >> ab
+  return 'lane' if xi and xi.bit_length() - 1 <= PAULI_LANE_PIVOT_MAX else 'pair'
 
 
 TOL = 1e-12                   # TOL of tests/test_gpu_inner.py: readers that accumulate in double from the stored amplitudes
@@ -473,6 +516,14 @@ class ModelState:
       self.put(d, out)
     return self.norm(d)
 
+  def _pauli_product(self, s):
+    """prod_t (a_t I + b_t P_t) in place, term 0 first, on the handle as stored; x masks are local, so the vector of the global
+    size needs nothing more (a held z bit is the plain sign of the global index)"""
+    h = s['h']
+    self.run(h)
+    self.put(h, ppu.np_pauli_product(self.wide(h), s['a'], s['b'], s['x'], s['z']))
+    return self.norm(h)
+
   # -- layout -------------------------------------------------------------------------------------------------------------------
   def _flush(self, s):
     self.run(s['h'])
@@ -537,6 +588,7 @@ class _Gen:
     self.steps = []
     self.next_slot = 0
     self.refused = 0
+    self.pp_calls = self.pp_rejected = 0                     # k_pauli_product: draws made, draws that missed M <= 8 or the norm range
 
   def live(self):
     return sorted(self.m.v)
@@ -1019,6 +1071,95 @@ class _Gen:
       self.emit({'op': 'copy', 'h': s['new'] if dst is None else dst, 'src': src})
     return True
 
+  PP_BUDGET = 8.0              # M = prod_t (|a_t| + |b_t|) <= 8 on every emitted step: pauli_product_util.bound stays near the real rounding
+
+  def _pp_factor(self, kind, share):
+    """one factor (a, b) of the given kind with log(|a| + |b|) <= share: the angle or the magnitude is shrunk into the share"""
+    rng = self.rng
+    if kind == 'rotation':                                   # exp(-i t P)
+      t = float(rng.uniform(-np.pi, np.pi))
+      while np.log(abs(np.cos(t)) + abs(np.sin(t))) > share:
+        t *= 0.5
+      return complex(np.cos(t)), complex(0, -np.sin(t))
+    if kind == 'imaginary':                                  # exp(-t P): cosh t + |sinh t| = e^|t|
+      t = float(rng.uniform(-0.5, 0.5))
+      while abs(t) > share:
+        t *= 0.5
+      return complex(np.cosh(t)), complex(-np.sinh(t))
+    if kind == 'projector':
+      return 0.5 + 0j, complex(0.5 * (1 - 2 * int(rng.integers(2))))
+    if kind == 'string':
+      return 0j, (1 + 0j, 1j, -1 + 0j, -1j)[int(rng.integers(4))]
+    if kind == 'identity':
+      return 1 + 0j, 0j
+    a, b = complex(*rng.uniform(-1, 1, 2)), complex(*rng.uniform(-1, 1, 2))
+    size = abs(a) + abs(b)
+    if size > np.exp(share):
+      a, b = a * (np.exp(share) / size * (1 - 1e-12)), b * (np.exp(share) / size * (1 - 1e-12))
+    return a, b
+
+  def k_pauli_product(self):
+    """h := F_{n-1} ... F_0 h in place, F_t = a_t I + b_t P_t, on a usable handle in whatever condition the program left it"""
+    rng, m = self.rng, self.m
+    c = [x for x in self.live() if self.usable(x)]
+    if not c:
+      return False
+    queued = [x for x in c if m.q[x]]
+    h = queued[int(rng.integers(len(queued)))] if queued and rng.random() < 0.5 else c[int(rng.integers(len(c)))]      # a queue about half the time
+    n, loc, held = m.n[h], m.local_bits(h), m.held[h]
+    # the bands: the edges are kPauliProdSmallT (the smaller instantiation) and QH_PAULI_PRODUCT_BATCH (a full run)
+    lo, hi = ((0, 0), (1, 1), (2, PAULI_PRODUCT_FEW), (PAULI_PRODUCT_FEW + 1, PAULI_PRODUCT_BATCH),
+              (PAULI_PRODUCT_BATCH + 1, 3 * PAULI_PRODUCT_BATCH))[int(rng.choice(5, p=[0.06, 0.27, 0.22, 0.2, 0.25]))]
+    nt = int(rng.integers(lo, hi + 1))
+    def xmask():
+      # local bits only, never 0.  One time in three of weight 1 or 2: only then can HALF and the in-wave walk occur whatever the
+      # layout -- and half of those among the four lowest local bits, one in four of them the lowest alone: where the local map
+      # is still the identity these are the in-wave walk and (complex64) HALF
+      if rng.random() < 1 / 3:
+        r = rng.random()
+        pool = loc[:1] if r < 0.125 else loc[:4] if r < 0.5 else loc
+        return sum(1 << int(b) for b in rng.choice(pool, size=int(rng.integers(1, min(2, len(pool)) + 1)), replace=False))
+      return sum(1 << int(b) for b in rng.choice(loc, size=int(rng.integers(1, len(loc) + 1)), replace=False))
+    shape = int(rng.integers(4))
+    if shape == 0:                                           # one shared X, diagonal terms interleaved: one run per 8 terms
+      X = xmask()
+      x = [X if rng.random() < 0.6 else 0 for _ in range(nt)]
+    elif shape == 1:                                         # two or three masks alternating: a new run at almost every term
+      pool = [xmask() for _ in range(int(rng.integers(2, 4)))]
+      x = [pool[t % len(pool)] for t in range(nt)]
+    elif shape == 2:
+      x = [xmask() for _ in range(nt)]                       # every mask drawn apart
+    else:
+      x = [0] * nt                                           # diagonal throughout
+    z = [int(rng.integers(1 << n)) if rng.random() < 0.8 else 0 for _ in range(nt)]      # all global bits, held ones included
+    runs = ppu.greedy_runs(x, PAULI_PRODUCT_BATCH, 0, PAULI_RUN_KINDS)                    # (logical masks cut as physical ones are)
+    for f, cnt, X, _ in runs:                                # half the runs that exchange: one z mask with an odd overlap with X ('flip')
+      if X and rng.random() < 0.5:
+        t = f + int(rng.integers(cnt))
+        if not _popcount(X & z[t]) & 1:
+          z[t] ^= X & -X
+    kinds = ('rotation', 'imaginary', 'projector', 'string', 'identity', 'general')
+    p = [0.1, 0.08, 0.07, 0.45, 0.15, 0.15] if nt == 1 else [0.3, 0.15, 0.1, 0.2, 0.05, 0.2]      # one term: the exact paths in 6 of 10
+    a, b, left = [], [], float(np.log(self.PP_BUDGET)) - 1e-9
+    for t in range(nt):                                      # each term an equal share of what is left of log M
+      at, bt = self._pp_factor(kinds[int(rng.choice(6, p=p))], max(left, 0.0) / (nt - t))
+      if nt == 1 and at == 0 and rng.random() < 0.4:         # the b that makes b' = b (-i)^nY (shard sign) == 1: the stored bits
+        neg = sum(v for hb, v in held.items() if (z[0] >> hb) & 1) & 1
+        bt = [u for u in (1 + 0j, 1j, -1 + 0j, -1j) if pauli_coef(u, _popcount(x[0] & z[0]), neg) == 1][0]
+      left -= float(np.log(abs(at) + abs(bt)))
+      a.append(at)
+      b.append(bt)
+    a, b = np.asarray(a, dtype=np.complex128).reshape(nt), np.asarray(b, dtype=np.complex128).reshape(nt)
+    self.pp_calls += 1
+    if nt:
+      trial = ppu.np_pauli_product(m.wide(h), a, b, x, z)
+      if not (ppu.magnitude(a, b) <= self.PP_BUDGET and 1e-3 <= float(np.vdot(trial, trial).real) <= 100):
+        self.pp_rejected += 1                                # (a zero result, of projectors mostly, is rejected here too)
+        return False
+    # (emit follows the step with a scale where the norm has left [0.25, 4])
+    self.emit({'op': 'pauli_product', 'h': h, 'a': a, 'b': b, 'x': x, 'z': z, 'norm': bool(rng.integers(2))})
+    return True
+
   def k_flush(self):
     h = self.pick(lambda x: self.m.q[x] > 0) or self.pick()
     self.emit({'op': 'flush', 'h': h})
@@ -1048,17 +1189,33 @@ class _Gen:
       return False
     loc = m.local_bits(h)
     whats = ['matrix_twice', 'mux_target_selected', 'marginal_twice', 'sample_descending', 'copy_self', 'axpby_self',
-             'extend_basis', 'release_value', 'perm_not_bijection', 'perm_control_in_register', 'pauli_sum_self', 'pauli_sum_bad_qubit']
+             'extend_basis', 'release_value', 'perm_not_bijection', 'perm_control_in_register', 'pauli_sum_self', 'pauli_sum_bad_qubit',
+             'pauli_product_nonfinite', 'pauli_product_bad_qubit']
     if m.held[h]:
       whats.append('perm_register_held')                     # (a register bit on the shard index: nothing is flushed)
       whats.append('pauli_sum_x_held')                       # (an x bit there: nothing runs, no handle comes into being)
+      whats.append('pauli_product_x_held')                   # (likewise: the whole list is checked before anything is flushed)
     what = whats[int(rng.integers(len(whats)))]
+    if m.held[h] and rng.random() < 0.4:                     # (the three that only a shard can draw, and few programs are shards)
+      what = whats[len(whats) - 3 + int(rng.integers(3))]
+    if what.startswith('pauli_product_') and rng.random() < 0.5:
+      # half of them on a handle with a burst queued, where the pool has one: the checks of a refused step then show that nothing was flushed
+      c = [x for x in self.live() if m.q[x] and m.nloc(x) >= 2 and bool(m.held[x]) == bool(m.held[h])]
+      if c:
+        h = c[int(rng.integers(len(c)))]
+        loc = m.local_bits(h)
     code = native.QH_ERR_SAME_QUBIT if what in ('matrix_twice', 'mux_target_selected', 'marginal_twice', 'perm_control_in_register') \
-        else native.QH_ERR_NONLOCAL if what in ('perm_register_held', 'pauli_sum_x_held') \
-        else native.QH_ERR_BAD_QUBIT if what == 'pauli_sum_bad_qubit' else native.QH_ERR_ARG
+        else native.QH_ERR_NONLOCAL if what in ('perm_register_held', 'pauli_sum_x_held', 'pauli_product_x_held') \
+        else native.QH_ERR_BAD_QUBIT if what in ('pauli_sum_bad_qubit', 'pauli_product_bad_qubit') else native.QH_ERR_ARG
     s = {'op': 'refused', 'h': h, 'what': what, 'code': code, 'bits': [int(loc[0]), int(loc[1])]}
-    if what in ('perm_register_held', 'pauli_sum_x_held'):
+    if what in ('perm_register_held', 'pauli_sum_x_held', 'pauli_product_x_held'):
       s['held'] = int(sorted(m.held[h])[int(rng.integers(len(m.held[h])))])
+    if what.startswith('pauli_product_'):
+      s['nbits'], s['queued'] = m.n[h], bool(m.q[h])
+      s['in_x'] = bool(rng.integers(2))                      # bad_qubit: the bit beyond the register in the x mask or in the z mask
+      if what == 'pauli_product_nonfinite':                  # NaN or an infinity in one of the four numbers of term 1 or 2 of 3
+        s['term'], s['slot'], s['value'] = int(rng.integers(1, 3)), int(rng.integers(4)), ('nan', 'inf', '-inf')[int(rng.integers(3))]
+        s['says'] = f"term {s['term']} "                      # qh_last_error names the first offending term
     if what.startswith('pauli_sum_'):
       s['nbits'] = m.n[h]
       o = self.partner(h) if what != 'pauli_sum_self' else None
@@ -1069,7 +1226,7 @@ class _Gen:
     return True
 
   WEIGHTS = {'gates': 9.0, 'close': 0.6, 'refused': 0.8, 'remap': 1.6, 'flush': 0.7, 'clone': 1.3, 'inner': 1.8, 'axpby': 1.8, 'copy': 1.3,
-             'pauli_sum': 2.5}
+             'pauli_sum': 2.5, 'pauli_product': 2.5}
 
   def run(self):
     self.start()
@@ -1089,6 +1246,12 @@ def gen_program(seed, bw, mode='own'):
   """the steps of program `seed` at width bw in mode 'own' | 'attached' | 'mapped' | 'shard': the same list every time"""
   assert bw in (128, 64) and mode in ('own', 'attached', 'mapped', 'shard')
   return _Gen(seed, bw, mode).run()
+
+
+def gen_program_counted(seed, bw, mode='own'):
+  """(the steps of gen_program, draws of k_pauli_product, draws among them rejected because M or the trial's norm left its range)"""
+  g = _Gen(seed, bw, mode)
+  return g.run(), g.pp_calls, g.pp_rejected
 
 
 def describe(s):
@@ -1362,6 +1525,15 @@ class _Runner:
         'pauli_sum_bad_qubit': lambda out: st.apply_pauli_sum([1.0, 0.5], [1 << a, 0], [0, 1 << s.get('nbits', 0)], out=out),
         'pauli_sum_x_held': lambda out: st.apply_pauli_sum([0.5, 1.0], [1 << a, (1 << s.get('held', 0)) | (1 << b)], [0, 0], out=out),
     }
+    if s['what'].startswith('pauli_product_'):               # three terms, the offending one never the first
+      bad, high = float(s.get('value', 'nan')), 1 << s['nbits']
+      ab = [[0.6, 0.0, 0.0, -0.8] for _ in range(3)]
+      ab[s.get('term', 1)][s.get('slot', 0)] = bad
+      ok_x, ok_z = [1 << a, 0, 1 << b], [1 << b, 1 << a, 0]
+      calls['pauli_product_nonfinite'] = lambda: st.apply_pauli_product([complex(*t[:2]) for t in ab], [complex(*t[2:]) for t in ab], ok_x, ok_z)
+      calls['pauli_product_bad_qubit'] = lambda: st.apply_pauli_product([0.6] * 3, [-0.8j] * 3, ok_x[:2] + [ok_x[2] | (high if s['in_x'] else 0)],
+                                                                        ok_z[:2] + [ok_z[2] | (0 if s['in_x'] else high)], norm=True)
+      calls['pauli_product_x_held'] = lambda: st.apply_pauli_product([0.6] * 3, [-0.8j] * 3, ok_x[:2] + [ok_x[2] | (1 << s.get('held', 0))], ok_z)
     # a refused Pauli sum: into a new handle (none may come into being) and, where the pool has one, into an existing one
     outs = [None] + ([self.dev[s['other']]] if s.get('other') is not None else []) if s['what'].startswith('pauli_sum_') else [()]
     for out in outs:
@@ -1369,6 +1541,7 @@ class _Runner:
         made = calls[s['what']](*(() if out == () else (out,)))
       except native.QhError as e:
         self.need(e.code == s['code'], f'error code {e.code}, expected {s["code"]}')
+        self.need(s.get('says', '') in str(e), f'the error message does not say "{s.get("says")}": {e}')
         continue
       if s['what'].startswith('pauli_sum_') and made is not None and made is not out and hasattr(made, 'close'):
         made.close()                                         # (the handle that should not exist)
@@ -1408,6 +1581,9 @@ class _Runner:
         self.need(not _plans_relayout(self.dev[x]), f'handle {x}: the queued burst is planned with relayout sweeps, its relayout mode is off')
     if op == 'pauli_sum':
       self.run_pauli_sum(s, q_before, bm_before)
+      return
+    if op == 'pauli_product':
+      self.run_pauli_product(s, q_before[h], bm_before[h])
       return
     k_before = {x: self.kernels(x) for x in involved}
     n0 = {x: self.dev[x].marginal([]).tobytes() for x in involved} if quiet and op in READERS + ('inner',) else {}
@@ -1669,6 +1845,120 @@ class _Runner:
            'relaid': not quiet and moved and not _canonical(bm_src, st.nbits),
            'px0': bool(ab) and any(t['px'] & 1 for t in terms), 'pz0': bool(ab) and any(t['pz'] & 1 for t in terms)}
     self.check.events.append((self.i, 'pauli_sum', not _canonical(bm_src, st.nbits), not quiet, None, rec))
+
+  def run_pauli_product(self, s, queued, bm_before):
+    """One 'pauli_product' step, in place on h in whatever condition the program left it: every check of _apply_checked of
+    tests/test_gpu_pauli_product.py and those of run_pauli_sum that apply.  A step is QUIET where h has nothing queued: then
+    the plan, the bit map, the stats and the exact cases are held exactly, and the call is repeated from the same start
+    (restored from a clone) for the same norm2 bits and the same amplitude bytes."""
+    m, bw = self.m, self.bw
+    h, st = s['h'], self.dev[s['h']]
+    a, b, xs, zs = s['a'], s['b'], s['x'], s['z']
+    nt, n, nloc = len(xs), m.n[h], st.nbits
+    quiet = queued == 0
+    mag = ppu.magnitude(a, b)                               # M
+    mine = mine_of(n, m.held[h]).astype(np.int64)
+    local = sum(1 << x for x in m.local_bits(h))
+    plan0 = st.pauli_product_plan(xs, zs) if quiet else None      # asked right before the call
+    keep = st.clone() if quiet and nt else None              # the start, for the repeat
+    try:
+      stats0 = st.stats()
+      try:
+        n2 = st.apply_pauli_product(a, b, xs, zs, norm=s['norm'])
+      except native.QhError as e:
+        self.fail(f'the engine refused a valid step: {e}')
+      stats1 = st.stats()
+      terms, runs = st.pauli_product_plan(xs, zs)             # right behind the call: the layout the call's own flush left
+      bm = _bitmap(st)
+      m.run(h)
+      before = m.wide(h)                                      # quiet: what the handle held, bit for bit; else the model behind the burst
+      want_n2 = m.step(s)
+      for mdl in (self.chain, self.chain_r):
+        if mdl is not None:
+          mdl.step(s)
+      self.need(_pending(st) == 0, f'{_pending(st)} gates pending behind a Pauli product')
+      # -- bit map: as the call found it; behind a queue it moves only where the relayout mode is on -----------------------------
+      moved = bm != bm_before
+      if quiet:
+        self.need(not moved, 'the bit map moved in a step that had nothing to flush')
+      elif moved:
+        self.need(m.mode[h] == 1, f'a flush re-laid the handle out, its relayout mode is {m.mode[h]}')
+        self.check.relaid += 1
+      self.need({x for x, p in enumerate(bm) if p >= nloc} == set(m.held[h]), 'the held bits changed')
+      self.check_ptr(h)
+      # -- the plan, held to the bit map by the rule stated in Python ------------------------------------------------------------------
+      want_plan = pauli_product_rule(nloc, bw, bm, self.shard[h], xs, zs)
+      self.need((terms, runs) == want_plan, f'qh_pauli_product_plan says {(terms, runs)}, the rule on bit map {bm} gives {want_plan}')
+      if quiet:
+        self.need(plan0 == (terms, runs), 'the plan asked before a quiet call differs from the plan asked behind it')
+      # -- stats of a quiet step, as the header gives them from the plan ----------------------------------------------------------------
+      sb = (1 << nloc) * (16 if bw == 128 else 8)
+      if quiet:
+        grow = {'gates_submitted': nt, 'kernels_launched': len(runs), 'bytes_swept': 2 * len(runs) * sb, 'bytes_algorithmic': 2 * len(runs) * sb}
+        for k in stats0:
+          self.need(stats1[k] - stats0[k] == grow.get(k, 0), f'{k} grew by {stats1[k] - stats0[k]}, the header says {grow.get(k, 0)} ({len(runs)} runs)')
+      # -- amplitudes ---------------------------------------------------------------------------------------------------------------------
+      after = self.read(h)
+      self.need(_bitmap(st) == bm, 'reading the handle through a clone moved its bit map')
+      want = m.wide(h)                                        # np_pauli_product of what the handle held
+      amax = float(np.max(np.abs(before)))
+      bound = ppu.bound(bw, a, b, amax, len(runs))
+      if not quiet:
+        bound += mag * amp_tol(bw)                            # the burst's own rounding passes through the factors and grows by at most M
+      bps = [pauli_coef(b[t['index']], t['ny'], t['neg']) for t in terms]
+      unit = pauli_unit(bps[0]) if nt == 1 and complex(a[0]) == 0 else None
+      ident = nt == 1 and complex(a[0]) == 1 and complex(b[0]) == 0
+      signs = lambda got, exp: int(np.sum(np.signbit(got.view(np.float64)) != np.signbit(exp.view(np.float64))))      # noqa: E731
+      if quiet and nt == 0:
+        self.need(after.tobytes() == before.tobytes(), 'no terms: the amplitudes changed')
+      elif quiet and unit is not None:                        # the stored bits moved: the same bytes, the sign of a zero included
+        exp = np.zeros(1 << n, dtype=np.complex128)
+        exp[mine] = pauli_rotated(before, n, xs[0], zs[0] & local, unit)[mine]
+        self.need(after.tobytes() == exp.tobytes(), f'one string with a == 0 and b\' = i^{unit}: not the stored bits moved '
+                  f'(max diff {float(np.max(np.abs(after - exp))):.3e}, {signs(after, exp)} signs differ)')
+      elif quiet and ident:
+        self.need(after.tobytes() == before.tobytes(), f'the factor (1, 0): not every bit as it was (max diff '
+                  f'{float(np.max(np.abs(after - before))):.3e}, {signs(after, before)} signs differ)')
+      else:
+        err = float(max(np.max(np.abs(after.real - want.real)), np.max(np.abs(after.imag - want.imag))))
+        self.need(err <= bound, f'amplitudes off by {err:.3e} per component (bound {bound:.3e}, {len(runs)} runs, M = {mag:.3g})')
+      m.put(h, after)
+      self.check_raw(h, after, bm)
+      # -- norm2 --------------------------------------------------------------------------------------------------------------------------
+      if s['norm']:
+        n2_np = float(np.vdot(after, after).real)
+        self.need(abs(n2 - n2_np) <= 1e-12 * n2_np, f'norm2 {n2!r}, the amplitudes read back give {n2_np!r}')
+        n2_tol = 4 * mag * amax * bound * (1 << nloc) + 1e-12 * want_n2      # (as _apply_checked of tests/test_gpu_pauli_product.py)
+        self.need(abs(n2 - want_n2) <= n2_tol, f'norm2 {n2!r}, the model gives {want_n2!r} (tolerance {n2_tol:.3e})')
+      else:
+        self.need(n2 is None, f'norm2 was not asked for, the call returned {n2!r}')
+      # -- the same start again: the same bits --------------------------------------------------------------------------------------------
+      if keep is not None:
+        st.copy_from(keep)
+        self.need(_bitmap(st) == bm, 'copy_from a clone of the handle itself moved the bit map')
+        again = st.apply_pauli_product(a, b, xs, zs, norm=s['norm'])
+        self.need(again == n2, f'norm2 {n2!r}, from the same call repeated {again!r}')
+        self.need(_bitmap(st) == bm and _pending(st) == 0, 'the repeated call moved the bit map or queued something')
+        self.need(self.read(h).tobytes() == after.tobytes(), 'the same call from the same start gave other amplitude bytes')
+    finally:
+      if keep is not None:
+        keep.close()
+    # -- the record ---------------------------------------------------------------------------------------------------------------------
+    ab = 0 if bw == 128 else 1
+    rec_runs = []
+    for r in runs:
+      tl = terms[r['first']:r['first'] + r['count']]
+      one = tl[0]['index'] if r['count'] == 1 else None
+      exact = None if one is None else 'string' if complex(a[one]) == 0 and pauli_unit(bps[r['first']]) is not None \
+          else 'identity' if complex(a[one]) == 1 and complex(b[one]) == 0 else None
+      rec_runs.append({'kind': r['kind'], 'walk': pauli_product_walk(nloc, bw, r), 'slots': 'few' if r['count'] <= PAULI_PRODUCT_FEW else 'many',
+                       'exact': exact, 'flip': any(_popcount(r['px'] & t['pz']) & 1 for t in tl),
+                       'mixed': any(t['px'] for t in tl) and not all(t['px'] for t in tl), 'px0': bool(ab) and bool(r['px'] & 1)})
+    rec = {'nloc': nloc, 'main': pauli_product_main_shape(nloc, bw), 'nruns': len(runs), 'zero': nt == 0, 'norm': bool(s['norm']), 'runs': rec_runs,
+           'shard': bool(m.held[h]), 'held_z': any((z >> hb) & 1 for z in zs for hb in m.held[h]), 'neg': any(t['neg'] for t in terms),
+           'queued': not quiet, 'relayout_on': m.mode[h] == 1, 'relaid': not quiet and moved and not _canonical(bm, nloc),
+           'fixed': h in self.fixed_ptr, 'pz0': bool(ab) and any(t['pz'] & 1 for t in terms)}
+    self.check.events.append((self.i, 'pauli_product', not _canonical(bm, nloc), not quiet, None, rec))
 
   def perm_record(self, s, queued, bm_before):
     """What qh_perm_plan says of the step's bits right behind the call: the call does not move the bit map, so this is the
@@ -2252,3 +2542,104 @@ class NumpyDevice:
 
   def _pauli_norm2(self, stored, unrounded):
     return float(np.vdot(stored, stored).real)
+
+  # -- Pauli products: run by run as the header describes them, through hooks a mutant overrides one at a time ----------------------
+  def pauli_product_plan(self, xmasks, zmasks):
+    xs, zs = [int(x) for x in xmasks], [int(z) for z in zmasks]
+    self._pauli_check('pauli_product_plan', None, xs, zs)
+    return pauli_product_rule(self.nbits, self.bit_width, self.bm, self.shard, xs, zs, self._pprod_batch())
+
+  def apply_pauli_product(self, a, b, xmasks, zmasks, norm=False):
+    av, bv = [complex(v) for v in a], [complex(v) for v in b]
+    xs, zs = [int(x) for x in xmasks], [int(z) for z in zmasks]
+    self._pprod_check(av, bv, xs, zs, len(xs))               # the WHOLE list, before anything is flushed
+    self._pprod_enter(len(xs))
+    self._pprod_check(av, bv, xs, zs, len(xs), late=True)
+    if not xs:                                               # nothing is launched; norm2 is the reader's
+      self.kernels += self._pprod_zero_kernels()
+      return self._model(self._read(0)).norm(0) if norm else None      # (the reader's sum; the call counts no kernel)
+    terms, _ = self.pauli_product_plan(xs, zs)
+    terms = self._pprod_order_list(terms)
+    runs = ppu.greedy_runs([t['px'] for t in terms], self._pprod_batch(), 0 if self.bit_width == 128 else 1, PAULI_RUN_KINDS)
+    n, mine = self.nbits_global, self._lidx()
+    local = sum(1 << q for q in range(n) if self.bm[q] < self.nbits)
+    vec = exact = self.to_logical()
+    first_stored = None
+    for first, count, _, _ in runs:
+      tl = terms[first:first + count]
+      t0 = tl[0]['index']
+      bps = [pauli_coef(bv[t['index']], self._pprod_ny(t), self._pprod_neg(t)) for t in tl]
+      if count == 1 and av[t0] == 0 and pauli_unit(bps[0]) is not None:      # the stored bits moved, negated and / or swapped
+        vec = self._pprod_unit(vec, pauli_rotated(vec, n, xs[t0], zs[t0] & local, pauli_unit(bps[0])))
+      elif count == 1 and av[t0] == 1 and bv[t0] == 0:                       # every bit as it was
+        vec = self._pprod_identity(vec, xs[t0], zs[t0] & local)
+      else:
+        for t, bp in self._pprod_order_run(list(zip(tl, bps))):
+          vec = av[t['index']] * vec + bp * self._pprod_partner(vec, xs[t['index']], zs[t['index']] & local)
+      exact = vec
+      vec = self._round(vec)                                  # rounded once per run to the handle's width
+      if first_stored is None:
+        first_stored = vec[mine]
+    keep = np.zeros(1 << n, dtype=np.complex128)
+    keep[mine] = vec[mine]
+    self.store(keep)
+    self._pprod_layout()
+    sb = (1 << self.nbits) * (16 if self.bit_width == 128 else 8)
+    self.submitted += len(xs)
+    self.kernels += len(runs)
+    self.swept += self._pprod_bytes(len(runs), sb)
+    self.algorithmic += self._pprod_bytes(len(runs), sb)
+    return self._pprod_norm2(self.phys.astype(np.complex128), exact[mine], first_stored) if norm else None
+
+  def _pprod_check(self, av, bv, xs, zs, upto, late=False):
+    if late:
+      return
+    for t in range(upto):
+      if not all(np.isfinite(v) for v in (av[t].real, av[t].imag, bv[t].real, bv[t].imag)):
+        raise native.QhError(native.QH_ERR_ARG, f'apply_pauli_product: term {t} has a non-finite coefficient')
+    self._pauli_check('apply_pauli_product', None, xs[:upto], zs[:upto])
+
+  def _pprod_enter(self, nterms):
+    self.flush()                                             # a barrier: what is queued runs first
+
+  def _pprod_batch(self):
+    return PAULI_PRODUCT_BATCH
+
+  def _pprod_zero_kernels(self):
+    return 0
+
+  def _pprod_order_list(self, terms):
+    return terms                                             # the caller's order is never changed
+
+  def _pprod_order_run(self, pairs):
+    return pairs
+
+  def _pprod_ny(self, term):
+    return term['ny']
+
+  def _pprod_neg(self, term):
+    return term['neg']
+
+  def _pprod_unit(self, vec, moved):
+    return moved
+
+  def _pprod_identity(self, vec, x, z):
+    return vec
+
+  def _pprod_own_index(self, idx, x):
+    return idx                                               # the index whose z parity signs what arrives at idx: its own
+
+  def _pprod_partner(self, vec, x, z):
+    """(-1)^popcount(i & z) vec[i ^ x]"""
+    idx = np.arange(vec.size, dtype=np.uint64)
+    sign = 1.0 - 2.0 * pauli_util.parity(self._pprod_own_index(idx, x), z).astype(np.float64)
+    return sign * vec[(idx ^ np.uint64(x)).astype(np.int64)]
+
+  def _pprod_layout(self):
+    pass                                                     # the bit map is as the call found it
+
+  def _pprod_bytes(self, nruns, shard_bytes):
+    return 2 * nruns * shard_bytes
+
+  def _pprod_norm2(self, stored, unrounded, first_stored):
+    return float(np.vdot(stored, stored).real)               # of the final amplitudes as stored, summed by the last run

@@ -11,17 +11,23 @@ non-identity local map that its own flush had left.  Of the Pauli-sum operators 
 qh_get_bitmap said right behind each call: at both widths k_pauli_small and k_pauli_batch ran, the latter in all four
 instantiation classes (few or many term slots, one x mask or several) and with an accumulating batch, on a shard with the shard
 sign set, on a non-identity local map that the call's own flush had left, into a destination whose queue was dropped and into
-one that held NaN; at complex64 with physical bit 0 in an x mask and in a z mask.  The CPU table
+one that held NaN; at complex64 with physical bit 0 in an x mask and in a z mask.  Of the Pauli products it reads what the real
+qh_pauli_product_plan and qh_get_bitmap said right behind each call: at both widths k_pauli_product_small ran and k_pauli_product
+in each of its walks (items of a diagonal run, items with a lane exchange, pair numbers, and at complex64 the two halves of an
+item), each with few and with many term slots, on lists of three runs or more, with norm2 asked and not asked on several runs,
+with the partner's sign flipped, with diagonal and exchanging terms in one run, on both exact paths, with no terms behind a queue,
+on a shard with the shard sign set, on a non-identity local map that the call's own flush had left, on an attached and on a
+host-mapped handle; at complex64 with physical bit 0 in the X of a pair or lane run and in a z mask.  The CPU table
 (tests/test_program_fuzz_cpu.py) only predicts this.
 
 The figures recorded when the file was added (time, chain errors per program) are in HISTORY.md, section T1; those of the
-register permutations in section T2, those of the Pauli-sum operators in section T3.
+register permutations in section T2, those of the Pauli-sum operators in section T3, those of the Pauli products in section T4.
 """
 import pytest
 
 from qcc_amd import native
 from tests import program_model as pm
-from tests.test_program_fuzz_cpu import pauli_counts
+from tests.test_program_fuzz_cpu import PRODUCT_WALKS, pauli_counts, pauli_product_counts
 
 pytestmark = pytest.mark.gpu
 
@@ -29,12 +35,15 @@ SEEN = {'own': 0, 'own_big': 0, 'own_big_relaid': 0, 'paths': set(), 'gather_rel
 PERMS = []                    # (mode, width, the record of a 'perm' step: program_model._Runner.perm_record), fixed programs only
 PAULIS = []                   # (mode, width, non-identity local map, the record of a 'pauli_sum' step: _Runner.run_pauli_sum), likewise
 VARIANT_PAULIS = {}           # planner variant (its index in pm.ENV_VARIANTS) -> 'pauli_sum' steps on the main shape under it
+PRODUCTS = []                 # (mode, width, non-identity local map, the record of a 'pauli_product' step: _Runner.run_pauli_product), fixed programs only
+VARIANT_PRODUCTS = {}         # planner variant -> 'pauli_product' steps on the main shape under it
 # the 'own' programs that run again under a planner variant: (seed, width) whose first handle has sweeps that re-lay out and
 # which hold a register permutation (checked below, so that a change of the generator cannot quietly empty the list); of
 # the four under QH_RELAYOUT=0 the last two were added for a register wide enough for the gather path, there through a
 # temporary on a handle that owns its memory.  Under each variant at least one program holds a Pauli sum on the main shape
-# (checked by the closing item): own-18 at complex64 no longer holds a 'perm' step and gave way to own-92.
-VARIANT_PROGRAMS = [(env, seed, bw) for env, pair in zip(pm.ENV_VARIANTS, ([(1, 128), (4, 64), (8, 128), (15, 64)], [(15, 128), (92, 64)], [(6, 128), (8, 64)]))
+# and a Pauli product on the main shape (checked by the closing item): own-18 at complex64 no longer held a 'perm' step when
+# 'pauli_sum' became a kind and gave way to own-92, which lost its own when 'pauli_product' did and gave way to own-11.
+VARIANT_PROGRAMS = [(env, seed, bw) for env, pair in zip(pm.ENV_VARIANTS, ([(1, 128), (4, 64), (8, 128), (15, 64)], [(15, 128), (11, 64)], [(6, 128), (8, 64)]))
                     for seed, bw in pair]
 
 
@@ -51,6 +60,7 @@ def test_program(mode, seed, bw):
   prog, check = _run(mode, seed, bw)
   PERMS.extend((mode, bw, e[5]) for e in check.events if e[1] == 'perm')
   PAULIS.extend((mode, bw, e[2], e[5]) for e in check.events if e[1] == 'pauli_sum')
+  PRODUCTS.extend((mode, bw, e[2], e[5]) for e in check.events if e[1] == 'pauli_product')
   if mode == 'own':
     SEEN['own'] += 1
     SEEN['paths'] |= {e[4] for e in check.events if e[4] is not None}
@@ -68,6 +78,7 @@ def test_program_under_planner_variants(env, seed, bw, monkeypatch):
   assert prog[0]['nloc'] >= pm.PERMUTED_FROM and any(s['op'] == 'perm' for s in prog)
   which = pm.ENV_VARIANTS.index(env)
   VARIANT_PAULIS[which] = VARIANT_PAULIS.get(which, 0) + sum(1 for e in check.events if e[1] == 'pauli_sum' and e[5]['main'])
+  VARIANT_PRODUCTS[which] = VARIANT_PRODUCTS.get(which, 0) + sum(1 for e in check.events if e[1] == 'pauli_product' and e[5]['main'] and not e[5]['zero'])
   if env.get('QH_RELAYOUT') == '0':
     assert check.relaid == 0                                # no flush re-laid a handle out: clones and siblings decide as told
     perms = [e[5] for e in check.events if e[1] == 'perm']
@@ -109,3 +120,16 @@ def test_zz_relayout_and_inner_paths_were_met():
       assert n.get(k, 0) >= 1, (bw, k, n)
   print(f'pauli_sum steps on the main shape under the planner variants: {VARIANT_PAULIS}')
   assert all(VARIANT_PAULIS.get(which, 0) >= 1 for which in range(len(pm.ENV_VARIANTS))), VARIANT_PAULIS
+  # the Pauli products, from what the real qh_pauli_product_plan and qh_get_bitmap said right behind each call
+  for bw in (128, 64):
+    n = pauli_product_counts([(mode, permuted, r) for mode, w, permuted, r in PRODUCTS if w == bw], bw)
+    print(f'pauli_product steps at complex{bw}: {n}')
+    walks = [f'main shape: {walk} walk, {slots} term slots' for walk in PRODUCT_WALKS[:4 if bw == 64 else 3] for slots in ('few', 'many')]
+    for k in ['k_pauli_product_small shape', 'main shape'] + walks + \
+             ['three or more runs', 'several runs, norm2 asked', 'several runs, norm2 not asked', 'a run with flip set', 'a run with flip set on the main shape',
+              'a run mixing diagonal and exchanging terms', 'exact path: one unit string', 'exact path: the factor (1, 0)', 'zero terms behind a queue',
+              'shard: main shape with neg set', 'on a non-identity local map its own flush left', 'on an attached handle', 'on a host-mapped handle'] + \
+             (['complex64: physical bit 0 in X of a pair or lane run', 'complex64: physical bit 0 in a z mask'] if bw == 64 else []):
+      assert n.get(k, 0) >= 1, (bw, k, n)
+  print(f'pauli_product steps on the main shape under the planner variants: {VARIANT_PRODUCTS}')
+  assert all(VARIANT_PRODUCTS.get(which, 0) >= 1 for which in range(len(pm.ENV_VARIANTS))), VARIANT_PRODUCTS

@@ -8,13 +8,13 @@ from tests import program_model as pm
 from tests.fake_device import np_marginal
 
 WIDTHS = (128, 64)
-_PROGRAMS, _CHECKS = {}, {}
+_PROGRAMS, _CHECKS, _DRAWS = {}, {}, {}
 
 
 def program(mode, seed, bw):
   key = (mode, seed, bw)
   if key not in _PROGRAMS:
-    _PROGRAMS[key] = pm.gen_program(seed, bw, mode)
+    _PROGRAMS[key], *_DRAWS[key] = pm.gen_program_counted(seed, bw, mode)
   return _PROGRAMS[key]
 
 
@@ -41,6 +41,30 @@ def test_generator_is_deterministic_and_sized():
       if x['op'] == 'gates':
         assert 5 <= len(x['gates']) <= 40 and all(np.array_equal(g, h) for (_, _, g), (_, _, h) in zip(x['gates'], y['gates']))
   assert pm.gen_program(0, 64, 'mapped')[0]['nloc'] <= 12
+
+
+def test_pauli_product_draws_keep_their_conditions_and_are_rarely_rejected():
+  """every emitted 'pauli_product' step has M = prod (|a_t| + |b_t|) <= 8 (pauli_product_util.bound stays near the real rounding;
+  the norm range is the generator's own trial), and the budgeted draw misses M or the norm range in at most one call in ten:
+  over the fixed programs and seeds 0..199 (the four modes in turn) at both widths"""
+  modes = ('own', 'shard', 'attached', 'mapped')
+  keys = [(mode, seed, bw) for bw in WIDTHS for mode, seed in pm.FIXED]
+  keys += [key for key in ((modes[seed % 4], seed, bw) for seed in range(200) for bw in WIDTHS) if key not in keys]
+  calls = rejected = steps = 0
+  for key in keys:
+    if key in _PROGRAMS:
+      prog = program(*key)
+      c, r = _DRAWS[key]
+    else:
+      prog, c, r = pm.gen_program_counted(key[1], key[2], key[0])      # (not kept: 400 programs)
+    calls, rejected = calls + c, rejected + r
+    for s in prog:
+      if s['op'] == 'pauli_product':
+        steps += 1
+        assert len(s['a']) == len(s['b']) == len(s['x']) == len(s['z']) <= 3 * pm.PAULI_PRODUCT_BATCH
+        assert pm.ppu.magnitude(s['a'], s['b']) <= 8.0, (key, pm.describe(s))
+  print(f'k_pauli_product: {calls} draws in {len(keys)} programs, {rejected} rejected ({rejected / calls:.2%}), {steps} steps emitted')
+  assert steps == calls - rejected and 10 * rejected <= calls
 
 
 def test_fixed_programs_pass_on_the_numpy_device():
@@ -301,14 +325,145 @@ class PauliNormUnrounded(pm.NumpyDevice):
     return float(np.vdot(unrounded, unrounded).real) if self.dtype == np.complex64 else super()._pauli_norm2(stored, unrounded)
 
 
+# -- Pauli products.  Which check of _Runner.run_pauli_product catches which (the mutants named "only" pass every fixed program once
+#    that one check is deleted; each deletion was tried once, HISTORY.md T4)
+#      31, 32  the amplitudes within pauli_product_util.bound: a run whose terms do not commute, a list whose x masks alternate
+#      33, 34  the amplitudes (33 on a shard whose held z bits have odd parity, 34 where x & z has an odd number of bits)
+#      35      the amplitudes of a run with an exchanging term whose z mask shares an odd number of bits with X
+#      36      the amplitudes behind a step with a queue (bound + M _amp_tol)
+#      37      the pending count of a REFUSED step on a handle with a queue: the list is checked whole before anything is flushed
+#      38      the bit map: it may not move in a step with nothing to flush, nor behind a flush whose relayout mode is off; without
+#              those checks, the plan asked before a quiet call against the plan asked behind it
+#      39      the plan against the run rule (the engine launches from the plan), then the stats
+#      40      only the stats of a quiet step: kernels_launched + 0 for no terms ("only": passes once that check is deleted)
+#      41      the pending count behind a step of no terms on a handle with a queue
+#      42, 43  only the BYTES of a quiet one-term step on an exact path: equal as numbers, the bound and norm2 see nothing
+#      44      only norm2 against the amplitudes read back, 1e-12 relative (complex64)
+#      45      norm2 against the amplitudes read back on a list of several runs; without that check, norm2 against the model
+#      46      only the stats of a quiet step of several runs: both byte counters + 2 x the shard's bytes PER RUN
+class ProductTermsReversed(pm.NumpyDevice):
+  """31. apply_pauli_product applies the terms of a run in reverse order"""
+  def _pprod_order_run(self, pairs):
+    return pairs[::-1]
+
+
+class ProductSortsByX(pm.NumpyDevice):
+  """32. apply_pauli_product sorts the terms stably by x mask first, as the sum does"""
+  def _pprod_order_list(self, terms):
+    return sorted(terms, key=lambda t: t['px'])
+
+
+class ProductIgnoresHeldZ(pm.NumpyDevice):
+  """33. apply_pauli_product ignores the z bits the shard index holds (no shard sign)"""
+  def _pprod_neg(self, term):
+    return 0
+
+
+class ProductPlusI(pm.NumpyDevice):
+  """34. apply_pauli_product multiplies by (+i)^nY instead of (-i)^nY"""
+  def _pprod_ny(self, term):
+    return -term['ny'] & 3
+
+
+class ProductNeverFlips(pm.NumpyDevice):
+  """35. the partner's sign is never flipped: both amplitudes of a pair take the sign of the one whose pivot bit is clear"""
+  def _pprod_own_index(self, idx, x):
+    if not x:
+      return idx
+    pivot = np.uint64(1 << (int(x).bit_length() - 1))
+    return np.where(idx & pivot != 0, idx ^ np.uint64(x), idx)
+
+
+class ProductBeforeItsQueue(pm.NumpyDevice):
+  """36. apply_pauli_product works before what is queued has run (the queue runs behind the call)"""
+  def apply_pauli_product(self, a, b, xmasks, zmasks, norm=False):
+    self._pprod_enter = lambda nterms: None
+    try:
+      res = super().apply_pauli_product(a, b, xmasks, zmasks, norm)
+    finally:
+      del self._pprod_enter
+    self.flush()
+    return res
+
+
+class ProductChecksLateTermsLate(pm.NumpyDevice):
+  """37. apply_pauli_product checks the first term, flushes, and refuses a bad later term only then"""
+  def _pprod_check(self, av, bv, xs, zs, upto, late=False):
+    super()._pprod_check(av, bv, xs, zs, upto if late else min(upto, 1))
+
+
+class ProductCanonicalises(pm.NumpyDevice):
+  """38. apply_pauli_product leaves the local bits in canonical order"""
+  def _pprod_layout(self):
+    self._canonicalize()
+
+
+class ProductRunsOf16(pm.NumpyDevice):
+  """39. apply_pauli_product cuts its runs every 16 terms"""
+  def _pprod_batch(self):
+    return 16
+
+
+class ProductZeroTermsCountAKernel(pm.NumpyDevice):
+  """40. apply_pauli_product with no terms counts a kernel"""
+  def _pprod_zero_kernels(self):
+    return 1
+
+
+class ProductZeroTermsDoNotFlush(pm.NumpyDevice):
+  """41. apply_pauli_product with no terms leaves what is queued in place"""
+  def _pprod_enter(self, nterms):
+    if nterms:
+      self.flush()
+
+
+class ProductUnitComputes(pm.NumpyDevice):
+  """42. a run of one unit string is computed as 0 * x + 1 * P x: a negative zero loses its sign"""
+  def _pprod_unit(self, vec, moved):
+    return 0.0 * vec + 1.0 * moved
+
+
+class ProductIdentityComputes(pm.NumpyDevice):
+  """43. a run of one factor (1, 0) is computed as 1 * x + 0 * P x: a negative zero loses its sign"""
+  def _pprod_identity(self, vec, x, z):
+    return 1.0 * vec + 0.0 * self._pprod_partner(vec, x, z)
+
+
+class ProductNormUnrounded(pm.NumpyDevice):
+  """44. at complex64 norm2 is summed from the double values before they are rounded to the handle's width"""
+  def _pprod_norm2(self, stored, unrounded, first_stored):
+    return float(np.vdot(unrounded, unrounded).real) if self.dtype == np.complex64 else super()._pprod_norm2(stored, unrounded, first_stored)
+
+
+class ProductNormByFirstRun(pm.NumpyDevice):
+  """45. norm2 is summed by the first run of the list, not by the last"""
+  def _pprod_norm2(self, stored, unrounded, first_stored):
+    return float(np.vdot(first_stored, first_stored).real)
+
+
+class ProductBytesOncePerCall(pm.NumpyDevice):
+  """46. the byte counters grow by 2 x the shard's bytes once per call, not once per run"""
+  def _pprod_bytes(self, nruns, shard_bytes):
+    return 2 * shard_bytes
+
+
 MUTANTS = [QueueBehindBarrier, CopyKeepsQueue, CopyDropsBitmap, ReleaseKeepsLogicalNumbers, ExtendOnTop, MuxSelectorsReversed,
            TopkTiesByPhysicalIndex, AxpbyReadsDstAnyway, SelectInPhysicalOrder, ReaderCanonicalises, MarginalIgnoresHeldBits,
            RoundsTwice, ReaderTurnsRelayoutOn, PermTableBackwards, PermBitsAscending, PermHeldControlMet, PermCanonicalises,
            PermNoopCountsAKernel, PermComputes, PermBeforeItsQueue, PauliIgnoresHeldZ, PauliPlusI, PauliDstKeepsBitmap,
            PauliDstKeepsQueue, PauliBeforeSrcQueue, PauliLaterBatchOverwrites, PauliFirstBatchReadsDst, PauliZeroTermsCountNothing,
-           PauliUnitComputes, PauliNormUnrounded]
+           PauliUnitComputes, PauliNormUnrounded, ProductTermsReversed, ProductSortsByX, ProductIgnoresHeldZ, ProductPlusI,
+           ProductNeverFlips, ProductBeforeItsQueue, ProductChecksLateTermsLate, ProductCanonicalises, ProductRunsOf16,
+           ProductZeroTermsCountAKernel, ProductZeroTermsDoNotFlush, ProductUnitComputes, ProductIdentityComputes, ProductNormUnrounded,
+           ProductNormByFirstRun, ProductBytesOncePerCall]
 PERM_MUTANTS = MUTANTS[13:20]
-PAULI_MUTANTS = MUTANTS[20:]
+PAULI_MUTANTS = MUTANTS[20:30]
+PRODUCT_MUTANTS = MUTANTS[30:]
+
+
+def _product_step(s):
+  """a 'pauli_product' step, or a call of apply_pauli_product that is to be refused"""
+  return s['op'] == 'pauli_product' or (s['op'] == 'refused' and s['what'].startswith('pauli_product_'))
 
 
 @pytest.mark.parametrize('mutant', MUTANTS, ids=[m.__name__ for m in MUTANTS])
@@ -324,6 +479,14 @@ def test_the_runner_fails_on_a_broken_device(mutant):
       order = [key for key in order if key[0] == 'shard']
     if mutant is PauliNormUnrounded:
       order = [key for key in order if key[2] == 64]
+  if mutant in PRODUCT_MUTANTS:                               # (they differ from NumpyDevice in apply_pauli_product alone)
+    order = [key for key in order if any(_product_step(s) for s in program(*key))]
+    if mutant is ProductIgnoresHeldZ:
+      order = [key for key in order if key[0] == 'shard']
+    if mutant is ProductNormUnrounded:
+      order = [key for key in order if key[2] == 64]
+    if mutant is ProductZeroTermsDoNotFlush:                  # (it differs on a list of no terms alone)
+      order = [key for key in order if any(s['op'] == 'pauli_product' and not s['x'] for s in program(*key))]
   for key in order:
     try:
       run_on(mutant, *key)
@@ -334,6 +497,8 @@ def test_the_runner_fails_on_a_broken_device(mutant):
         assert e.step['op'] == 'perm', e.step['op']
       if mutant in PAULI_MUTANTS:                                                     # ... or a Pauli sum
         assert e.step['op'] == 'pauli_sum', e.step['op']
+      if mutant in PRODUCT_MUTANTS:                                                   # ... or a Pauli product (applied or refused)
+        assert _product_step(e.step), e.step
       return
   raise AssertionError(f'{mutant.__name__} ({mutant.__doc__}) passes every fixed program')
 
@@ -342,7 +507,7 @@ def test_the_runner_fails_on_a_broken_device(mutant):
 def coverage(bw):
   kinds = dict.fromkeys(pm.KINDS, 0)
   permuted = dict.fromkeys(pm.BARRIERS + pm.READERS, 0)
-  queued = dict.fromkeys(pm.BARRIERS + pm.READERS + ('clone', 'copy', 'extend', 'release', 'inner', 'axpby', 'pauli_sum', 'remap'), 0)
+  queued = dict.fromkeys(pm.BARRIERS + pm.READERS + ('clone', 'copy', 'extend', 'release', 'inner', 'axpby', 'pauli_sum', 'pauli_product', 'remap'), 0)
   paths = {(op, p): 0 for op in pm.TWO_STATE for p in (pm.LINEAR, pm.TILES, pm.GATHER)}
   for (mode, seed, w), c in checks().items():
     if w != bw:
@@ -454,6 +619,71 @@ PAULI_AT_LEAST = {'k_pauli_small shape': 2, 'main shape': 3, 'main shape: few te
 PAULI_AT_LEAST_64 = {'complex64: px bit 0 set': 2, 'complex64: pz bit 0 set': 2}
 
 
+PRODUCT_WALKS = ('diag', 'lane', 'pair', 'half')           # program_model.pauli_product_walk on the main shape ('half': complex64 alone)
+
+
+def pauli_product_counts(records, bw):
+  """what 'pauli_product' steps met, from (mode, non-identity local map, record of _Runner.run_pauli_product); shared with the
+  closing item of tests/test_gpu_program_fuzz.py, which counts what the real qh_pauli_product_plan and qh_get_bitmap said"""
+  n = {}
+  def count(name, cond):
+    n[name] = n.get(name, 0) + bool(cond)
+  for mode, permuted, r in records:
+    runs = r['runs']
+    count('k_pauli_product_small shape', not r['main'] and not r['zero'])
+    count('main shape', r['main'] and not r['zero'])
+    for walk in PRODUCT_WALKS[:4 if bw == 64 else 3]:
+      for slots in ('few', 'many'):
+        count(f'main shape: {walk} walk, {slots} term slots', any(x['walk'] == walk and x['slots'] == slots for x in runs))
+    count('three or more runs', r['nruns'] >= 3)
+    count('three or more runs on the main shape', r['nruns'] >= 3 and r['main'])
+    count('several runs, norm2 asked', r['nruns'] >= 2 and r['norm'])
+    count('several runs, norm2 not asked', r['nruns'] >= 2 and not r['norm'])
+    count('a run with flip set', any(x['flip'] for x in runs))
+    count('a run with flip set on the main shape', r['main'] and any(x['flip'] and x['kind'] != pm.native.QH_PAULI_RUN_DIAG for x in runs))
+    count('a run mixing diagonal and exchanging terms', any(x['mixed'] for x in runs))
+    count('exact path: one unit string', any(x['exact'] == 'string' for x in runs))
+    count('exact path: the factor (1, 0)', any(x['exact'] == 'identity' for x in runs))
+    count('zero terms', r['zero'])
+    count('zero terms behind a queue', r['zero'] and r['queued'])
+    count('behind a queued burst', r['queued'])
+    count('behind a queued burst with relayout on, at 14 or more local bits', r['queued'] and r['relayout_on'] and r['nloc'] >= 14)
+    count('on a non-identity local map its own flush left', r['relaid'])
+    count('on a non-identity local map', permuted)
+    count('shard: a held z bit with neg set', r['shard'] and r['held_z'] and r['neg'])
+    count('shard: main shape with neg set', r['shard'] and r['main'] and r['neg'])
+    count('on an attached handle', mode == 'attached' and r['fixed'])
+    count('on a host-mapped handle', mode == 'mapped' and r['fixed'])
+    if bw == 64:
+      count('complex64: physical bit 0 in X of a pair or lane run', any(x['px0'] and x['walk'] in ('pair', 'lane') for x in runs))
+      count('complex64: physical bit 0 in a z mask', r['pz0'])
+  return n
+
+
+def pauli_product_coverage(bw):
+  """what the 'pauli_product' steps of the fixed programs met, from the plan NumpyDevice.pauli_product_plan gives on its own bit map"""
+  n = pauli_product_counts([(mode, e[2], e[5]) for (mode, seed, w), c in checks().items() if w == bw for e in c.events if e[1] == 'pauli_product'], bw)
+  for (mode, seed, w) in checks():                             # the refusals of apply_pauli_product, from the programs themselves
+    for s in program(mode, seed, w):
+      if w == bw and s['op'] == 'refused' and s['what'].startswith('pauli_product_'):
+        n['refused: ' + s['what']] = n.get('refused: ' + s['what'], 0) + 1
+        n['refused on a handle with a queue'] = n.get('refused on a handle with a queue', 0) + bool(s['queued'])
+  return n
+
+
+PAULI_PRODUCT_AT_LEAST = dict({'k_pauli_product_small shape': 3, 'main shape': 3, 'three or more runs': 3, 'three or more runs on the main shape': 1,
+                               'several runs, norm2 asked': 2, 'several runs, norm2 not asked': 2, 'a run with flip set': 3,
+                               'a run with flip set on the main shape': 1, 'a run mixing diagonal and exchanging terms': 2,
+                               'exact path: one unit string': 2, 'exact path: the factor (1, 0)': 1, 'zero terms': 1, 'zero terms behind a queue': 1,
+                               'behind a queued burst': 3, 'behind a queued burst with relayout on, at 14 or more local bits': 1,
+                               'on a non-identity local map': 3, 'shard: a held z bit with neg set': 1, 'shard: main shape with neg set': 1,
+                               'on an attached handle': 1, 'on a host-mapped handle': 1, 'refused: pauli_product_nonfinite': 1,
+                               'refused: pauli_product_bad_qubit': 1, 'refused: pauli_product_x_held': 1, 'refused on a handle with a queue': 1},
+                              **{f'main shape: {walk} walk, {slots} term slots': 1 for walk in PRODUCT_WALKS[:3] for slots in ('few', 'many')})
+PAULI_PRODUCT_AT_LEAST_64 = {'main shape: half walk, few term slots': 1, 'main shape: half walk, many term slots': 1,
+                             'complex64: physical bit 0 in X of a pair or lane run': 1, 'complex64: physical bit 0 in a z mask': 2}
+
+
 @pytest.mark.parametrize('bw', WIDTHS)
 def test_coverage_of_the_fixed_programs(bw):
   kinds, permuted, queued, paths = coverage(bw)
@@ -473,6 +703,10 @@ def test_coverage_of_the_fixed_programs(bw):
   paulis = pauli_coverage(bw)
   print('  pauli_sum steps: ' + ', '.join(f'{k} {n}' + (f' (>= {least[k]})' if k in least else '') for k, n in paulis.items()))
   assert all(paulis.get(k, 0) >= v for k, v in least.items()), {k: paulis.get(k, 0) for k, v in least.items() if paulis.get(k, 0) < v}
+  least = dict(PAULI_PRODUCT_AT_LEAST, **(PAULI_PRODUCT_AT_LEAST_64 if bw == 64 else {}))
+  products = pauli_product_coverage(bw)
+  print('  pauli_product steps: ' + ', '.join(f'{k} {n}' + (f' (>= {least[k]})' if k in least else '') for k, n in products.items()))
+  assert all(products.get(k, 0) >= v for k, v in least.items()), {k: products.get(k, 0) for k, v in least.items() if products.get(k, 0) < v}
 
 
 def test_the_long_running_tool_ends_at_the_first_failure(monkeypatch, capsys):
