@@ -372,6 +372,65 @@ int qh_topk(qh_handle h, uint64_t k, qh_entry *out, uint64_t *count);
  * and one copy back, no read of the state (kernels_launched is unchanged).  Duplicates and count == 0 are allowed.
  * Errors, nothing written: QH_ERR_ARG (null, count > 2^24, an index >= 2^nbits_global).                                   */
 int qh_amplitudes(qh_handle h, uint64_t count, const uint64_t *logical, double *out, uint64_t *nlocal);
+/* Reduced density matrix of k listed LOGICAL bits (kernels_density.hip.h): rho = Tr_rest |psi><psi| of this shard.
+ * out[2 (r 2^k + c)], out[2 (r 2^k + c) + 1] = (re, im) of rho[r][c] = sum_e a(r,e) conj(a(c,e)), where a(r,e) is the shard's
+ * amplitude whose logical bit bits[t] equals bit t of r (the bit convention of qh_marginal) and whose remaining local bits
+ * spell e.  Per shard and not normalised: the trace is the shard's norm.  The output is always complex128: complex64
+ * amplitudes are widened unrounded, every product and sum is formed in double.
+ * 0 <= k <= min(QH_DENSITY_MAX_BITS, nbits_local): k = 0 gives the norm, k = nbits_local the outer product of the shard's
+ * state.  Works from 1 local bit up, at either width, on attached and host-mapped handles, in whatever layout the last flush
+ * left; the bits may sit at any physical positions.  Runs what is queued first; reads only (state, bit map, relayout mode
+ * and device pointer are as before).
+ * Exact properties: rho[c][r] is the bitwise conjugate of rho[r][c] (one triangle is computed, the other mirrored); every
+ * diagonal imaginary part is exactly 0.0; sums run in a fixed order without float atomics, so two calls on the same state
+ * and layout return the same bits; a basis state gives exactly one 1.0 and zeros elsewhere.  The diagonal agrees with
+ * qh_marginal to rounding (the summation orders differ).
+ * A listed bit held by the shard index is QH_ERR_NONLOCAL (nothing runs, out untouched: the off-diagonal blocks would live
+ * on other shards; exchange first, as for an x bit of qh_expect_pauli).  With every listed bit local, the sum of the shards'
+ * results is the global rho.
+ * The walk (qh_density_tiles below is what the engine launches from): a 256-thread workgroup owns a tile of up to 64 x 64
+ * entries, a thread a 4 x 4 block of complex accumulators; the workgroup walks its share of the remaining (environment)
+ * bits in chunks of columns that go into LDS once, with 16-byte loads in physical order.  k < 6: the 256 threads form groups
+ * that take different columns and are folded through LDS in a fixed order (k <= 2: one tile per thread, straight from
+ * memory).  k = 7, 8: the matrix is cut into blocks of 64 rows and one launch covers the block pairs (R, C >= R), 3 or 10 of
+ * them; a pair reads the rows of both blocks, so the state is read 2 or 4 times.  Every workgroup writes its partial tile
+ * to a slab row; a fold kernel adds the rows of a pair in workgroup order and scatters to out, mirroring the conjugate.
+ * Fewer than 8 local bits: one workgroup gathers amplitude by amplitude.
+ * qh_stats: kernels_launched + 1 (the fold is not counted), bytes_algorithmic + the shard's bytes, bytes_swept + the bytes
+ * the kernel requests (qh_density_tiles.amps_swept amplitudes).
+ * Errors, nothing runs and out is untouched: QH_ERR_ARG (null pointers, k out of range, dry handle), QH_ERR_BAD_QUBIT,
+ * QH_ERR_SAME_QUBIT, QH_ERR_NONLOCAL as above.                                                                            */
+#define QH_DENSITY_MAX_BITS 8
+int qh_reduced_density(qh_handle h, int k, const int32_t *bits, double *out /* 2 * 4^k doubles */);
+/* How qh_reduced_density would walk the state right now (density_plan.h: host arithmetic on the bit map only; nothing runs,
+ * nothing is flushed; planner-only handles too).  Positions are physical, local, ascending in every table.
+ *   row_pos[j], j < k       the register's positions; bit j of a row number as the kernels count it.  The first tile_bits
+ *                           of them number the rows of a tile, the others (k = 7, 8: the highest) number the row blocks.
+ *   row_bit[j]              row_pos[j] holds bits[row_bit[j]]: bit j of a kernel row number is bit row_bit[j] of r in out.
+ *   col_pos[c], c < chunk_bits   the columns of a chunk: the LOWEST positions the register does not hold.
+ *   rest_pos[q], q < nrest  the other environment positions: bit q of a chunk number.
+ * A launch has block_pairs * wg_per_pair workgroups; a workgroup walks chunks_per_wg consecutive chunks of 2^chunk_bits
+ * columns: wg_per_pair * chunks_per_wg * 2^chunk_bits = 2^(nbits_local - k), the environment exactly once per pair.
+ * Errors: QH_ERR_ARG (null, k out of range), QH_ERR_BAD_QUBIT, QH_ERR_SAME_QUBIT, QH_ERR_NONLOCAL as qh_reduced_density.    */
+#define QH_DENSITY_TILES 0      /* tiles of min(k, 6) row bits, chunks of columns                    */
+#define QH_DENSITY_GATHER 1     /* fewer than 8 local bits: one workgroup, amplitude by amplitude    */
+typedef struct {
+  uint32_t path;               /* QH_DENSITY_*                                                */
+  uint32_t k;                  /* register bits                                               */
+  uint32_t tile_bits;          /* row bits of a tile: min(k, 6); QH_DENSITY_GATHER: k          */
+  uint32_t chunk_bits;         /* column bits of a chunk                                      */
+  uint32_t nrest;              /* chunk-number bits: nbits_local - k - chunk_bits             */
+  uint32_t block_pairs;        /* 1, 3 (k = 7) or 10 (k = 8)                                  */
+  uint32_t wg_per_pair;        /* workgroups, = slab rows, per block pair                     */
+  uint32_t pad;
+  uint64_t chunks_per_wg;
+  uint64_t slab_bytes;         /* block_pairs * wg_per_pair rows of 4^tile_bits complex128    */
+  uint64_t amps_swept;         /* amplitudes the kernel requests: 2^(nbits_local + k - tile_bits) */
+  uint8_t row_pos[8], row_bit[8];
+  uint8_t col_pos[16];
+  uint8_t rest_pos[40];
+} qh_density_tiles;
+int qh_density_plan(qh_handle h, int k, const int32_t *bits, qh_density_tiles *out);
 
 /* ---- two states (kernels_two_state.hip.h) ------------------------------------ */
 /* A new handle on src's device holding a copy of src's state: what src has queued runs first, then one device-to-device

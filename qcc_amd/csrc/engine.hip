@@ -33,6 +33,8 @@
 #include "kernels_select.hip.h"
 #include "select_plan.h"
 #include "kernels_expect.hip.h"
+#include "kernels_density.hip.h"
+#include "density_plan.h"
 #include "kernels_pauli.hip.h"
 #include "pauli_plan.h"
 #include "kernels_pauli_product.hip.h"
@@ -761,7 +763,7 @@ int select_device(int device) {
 extern "C" {
 
 const char *qh_last_error(void) { return g_err.c_str(); }
-int qh_version(void) { return 116; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
+int qh_version(void) { return 117; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
 
 int qh_device_count(int *count) {
   if (!count) return fail(QH_ERR_ARG, "null");
@@ -2232,6 +2234,125 @@ int qh_amplitudes(qh_handle h, uint64_t count, const uint64_t *logical, double *
     if ((rc = read_back(h, out, d_out, count * 16, "amplitudes"))) return rc;
   }
   if (nlocal) *nlocal = mine;
+  return QH_OK;
+}
+
+}  // extern "C"
+
+// ---- reduced density matrices: qh_reduced_density, qh_density_plan (kernels_density.hip.h, density_plan.h) -------------------
+namespace {
+
+// The argument checks both entry points share, then the plan; nothing touches the device
+int plan_density_for(const qh_state_s *h, const char *who, int k, const int32_t *bits, const void *out, qh_density_tiles *pl) {
+  if (!h || !out || (k > 0 && !bits)) return fail(QH_ERR_ARG, "%s: null handle, bits or out", who);
+  const int kmax = std::min(QH_DENSITY_MAX_BITS, h->nloc);
+  if (k < 0 || k > kmax) return fail(QH_ERR_ARG, "%s: k = %d outside [0,%d]", who, k, kmax);
+  uint64_t seen = 0;
+  const int rc = check_bit_list(h, who, k, bits, &seen);
+  if (rc) return rc;
+  int pos[QH_DENSITY_MAX_BITS] = {};
+  for (int t = 0; t < k; ++t) {
+    if (place_bit(h, bits[t]).held)
+      return fail(QH_ERR_NONLOCAL, "%s: logical bit %d is at physical bit %d, held by the shard index (local bits: %d); exchange first",
+                  who, bits[t], h->perm[bits[t]], h->nloc);
+    pos[t] = h->perm[bits[t]];
+  }
+  qh::plan_density(h->nloc, k, pos, pl);
+  return QH_OK;
+}
+
+template <typename R, int KT>
+void launch_density_tiles(qh_state_s *h, const qh_density_tiles &pl, const qh::DensityArgs &a, double2 *slab) {
+  using A = typename qh::AmpT<R>::type;
+  const dim3 grid(pl.block_pairs * pl.wg_per_pair);
+  if constexpr (KT <= 2) {
+    hipLaunchKernelGGL((qh::k_density_direct<R, KT>), grid, dim3(256), 0, h->stream, (const A *)h->d_psi, a, (double *)slab);
+  } else if constexpr (KT == qh::kDensityTileBits) {
+    if (pl.block_pairs > 1) hipLaunchKernelGGL((qh::k_density_tiles<R, KT, true>), grid, dim3(256), 0, h->stream, (const A *)h->d_psi, a, slab);
+    else hipLaunchKernelGGL((qh::k_density_tiles<R, KT, false>), grid, dim3(256), 0, h->stream, (const A *)h->d_psi, a, slab);
+  } else {
+    hipLaunchKernelGGL((qh::k_density_tiles<R, KT, false>), grid, dim3(256), 0, h->stream, (const A *)h->d_psi, a, slab);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int qh_density_plan(qh_handle h, int k, const int32_t *bits, qh_density_tiles *out) {
+  qh_density_tiles pl;
+  const int rc = plan_density_for(h, "density_plan", k, bits, out, &pl);
+  if (rc) return rc;
+  *out = pl;
+  return QH_OK;
+}
+
+int qh_reduced_density(qh_handle h, int k, const int32_t *bits, double *out) {
+  qh_density_tiles pl;
+  int rc = plan_density_for(h, "reduced_density", k, bits, out, &pl);
+  if (rc) return rc;
+  if ((rc = enter(h))) return rc;
+  if ((rc = plan_density_for(h, "reduced_density", k, bits, out, &pl))) return rc;      // the flush may have re-laid the state out
+  const size_t out_bytes = (size_t)16 << (2 * k);
+  qh::ScratchLayout lay;
+  const size_t slab_off = lay.add(pl.slab_bytes), out_off = lay.add(out_bytes);
+  HIP_TRY(h->meas.reserve(lay.total));
+  double2 *slab = (double2 *)(h->meas.as<char>() + slab_off), *dout = (double2 *)(h->meas.as<char>() + out_off);
+  if (pl.path == QH_DENSITY_GATHER) {
+    qh::DensityGatherArgs g{};
+    memcpy(g.row_pos, pl.row_pos, 8);
+    memcpy(g.row_bit, pl.row_bit, 8);
+    memcpy(g.rest_pos, pl.rest_pos, 8);
+    g.k = k;
+    g.ne = (int)pl.nrest;
+    with_real(h, [&](auto x) {
+      using R = decltype(x);
+      hipLaunchKernelGGL(qh::k_density_gather<R>, dim3(1), dim3(256), 0, h->stream, (const typename qh::AmpT<R>::type *)h->d_psi, g, dout);
+    });
+  } else {
+    qh::DensityArgs a{};
+    memcpy(a.row_pos, pl.row_pos, 8);
+    memcpy(a.col_pos, pl.col_pos, sizeof a.col_pos);
+    memcpy(a.rest_pos, pl.rest_pos, sizeof a.rest_pos);
+    a.k = k;
+    a.kt = (int)pl.tile_bits;
+    a.cb = (int)pl.chunk_bits;
+    a.nrest = (int)pl.nrest;
+    a.wgpp = pl.wg_per_pair;
+    a.cpw = pl.chunks_per_wg;
+    for (uint32_t q = 0; q < pl.nrest; ++q) a.rest_mask |= 1ull << pl.rest_pos[q];
+    // the load order of a chunk of a tile: its row and column positions merged, ascending
+    for (int i = 0, jr = 0, jc = 0; i < a.kt + a.cb; ++i) {
+      const bool row = jc == a.cb || (jr < a.kt && pl.row_pos[jr] < pl.col_pos[jc]);
+      a.upos[i] = row ? pl.row_pos[jr] : pl.col_pos[jc];
+      a.udst[i] = (uint8_t)(row ? jr++ : 16 + jc++);
+    }
+    with_real(h, [&](auto x) {
+      using R = decltype(x);
+      switch (a.kt) {
+        case 0: launch_density_tiles<R, 0>(h, pl, a, slab); break;
+        case 1: launch_density_tiles<R, 1>(h, pl, a, slab); break;
+        case 2: launch_density_tiles<R, 2>(h, pl, a, slab); break;
+        case 3: launch_density_tiles<R, 3>(h, pl, a, slab); break;
+        case 4: launch_density_tiles<R, 4>(h, pl, a, slab); break;
+        case 5: launch_density_tiles<R, 5>(h, pl, a, slab); break;
+        default: launch_density_tiles<R, 6>(h, pl, a, slab); break;
+      }
+    });
+    qh::DensityFoldArgs f{};
+    memcpy(f.row_bit, pl.row_bit, 8);
+    f.k = k;
+    f.kt = a.kt;
+    f.wgpp = pl.wg_per_pair;
+    f.npairs = pl.block_pairs;
+    const uint32_t nfold = pl.block_pairs << (2 * a.kt);
+    hipLaunchKernelGGL(qh::k_density_fold, dim3((nfold + 3) / 4), dim3(256), 0, h->stream, (const double2 *)slab, f, dout);
+  }
+  if ((rc = check_launch(h))) return rc;
+  if ((rc = read_back(h, out, dout, out_bytes, "reduced_density"))) return rc;
+  h->stats.kernels_launched += 1;      // (the fold is not counted, as in qh_inner)
+  h->stats.bytes_algorithmic += (1ull << h->nloc) * h->amp_bytes();
+  h->stats.bytes_swept += pl.amps_swept * h->amp_bytes();
   return QH_OK;
 }
 

@@ -15,6 +15,7 @@ from qcc_amd import native
 
 _dp = ctypes.POINTER(ctypes.c_double)
 MAX_MARGINAL_BITS = 16     # qh_marginal: k <= 16
+MAX_DENSITY_BITS = native.QH_DENSITY_MAX_BITS     # qh_reduced_density: k <= 8
 
 
 def _g8(gate):
@@ -365,6 +366,24 @@ class DeviceState:
     native.check(self.lib.qh_marginal(self.h, int(b.size), b.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
                                       out.ctypes.data_as(_dp)))
     return out
+
+  def reduced_density(self, bits):
+    """(2^k, 2^k) complex128: rho[r][c] = sum_e a(r,e) conj(a(c,e)) over this shard, where the LOGICAL bit bits[t] of a(r,e)'s
+    index is bit t of r (qh_reduced_density; 0 <= k <= 8, not normalised, bitwise Hermitian and reproducible)."""
+    b = np.ascontiguousarray([int(x) for x in bits], dtype=np.int32)
+    if b.size > MAX_DENSITY_BITS:      # (before sizing the 4^k result: the engine would refuse it anyway)
+      raise native.QhError(native.QH_ERR_ARG, f'reduced_density: k = {b.size} outside [0,{MAX_DENSITY_BITS}]')
+    out = np.zeros((1 << b.size, 1 << b.size), dtype=np.complex128)
+    native.check(self.lib.qh_reduced_density(self.h, int(b.size), b.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                             out.ctypes.data_as(_dp)))
+    return out
+
+  def density_plan(self, bits):
+    """How reduced_density(bits) would walk the state right now (qh_density_plan), as a dict."""
+    b = np.ascontiguousarray([int(x) for x in bits], dtype=np.int32)
+    t = native.QhDensityTiles()
+    native.check(self.lib.qh_density_plan(self.h, int(b.size), b.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(t)))
+    return t.as_dict()
 
   def sample(self, u):
     """LOGICAL indices drawn by inverse CDF for the ascending uniforms u in [0, 1) (qh_sample)."""

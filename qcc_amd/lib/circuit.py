@@ -77,6 +77,7 @@ def _u1_operator(value):
 _DENSE_MAX_BITS = 6        # qh_apply_matrix: dense operators on up to 6 qubits run on the device
 _TABLE_MAX_BITS = 16       # qh_apply_mux / qh_apply_diag: tables over up to 16 qubits
 _MARGINAL_MAX_BITS = 16    # qh_marginal: registers of up to 16 qubits (2^16 probabilities)
+_DENSITY_MAX_BITS = 8      # qh_reduced_density: registers of up to 8 qubits (a 256 x 256 matrix)
 _EXTEND_MAX_BITS = 16      # qh_extend / qh_release: up to 16 qubits added or given back per call
 
 
@@ -922,13 +923,15 @@ class qc:
     # Register readout (extensions: the reference loops psi.prob(*bits) over basis states).  qubits[0] is the most
     # significant bit of a register value (np.kron order, helper.bits2val); the engine takes LOGICAL bits (qubit q is
     # bit n-1-q).  Devices without marginal / sample / project_bits read qc.psi on the host instead.
-    def _register(self, qubits, what):
+    def _register(self, qubits, what, at_most=None):
         n = self._nbits
         qubits = list(range(n)) if qubits is None else [int(q) for q in qubits]
         if any(q < 0 or q >= n for q in qubits):
             raise ValueError(f'{what}: qubits {qubits} out of range for {n} qubits')
         if len(set(qubits)) != len(qubits):
             raise ValueError(f'{what}: a qubit appears twice in {qubits}')
+        if at_most is not None and len(qubits) > at_most:
+            raise ValueError(f'{what}: {len(qubits)} qubits (at most {at_most})')
         return qubits
 
     def _register_values(self, idx, qubits):
@@ -954,6 +957,66 @@ class qc:
         out = np.zeros(1 << k, dtype=np.float64)
         np.add.at(out, self._register_values(np.arange(p.size, dtype=np.uint64), qubits).astype(np.int64), p)
         return out
+
+    # Reduced density matrices (extensions: the reference traces a 4^n matrix, ops.TraceOut(psi.density(), ...)).  One call
+    # of qh_reduced_density gives the 2^k x 2^k matrix of up to 8 qubits without downloading the state; the derived
+    # quantities are host NumPy on that small matrix, divided by its trace.  A state that is still a product on the host and
+    # alias mode read qc.psi with NumPy instead, and so do devices without reduced_density; any other state that is current
+    # on the host only is uploaded first, as probabilities does.
+    def _rho(self, qubits, what):
+        """(2^k, 2^k) complex128, not normalised."""
+        qubits = self._register(qubits, what, at_most=_DENSITY_MAX_BITS)
+        n, k = self._nbits, len(qubits)
+        if self._q_ops:
+            self._drain()
+        if not self._aliased() and not (self._is_product and not self._dev_ok):
+            dev = self._ensure_device()
+            if hasattr(dev, 'reduced_density'):
+                return np.asarray(dev.reduced_density([n - 1 - q for q in reversed(qubits)]), dtype=np.complex128)
+        a = np.asarray(self.psi, dtype=np.complex128).reshape((2,) * n)
+        a = np.moveaxis(a, qubits, list(range(k))).reshape(1 << k, -1)
+        return a @ a.conj().T
+
+    def reduced_density(self, qubits):
+        """ops.Operator (2^k, 2^k): rho = Tr_rest |psi><psi| of the qubits `qubits` (k <= 8); qubits[0] is the most
+        significant bit of a row or column number, so for ascending qubits it is ops.TraceOut(psi.density(), [the other
+        qubits]).  Not renormalised: the trace is the state's norm.  (An Operator has the tensor width; the quantities
+        below work on the complex128 matrix.)"""
+        return ops.Operator(self._rho(qubits, 'reduced_density'))
+
+    def _unit_density(self, qubits, what):
+        rho = self._rho(qubits, what)
+        tr = float(np.trace(rho).real)
+        if not tr > 0:
+            raise ValueError(f'{what}: the state has norm 0')
+        return rho / tr
+
+    def purity(self, qubits):
+        """Tr rho^2 of the qubits' reduced state (1 for a pure one, 2^-k for the maximally mixed one)."""
+        rho = self._unit_density(qubits, 'purity')
+        return float(np.sum(np.abs(rho) ** 2))
+
+    def entropy(self, qubits, base=2):
+        """Von Neumann entropy -Tr rho log rho of the qubits' reduced state: for a pure global state, the entanglement
+        entropy between `qubits` and the rest.  Eigenvalues <= 0 contribute 0."""
+        ev = np.linalg.eigvalsh(self._unit_density(qubits, 'entropy'))
+        ev = ev[ev > 0]
+        return float(max(0.0, -np.sum(ev * np.log(ev)) / math.log(base)))
+
+    def schmidt_coefficients(self, qubits):
+        """The Schmidt coefficients of the cut `qubits` | rest, descending: square roots of rho's eigenvalues (clipped at 0)."""
+        ev = np.linalg.eigvalsh(self._unit_density(qubits, 'schmidt_coefficients'))
+        return np.sqrt(np.clip(ev[::-1], 0.0, None))
+
+    def mutual_information(self, a, b, base=2):
+        """S(a) + S(b) - S(a u b) for two disjoint registers of at most 8 qubits together."""
+        a, b = self._register(a, 'mutual_information'), self._register(b, 'mutual_information')
+        both = self._register(a + b, 'mutual_information', at_most=_DENSITY_MAX_BITS)
+        return self.entropy(a, base) + self.entropy(b, base) - self.entropy(both, base)
+
+    def bloch(self, qubit):
+        """(x, y, z) of one qubit's reduced state (helper.density_to_cartesian)."""
+        return helper.density_to_cartesian(self._unit_density([qubit], 'bloch'))
 
     @staticmethod
     def _uniforms(count, seed, dev):

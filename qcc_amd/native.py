@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB_PATH = os.environ.get('QCC_HIP_LIB') or os.path.join(PKG, 'libqcc_hip.so')  # env: A/B builds only
 SOURCES = [os.path.join(PKG, 'csrc', f) for f in
-           ('engine.hip', 'buffers.hip.h', 'kernels_common.hip.h', 'kernels_gate.hip.h', 'kernels_argmax.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_perm.hip.h', 'perm_plan.h', 'kernels_measure.hip.h', 'kernels_select.hip.h', 'select_plan.h', 'kernels_expect.hip.h', 'kernels_pauli.hip.h', 'pauli_plan.h', 'kernels_pauli_product.hip.h', 'pauli_product_plan.h', 'kernels_two_state.hip.h', 'kernels_inner.hip.h', 'kernels_axpby.hip.h', 'inner_plan.h', 'kernels_resize.hip.h', 'resize_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h', 'exchange_plan.h',
+           ('engine.hip', 'buffers.hip.h', 'kernels_common.hip.h', 'kernels_gate.hip.h', 'kernels_argmax.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_perm.hip.h', 'perm_plan.h', 'kernels_measure.hip.h', 'kernels_select.hip.h', 'select_plan.h', 'kernels_expect.hip.h', 'kernels_density.hip.h', 'density_plan.h', 'kernels_pauli.hip.h', 'pauli_plan.h', 'kernels_pauli_product.hip.h', 'pauli_product_plan.h', 'kernels_two_state.hip.h', 'kernels_inner.hip.h', 'kernels_axpby.hip.h', 'inner_plan.h', 'kernels_resize.hip.h', 'resize_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h', 'exchange_plan.h',
             'sweep_island_rb2.inc', 'sweep_island_rb3.inc', 'sweep_island_rb4.inc',
             'sweep_island_rb5.inc', 'sweep_island_f32_rb2.inc', 'sweep_island_f32_rb3.inc',
             'sweep_island_f32_rb4.inc', 'sweep_island_f32_rb5.inc', 'sweep_island_f32_rb6.inc', 'sweep_handlers.inc',
@@ -48,6 +48,23 @@ class QhInnerTiles(ctypes.Structure):
 
   def as_dict(self):
     return {k: (int(getattr(self, k)) if isinstance(getattr(self, k), int) else list(getattr(self, k))) for k, _ in self._fields_}
+
+
+QH_DENSITY_MAX_BITS = 8
+QH_DENSITY_TILES, QH_DENSITY_GATHER = 0, 1
+
+
+class QhDensityTiles(ctypes.Structure):
+  """include/qcc_hip.h qh_density_tiles: how qh_reduced_density walks the state."""
+  _u8 = ctypes.c_uint8
+  _fields_ = [('path', ctypes.c_uint32), ('k', ctypes.c_uint32), ('tile_bits', ctypes.c_uint32), ('chunk_bits', ctypes.c_uint32),
+              ('nrest', ctypes.c_uint32), ('block_pairs', ctypes.c_uint32), ('wg_per_pair', ctypes.c_uint32), ('pad', ctypes.c_uint32),
+              ('chunks_per_wg', _u64), ('slab_bytes', _u64), ('amps_swept', _u64), ('row_pos', _u8 * 8), ('row_bit', _u8 * 8),
+              ('col_pos', _u8 * 16), ('rest_pos', _u8 * 40)]
+
+  def as_dict(self):
+    return {k: (int(getattr(self, k)) if isinstance(getattr(self, k), int) else list(getattr(self, k))) for k, _ in self._fields_
+            if k != 'pad'}
 
 
 QH_PERM_MAX_BITS = 16
@@ -153,6 +170,8 @@ SIGNATURES = {
     'qh_select': (_i32, [_vp, ctypes.c_double, _u64, ctypes.POINTER(QhEntry), ctypes.POINTER(_u64), _dp]),
     'qh_topk': (_i32, [_vp, _u64, ctypes.POINTER(QhEntry), ctypes.POINTER(_u64)]),
     'qh_amplitudes': (_i32, [_vp, _u64, ctypes.POINTER(_u64), _dp, ctypes.POINTER(_u64)]),
+    'qh_reduced_density': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _dp]),
+    'qh_density_plan': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(QhDensityTiles)]),
     'qh_clone': (_i32, [_vp, ctypes.POINTER(_vp)]),
     'qh_copy': (_i32, [_vp, _vp]),
     'qh_inner': (_i32, [_vp, _vp, _dp]),
