@@ -585,6 +585,68 @@ int qh_pauli_product_plan(qh_handle h, uint64_t nterms, const uint64_t *xmask, c
                           qh_pauli_term *terms /* nterms, caller's order; may be NULL */,
                           qh_pauli_run *runs, uint64_t cap, uint64_t *nruns);
 
+/* ---- diagonal Z-polynomial operators (kernels_zpoly.hip.h, zpoly_plan.h) ------- */
+/* A classical cost function of the basis state as a polynomial in Z, over LOGICAL bits:
+ *   f(i) = sum_t w[t] * (-1)^popcount(i & zmask[t]),   zmask == 0: a constant term.
+ * qh_apply_zpoly: a_i *= exp(c * f(i)) in place for any finite complex c = (re, im): c = (0, -gamma) is the QAOA cost layer
+ * exp(-i gamma C), c = (-tau, 0) imaginary time under C.  A constant term is applied, not dropped (imaginary c: a global
+ * phase).  Terms are taken as given: equal masks are not merged.
+ * A barrier, as qh_apply_diag and qh_apply_pauli_product: what is queued runs first and the call works on the layout it finds;
+ * bit map, relayout mode and device pointer are as before.  Attached, host-mapped and shard handles, from 1 local bit up, at
+ * either width.  The caller's arrays are not referenced after the call returns.
+ * ONE kernel, one read and one write of the state, for any nterms <= QH_ZPOLY_MAX_TERMS.  On the layout as it is, the amplitude
+ * index splits into a chunk part (item bits 11 and up; an item is 16 bytes) and a low part below it.  A term wholly in the chunk
+ * part (or constant) is a scalar per chunk; a term wholly in the low part is a constant of the thread for the whole kernel; a
+ * term that straddles is sign_chunk * sign_low, and all straddling terms with the same low mask form one GROUP, one scalar per
+ * chunk.  A group whose low mask lies on thread bits only is added once per thread and chunk, one on register-index / half
+ * bits only once per chunk; per amplitude that leaves two adds (one more per group of mixed low mask; a 2-local cost function
+ * has none), one sincos (and one exp unless c.re == 0), one complex product.  States below one chunk take a
+ * one-amplitude-per-thread kernel that sums f by popcount.
+ * Shards: a z bit held by the shard index is a sign fixed per shard, folded into w[t] on the host as an exact negation: no
+ * Z-polynomial is non-local.
+ * Arithmetic: f is summed in double in a fixed order (the chunk scalar and the thread-only groups, + the thread's low sum, + the
+ * register-index / half groups, + the mixed groups; groups of a kind in order of first appearance; inside a scalar, the terms in
+ * the caller's order dealt to 64 lanes, then an xor tree).  The factor is
+ * exp(c.re f) * (cos(c.im f), sin(c.im f)) from the precise device sincos / exp; the product with the amplitude as stored is
+ * taken in double (complex64 widened unrounded) and rounded once to the handle's width.
+ * norm2 (may be NULL): sum |v|^2 of the final amplitudes as stored, over this shard, in the readers' fixed order without
+ * atomics: bitwise reproducible for a given state, layout and term list.
+ * nterms == 0 or c == (0, 0): flushes and launches nothing; norm2 is then qh_norm2's.
+ * qh_stats: gates_submitted + 1, kernels_launched + 1, bytes_swept and bytes_algorithmic + 2 x the shard's bytes.
+ * Errors, nothing runs, nothing changes, nothing is flushed, the whole list is checked first: QH_ERR_ARG (null handle, null
+ * arrays with nterms > 0, null c, nterms > QH_ZPOLY_MAX_TERMS, a non-finite weight or c: qh_last_error names the first
+ * offending term, dry handle), QH_ERR_BAD_QUBIT (mask bits >= nbits_global).                                               */
+#define QH_ZPOLY_MAX_TERMS 4096
+int qh_apply_zpoly(qh_handle h, uint64_t nterms, const double *w, const uint64_t *zmask, const double c[2],
+                   double *norm2 /* may be NULL */);
+/* out[0] = sum |a_i|^2, out[1] = sum |a_i|^2 f(i), out[2] = sum |a_i|^2 f(i)^2 over this shard, not normalised: the norm,
+ * <C> and <C^2> of a cost function in ONE kernel and one read of the state for any nterms.  Runs what is queued first and
+ * reads only.  The same fixed-order f; three sums in the readers' fixed order: bitwise reproducible.  nterms == 0 gives
+ * (qh_norm2, 0, 0).  qh_stats: kernels_launched + 1, bytes_swept and bytes_algorithmic + 1 x the shard's bytes.  Errors as
+ * above (null out: QH_ERR_ARG).                                                                                            */
+int qh_expect_zpoly(qh_handle h, uint64_t nterms, const double *w, const uint64_t *zmask, double out[3]);
+/* How the terms fall on h's layout right now: runs nothing, flushes nothing, planner-only handles too.  Per term, in the
+ * caller's order: the physical local mask pz, the weight with the shard's sign folded in, and its class.  low_bits: the
+ * amplitude-index bits below the chunk part (the small kernel: all local bits, so every term is constant or low).
+ * group_mask[g], g < ngroups: the distinct low masks among the straddling terms, in physical positions, in order of first
+ * appearance.  kernel: which kernel would run, on nblk blocks of 256 threads (main: cpb chunks each).  The engine launches
+ * from this very function.  Errors: QH_ERR_ARG (null, too many terms, non-finite weight), QH_ERR_BAD_QUBIT.               */
+#define QH_ZPOLY_CONST 0
+#define QH_ZPOLY_HIGH 1
+#define QH_ZPOLY_LOW 2
+#define QH_ZPOLY_STRADDLE 3
+#define QH_ZPOLY_KERNEL_MAIN 0
+#define QH_ZPOLY_KERNEL_SMALL 1
+typedef struct {
+  uint64_t nterms, nconst, nhigh, nlow, nstraddle, ngroups, nblk;
+  uint32_t kernel, low_bits, cpb, pad;
+  uint64_t group_mask[QH_ZPOLY_MAX_TERMS];
+  uint64_t pz[QH_ZPOLY_MAX_TERMS];
+  double w[QH_ZPOLY_MAX_TERMS];
+  uint8_t cls[QH_ZPOLY_MAX_TERMS];
+} qh_zpoly_info;
+int qh_zpoly_plan(qh_handle h, uint64_t nterms, const double *w, const uint64_t *zmask, qh_zpoly_info *out);
+
 /* ---- growing and shrinking a state (kernels_resize.hip.h) ----------------- */
 /* Both calls make a NEW handle and leave src as qh_clone leaves it: what src has queued runs first (exchange arrivals are
  * waited for); src keeps its amplitudes, bit map, relayout mode and device pointer.  The new handle lives on src's device with

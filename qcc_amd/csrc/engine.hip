@@ -39,6 +39,8 @@
 #include "pauli_plan.h"
 #include "kernels_pauli_product.hip.h"
 #include "pauli_product_plan.h"
+#include "kernels_zpoly.hip.h"
+#include "zpoly_plan.h"
 #include "kernels_two_state.hip.h"
 #include "kernels_inner.hip.h"
 #include "kernels_axpby.hip.h"
@@ -104,6 +106,9 @@ struct qh_state_s {
   // qh_apply_mux / qh_apply_diag: one pinned staging buffer and one device table, grown on demand (a k = 16 mux table is
   // 4 MiB: the ring's slots are too small); reused only after the event recorded behind the kernel that read the table
   qh::StagedUpload<1> tab;
+  // qh_apply_zpoly / qh_expect_zpoly: the term block (zpoly_plan.h), written on the host, read by one kernel; one slot of a
+  // fixed size, reused only after the event recorded behind that kernel
+  qh::StagedUpload<1> zpoly;
   qh::DeviceBuffer meas;       // the readers' scratch (slabs, chunk sums, shot lists, results), grown on demand
   double *d_red() const { return red.as<double>(); }
   uint64_t *d_redi() const { return redi.as<uint64_t>(); }
@@ -763,7 +768,7 @@ int select_device(int device) {
 extern "C" {
 
 const char *qh_last_error(void) { return g_err.c_str(); }
-int qh_version(void) { return 117; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
+int qh_version(void) { return 118; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
 
 int qh_device_count(int *count) {
   if (!count) return fail(QH_ERR_ARG, "null");
@@ -3117,6 +3122,177 @@ int qh_apply_pauli_product(qh_handle h, uint64_t nterms, const double *ab, const
   h->stats.kernels_launched += runs.size();      // (the fold is not counted, as in qh_axpby)
   h->stats.bytes_swept += 2 * runs.size() * shard_bytes;
   h->stats.bytes_algorithmic += 2 * runs.size() * shard_bytes;
+  return QH_OK;
+}
+
+}  // extern "C"
+
+// ---- Z-polynomial operators: qh_apply_zpoly, qh_expect_zpoly, qh_zpoly_plan (kernels_zpoly.hip.h, zpoly_plan.h) ------------
+namespace {
+
+// Argument checks of the three calls, then the terms on h's bit map as it is now (masks through the bit map, the shard's
+// sign folded into the weight) and their plan.  Host arithmetic only: valid on dry handles.
+int check_zpoly(const qh_state_s *h, const char *who, uint64_t nterms, const double *w, const uint64_t *zmask) {
+  if (!h) return fail(QH_ERR_ARG, "%s: null handle", who);
+  if (nterms && (!w || !zmask)) return fail(QH_ERR_ARG, "%s: null weights or masks with %llu terms", who, (unsigned long long)nterms);
+  if (nterms > QH_ZPOLY_MAX_TERMS)
+    return fail(QH_ERR_ARG, "%s: %llu terms (at most %d)", who, (unsigned long long)nterms, QH_ZPOLY_MAX_TERMS);
+  for (uint64_t t = 0; t < nterms; ++t) {
+    if (!std::isfinite(w[t])) return fail(QH_ERR_ARG, "%s: term %llu has a non-finite weight (%g)", who, (unsigned long long)t, w[t]);
+    if (h->nglob < 64 && (zmask[t] >> h->nglob))
+      return fail(QH_ERR_BAD_QUBIT, "%s: term %llu (z 0x%llx) has bits >= %d", who, (unsigned long long)t, (unsigned long long)zmask[t],
+                  h->nglob);
+  }
+  return QH_OK;
+}
+
+void plan_zpoly(const qh_state_s *h, uint64_t nterms, const double *w, const uint64_t *zmask, std::vector<qh::ZpolyTerm> *terms,
+                qh::ZpolyPlan *plan) {
+  terms->resize(nterms);
+  for (uint64_t t = 0; t < nterms; ++t) {
+    const Placed z = place(h, to_phys(h, zmask[t]));
+    (*terms)[t] = qh::ZpolyTerm{(__builtin_popcountll(h->shard & z.held) & 1) ? -w[t] : w[t], z.local};
+  }
+  qh::zpoly_plan(terms->data(), nterms, h->nloc, h->bw == 128 ? 0 : 1, plan);
+}
+
+// the block into the pinned slot and from there, on the handle's stream, to the device; a filled in with where its parts are
+int stage_zpoly(qh_state_s *h, const qh::ZpolyPlan &p, const char *who, qh::ZpolyArgs *a) {
+  char *host = nullptr, *d = nullptr;
+  unsigned slot = 0;
+  const int rc = acquire(h, h->zpoly, qh::kZpolyBlockBytes, who, &host, &d, &slot);
+  if (rc) return rc;
+  const size_t wb = p.wd.size() * 8, mb = p.md.size() * 8;
+  if (wb) memcpy(host, p.wd.data(), wb);
+  if (mb) memcpy(host + wb, p.md.data(), mb);
+  HIP_TRY(hipMemcpyAsync(d, host, wb + mb, hipMemcpyHostToDevice, h->stream));
+  a->wd = (const double *)d;
+  a->md = (const uint64_t *)(d + wb);
+  a->nseg = p.nseg;
+  a->nlow = (uint32_t)p.nlow;
+  a->nterms = p.nterms;
+  a->nseg_terms = p.nseg_terms;
+  a->cached = p.main && p.nseg_terms <= qh::kZpolyLdsTerms ? 1u : 0u;
+  a->ngt = p.ngt;
+  a->ngu = p.ngu;
+  a->off_lw = p.off_lw;
+  a->off_sc = p.off_sc;
+  a->off_gl = p.off_gl;
+  a->off_lm = p.off_lm;
+  a->cpb = p.cpb;
+  return QH_OK;
+}
+
+// one kernel on h's stream: the apply (expect == false) or the three moments
+void launch_zpoly(qh_state_s *h, const qh::ZpolyPlan &p, const qh::ZpolyArgs &a, bool expect, double *slab) {
+  with_real(h, [&](auto x) {
+    using R = decltype(x);
+    const dim3 grid((unsigned)p.nblk), block(256);
+    if (p.main) {
+      using V = typename qh::Item16<R>::vec;
+      const size_t lds = qh::zpoly_lds_bytes(p.nseg, p.nseg_terms, a.cached != 0);
+      if (expect) hipLaunchKernelGGL((qh::k_zpoly_expect<R>), grid, block, lds, h->stream, (const V *)h->d_psi, a, slab);
+      else hipLaunchKernelGGL((qh::k_zpoly_apply<R>), grid, block, lds, h->stream, (V *)h->d_psi, a, slab);
+    } else {
+      using A = typename qh::AmpT<R>::type;
+      const uint64_t n = 1ull << h->nloc;
+      if (expect) hipLaunchKernelGGL((qh::k_zpoly_small<R, true>), grid, block, 0, h->stream, (A *)h->d_psi, a, n, slab);
+      else hipLaunchKernelGGL((qh::k_zpoly_small<R, false>), grid, block, 0, h->stream, (A *)h->d_psi, a, n, slab);
+    }
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int qh_zpoly_plan(qh_handle h, uint64_t nterms, const double *w, const uint64_t *zmask, qh_zpoly_info *out) {
+  int rc = check_zpoly(h, "zpoly_plan", nterms, w, zmask);
+  if (rc) return rc;
+  if (!out) return fail(QH_ERR_ARG, "zpoly_plan: null out");
+  std::vector<qh::ZpolyTerm> terms;
+  qh::ZpolyPlan p;
+  plan_zpoly(h, nterms, w, zmask, &terms, &p);
+  memset(out, 0, sizeof *out);
+  out->nterms = nterms;
+  out->nconst = p.nconst;
+  out->nhigh = p.nhigh;
+  out->nlow = p.nlow;
+  out->nstraddle = p.nstraddle;
+  out->ngroups = p.group_mask.size();
+  out->nblk = p.nblk;
+  out->kernel = p.main ? QH_ZPOLY_KERNEL_MAIN : QH_ZPOLY_KERNEL_SMALL;
+  out->low_bits = (uint32_t)p.low_bits;
+  out->cpb = p.cpb;
+  for (size_t g = 0; g < p.group_mask.size(); ++g) out->group_mask[g] = p.group_mask[g];
+  for (uint64_t t = 0; t < nterms; ++t) {
+    out->pz[t] = terms[t].pz;
+    out->w[t] = terms[t].w;
+    out->cls[t] = p.cls[t];
+  }
+  return QH_OK;
+}
+
+int qh_apply_zpoly(qh_handle h, uint64_t nterms, const double *w, const uint64_t *zmask, const double c[2], double *norm2) {
+  int rc = check_zpoly(h, "apply_zpoly", nterms, w, zmask);
+  if (rc) return rc;
+  if (!c) return fail(QH_ERR_ARG, "apply_zpoly: null c");
+  if (!std::isfinite(c[0]) || !std::isfinite(c[1])) return fail(QH_ERR_ARG, "apply_zpoly: c = %g%+gi is not finite", c[0], c[1]);
+  if (h->dry) return fail(QH_ERR_ARG, "apply_zpoly: not on a dry (planner-only) handle");
+  if ((rc = enter(h))) return rc;          // a barrier: what is queued runs first, on whatever layout it leaves
+  if (nterms == 0 || (c[0] == 0.0 && c[1] == 0.0)) return norm2 ? masked_norm2(h, 0ull, 0ull, norm2) : QH_OK;
+  std::vector<qh::ZpolyTerm> terms;
+  qh::ZpolyPlan p;
+  plan_zpoly(h, nterms, w, zmask, &terms, &p);
+  qh::ZpolyArgs a{};
+  if ((rc = stage_zpoly(h, p, "qh_apply_zpoly", &a))) return rc;
+  a.cre = c[0];
+  a.cim = c[1];
+  a.norm = norm2 ? 1 : 0;
+  SlabSum sum{h};
+  if (norm2) HIP_TRY(sum.reserve(std::max<uint64_t>(qh::kPauliBlocks, 8), 1, 1));
+  launch_zpoly(h, p, a, false, sum.slab);
+  if (norm2) sum.fold(p.nblk, 1, 1);
+  if ((rc = check_launch(h))) return rc;
+  HIP_TRY(h->zpoly.commit(h->stream, 0));
+  if (norm2 && (rc = sum.get(norm2, 1, "qh_apply_zpoly"))) return rc;
+  const uint64_t shard_bytes = (1ull << h->nloc) * h->amp_bytes();
+  h->stats.gates_submitted += 1;
+  h->stats.kernels_launched += 1;      // (the fold is not counted, as in qh_axpby)
+  h->stats.bytes_swept += 2 * shard_bytes;
+  h->stats.bytes_algorithmic += 2 * shard_bytes;
+  return QH_OK;
+}
+
+int qh_expect_zpoly(qh_handle h, uint64_t nterms, const double *w, const uint64_t *zmask, double out[3]) {
+  int rc = check_zpoly(h, "expect_zpoly", nterms, w, zmask);
+  if (rc) return rc;
+  if (!out) return fail(QH_ERR_ARG, "expect_zpoly: null out");
+  if (h->dry) return fail(QH_ERR_ARG, "expect_zpoly: not on a dry (planner-only) handle");
+  if ((rc = enter(h))) return rc;
+  if (nterms == 0) {
+    double n2 = 0.0;
+    if ((rc = masked_norm2(h, 0ull, 0ull, &n2))) return rc;
+    out[0] = n2;
+    out[1] = out[2] = 0.0;
+    return QH_OK;
+  }
+  std::vector<qh::ZpolyTerm> terms;
+  qh::ZpolyPlan p;
+  plan_zpoly(h, nterms, w, zmask, &terms, &p);
+  qh::ZpolyArgs a{};
+  if ((rc = stage_zpoly(h, p, "qh_expect_zpoly", &a))) return rc;
+  SlabSum sum{h};
+  HIP_TRY(sum.reserve(std::max<uint64_t>(qh::kPauliBlocks, 8), 3, 3));
+  launch_zpoly(h, p, a, true, sum.slab);
+  sum.fold(p.nblk, 3, 3);
+  if ((rc = check_launch(h))) return rc;
+  HIP_TRY(h->zpoly.commit(h->stream, 0));
+  if ((rc = sum.get(out, 3, "qh_expect_zpoly"))) return rc;
+  const uint64_t shard_bytes = (1ull << h->nloc) * h->amp_bytes();
+  h->stats.kernels_launched += 1;
+  h->stats.bytes_swept += shard_bytes;
+  h->stats.bytes_algorithmic += shard_bytes;
   return QH_OK;
 }
 

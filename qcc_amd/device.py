@@ -589,6 +589,42 @@ class DeviceState:
     tl = [{k: int(getattr(terms[j], k)) for k, _ in native.QhPauliTerm._fields_} for j in range(n)]
     return tl, [runs[r].as_dict() for r in range(nr.value)]
 
+  # -- Z-polynomial operators ------------------------------------------------------
+  @staticmethod
+  def _zpoly_arrays(weights, zmasks):
+    w = np.ascontiguousarray([float(v) for v in weights], dtype=np.float64)
+    z = np.ascontiguousarray([int(v) for v in zmasks], dtype=np.uint64)
+    if w.size != z.size:
+      raise ValueError(f'zpoly: {w.size} weights, {z.size} z masks')
+    return (w, z), w.ctypes.data_as(_dp), z.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+
+  def apply_zpoly(self, weights, zmasks, c, norm=False):
+    """a_i *= exp(c f(i)) in place, f(i) = sum_t weights[t] (-1)^popcount(i & zmasks[t]) over LOGICAL bits, complex c
+    (qh_apply_zpoly: one pass over the state for any number of terms).  Queued gates run first.  norm=True returns
+    sum |a|^2 of the result over this shard, otherwise None."""
+    keep, wp, zp = self._zpoly_arrays(weights, zmasks)
+    c = complex(c)
+    cc = (ctypes.c_double * 2)(c.real, c.imag)
+    n2 = ctypes.c_double() if norm else None
+    native.check(self.lib.qh_apply_zpoly(self.h, int(keep[0].size), wp, zp, cc, ctypes.byref(n2) if norm else None))
+    return n2.value if norm else None
+
+  def expect_zpoly(self, weights, zmasks):
+    """(norm2, mean, second) = sum |a_i|^2 (1, f(i), f(i)^2) over this shard, not normalised (qh_expect_zpoly: one read of
+    the state for any number of terms)."""
+    keep, wp, zp = self._zpoly_arrays(weights, zmasks)
+    out = (ctypes.c_double * 3)()
+    native.check(self.lib.qh_expect_zpoly(self.h, int(keep[0].size), wp, zp, out))
+    return float(out[0]), float(out[1]), float(out[2])
+
+  def zpoly_plan(self, weights, zmasks):
+    """How the terms fall on the layout right now (qh_zpoly_plan), as a dict: counts by class, per-term physical masks,
+    folded weights and classes, the groups' low masks, the kernel and its grid."""
+    keep, wp, zp = self._zpoly_arrays(weights, zmasks)
+    info = native.QhZpolyInfo()
+    native.check(self.lib.qh_zpoly_plan(self.h, int(keep[0].size), wp, zp, ctypes.byref(info)))
+    return info.as_dict()
+
   def inner_plan(self, other):
     """How inner(other) would walk the two states right now (qh_inner_plan), as a dict."""
     t = native.QhInnerTiles()

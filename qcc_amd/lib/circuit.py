@@ -1387,6 +1387,89 @@ class qc:
             self._rescale(norm2, 'pauli_project')
         return norm2
 
+    # Diagonal Z-polynomial operators (eager extensions with the standing of diagonal and evolve: not recorded in the IR).  A
+    # classical cost function C = sum_t w_t Z..Z is one multiplication per amplitude (qh_apply_zpoly) and one read for
+    # <C> and <C^2> (qh_expect_zpoly), whatever the number of terms.  With a device that has no apply_zpoly (and in aliased
+    # mode) the same formula runs over qc.psi on the host.
+    def _zpoly_terms(self, terms, what):
+        coeffs, xs, zs = self._pauli_terms(terms, what)
+        if any(x for x in xs):
+            raise ValueError(f'{what}: Z and I only (a cost function is diagonal)')
+        if any(c.imag != 0 for c in coeffs):
+            raise ValueError(f'{what}: real weights only')
+        return [c.real for c in coeffs], zs
+
+    def _zpoly_host_f(self, ws, zs):
+        """f(i) over every index, float64"""
+        idx = np.arange(1 << self._nbits, dtype=np.uint64)
+        f = np.zeros(idx.size, dtype=np.float64)
+        for w, z in zip(ws, zs):
+            par = np.zeros(idx.size, dtype=np.uint64)
+            for bit in range(self._nbits):
+                if (z >> bit) & 1:
+                    par ^= (idx >> np.uint64(bit)) & np.uint64(1)
+            f += w * (1.0 - 2.0 * par.astype(np.float64))
+        return f
+
+    def _zpoly(self, ws, zs, c, norm=False):
+        dev = self._ensure_device()
+        if hasattr(dev, 'apply_zpoly') and not self._alias:
+            norm2 = dev.apply_zpoly(ws, zs, c, norm=norm)
+            self._gate_done()
+            return float(norm2) if norm else None
+        amps = np.asarray(self.psi).reshape(-1)
+        new = (amps.astype(np.complex128) * np.exp(complex(c) * self._zpoly_host_f(ws, zs))).astype(amps.dtype)
+        self.psi = new
+        return float(np.vdot(new.astype(np.complex128), new.astype(np.complex128)).real) if norm else None
+
+    def phase_polynomial(self, terms, gamma):
+        """exp(-i gamma C) for C = sum_t w_t P_t, terms = [(w_t, paulis_t), ...] with Z and I only and real w_t: the QAOA
+        cost layer, one pass over the state."""
+        ws, zs = self._zpoly_terms(terms, 'phase_polynomial')
+        self._zpoly(ws, zs, complex(0.0, -float(gamma)))
+
+    def cost_filter(self, terms, tau, normalize=True):
+        """exp(-tau C): imaginary time under a classical cost.  Returns the norm^2 of the result before any normalisation;
+        normalize=True follows with scale(1 / sqrt(norm^2)) and raises ValueError where the result is 0."""
+        ws, zs = self._zpoly_terms(terms, 'cost_filter')
+        norm2 = self._zpoly(ws, zs, complex(-float(tau), 0.0), norm=True)
+        if normalize:
+            self._rescale(norm2, 'cost_filter')
+        return norm2
+
+    def cost_expectation(self, terms, moments=False):
+        """<C>, or (<C>, <C^2>) with moments=True, in one read of the state.  Not divided by the norm, like expectation."""
+        ws, zs = self._zpoly_terms(terms, 'cost_expectation')
+        dev = self._ensure_device()
+        if hasattr(dev, 'expect_zpoly') and not self._alias:
+            _, mean, second = dev.expect_zpoly(ws, zs)
+        else:
+            a = np.asarray(self.psi).reshape(-1).astype(np.complex128)
+            p, f = a.real * a.real + a.imag * a.imag, self._zpoly_host_f(ws, zs)
+            mean, second = float(np.dot(p, f)), float(np.dot(p, f * f))
+        return (float(mean), float(second)) if moments else float(mean)
+
+    @staticmethod
+    def maxcut_terms(edges):
+        """[(u, v, w), ...] -> the terms w Z_u Z_v of a MaxCut cost function"""
+        terms = []
+        for e in edges:
+            try:
+                u, v, w = e
+            except (TypeError, ValueError):
+                raise ValueError(f'maxcut_terms: edge {e!r} is not (u, v, w)') from None
+            if u == v:
+                raise ValueError(f'maxcut_terms: edge {e!r} joins a node to itself')
+            terms.append((float(w), {int(u): 'Z', int(v): 'Z'}))
+        return terms
+
+    def qaoa_layer(self, terms, gamma, beta):
+        """One QAOA layer: exp(-i gamma C), then the mixer rx(q, 2 beta) = exp(-i beta X_q) on every qubit through the
+        normal queue."""
+        self.phase_polynomial(terms, gamma)
+        for q in range(self._nbits):
+            self.rx(q, 2.0 * float(beta))
+
     # Two states (extensions; the reference compares states on the host: State.diff, the swap and Hadamard tests).  With a
     # device that cannot clone / copy_from / inner, the amplitudes go through qc.psi on the host instead.
     def snapshot(self):
