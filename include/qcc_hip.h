@@ -302,7 +302,7 @@ int qh_exchange_stats(qh_handle h, qh_xstats *out);
 int qh_comm_allreduce_sum(qh_handle h, double *inout, int count);
 
 /* ---- device-side readers (state.py:24-78) ------------------ */
-int qh_norm2(qh_handle h, double *out);                       /* sum |a|^2 of the shard */
+int qh_norm2(qh_handle h, double *out);                       /* sum |a|^2 of the shard, in the readers' fixed order: same state and layout, same bits */
 /* One amplitude by LOGICAL index (state.py:31-40 ampl/prob), read where it lives now: no
  * re-layout, 16 bytes over PCIe.  QH_ERR_NONLOCAL if another shard holds it.                */
 int qh_amplitude(qh_handle h, uint64_t logical_index, double out[2]);

@@ -1205,14 +1205,17 @@ int qh_apply_stream(qh_handle h, uint64_t count, const int32_t *ops, const doubl
 
 // sum of |amplitude|^2 over the local indices i with (i & mask) == want
 static int masked_norm2(qh_handle h, uint64_t mask, uint64_t want, double *out) {
-  HIP_TRY(hipMemsetAsync(h->d_red(), 0, sizeof(double), h->stream));
   const uint64_t n = 1ull << h->nloc;
+  const unsigned nblk = grid_for(n, 4096);
+  SlabSum sum{h};                                           // one slab row per block, folded in block order: no atomics
+  HIP_TRY(sum.reserve(std::max<uint64_t>(nblk, 8), 1, 1));
   with_real(h, [&](auto x) {
     using R = decltype(x);
-    hipLaunchKernelGGL(qh::k_norm2<R>, dim3(grid_for(n, 4096)), dim3(256), 0, h->stream,
-                       (const typename qh::AmpT<R>::type *)h->d_psi, n, mask, want, h->d_red());
+    hipLaunchKernelGGL(qh::k_norm2<R>, dim3(nblk), dim3(256), 0, h->stream,
+                       (const typename qh::AmpT<R>::type *)h->d_psi, n, mask, want, sum.slab);
   });
-  return read_back(h, out, h->d_red(), sizeof(double));
+  sum.fold(nblk, 1, 1);
+  return sum.get(out, 1, "norm2 reader");
 }
 
 int qh_norm2(qh_handle h, double *out) {

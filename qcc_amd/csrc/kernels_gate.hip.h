@@ -358,12 +358,12 @@ __global__ __launch_bounds__(256) void k_permute_bits(const typename AmpT<R>::ty
 }
 
 // ---- readers ----------------------------------------------------
-// out[0] += sum |a|^2 over indices i with (i & mask) == want (mask==0: all).  The block's sum is formed in the fixed order
-// of kernels_common.hip.h; the blocks then meet in one atomic add, so the result depends on their order of arrival.
+// slab[block] = sum |a|^2 over the block's indices i with (i & mask) == want (mask==0: all), in the fixed order of
+// kernels_common.hip.h; k_slab_fold then adds the rows in block order.  No atomics: the same state in the same layout gives
+// the same bits (qh_expect_zpoly and qh_apply_zpoly hand this sum out for an empty term list and promise as much).
 template <typename R>
 __global__ __launch_bounds__(256) void k_norm2(const typename AmpT<R>::type *__restrict__ psi,
-                                                uint64_t n, uint64_t mask, uint64_t want, double *out) {
-  __shared__ double part[4];
+                                                uint64_t n, uint64_t mask, uint64_t want, double *__restrict__ slab) {
   double acc = 0.0;
   // four independent (non-temporal) loads in flight per thread: a read-only pass is bound by the bytes in flight
   const uint64_t stride = (uint64_t)gridDim.x * 256;
@@ -386,9 +386,8 @@ __global__ __launch_bounds__(256) void k_norm2(const typename AmpT<R>::type *__r
       acc += prob_sum(a.x, a.y);
     }
   }
-  wave_partial(acc, part);
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, four_waves(part));
+  const double row[1] = {acc};
+  block_row_sum(row, slab);
 }
 
 // zero every amplitude whose bit `bit` differs from `value`.

@@ -35,7 +35,9 @@ def np_qubit_density(psi, qubits):
 
 def tolerance(rho, m):
   """(2^k, 2^k) float64: the worst-case bound of a sum of m products in double, whatever the order:
-  4 m 2^-53 sqrt(rho_rr rho_cc)."""
+  4 m 2^-53 sqrt(rho_rr rho_cc).  On the diagonal the products are the m probabilities |a|^2 >= 0 that qh_marginal sums too (each
+  formed with at most three roundings, added in some order: an error below (m + 2) 2^-53 rho_rr), so the same bound holds the
+  marginal to the exact value as well; rho_rr and the marginal, each within it, lie within twice the bound of each other."""
   d = np.sqrt(np.abs(np.real(np.diag(rho))))
   return 4.0 * m * 2.0 ** -53 * np.outer(d, d)
 

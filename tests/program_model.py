@@ -18,14 +18,16 @@ np_release, select_util.np_select / np_topk / fma_probs, test_dense_cpu.dense_re
 diag_reference, test_expect_cpu.np_expect, test_perm_cpu.perm_reference (and the tile rule of qh_perm_plan it states),
 pauli_util.np_pauli_sum and pauli_util.bound (qh_apply_pauli_sum and its derived error bound),
 pauli_product_util.np_pauli_product, bound and greedy_runs (qh_apply_pauli_product, its derived bound and its run rule),
-shard_util.check_exact_cdf (the inverse CDF of qh_sample in physical order)."""
+shard_util.check_exact_cdf (the inverse CDF of qh_sample in physical order), density_util.np_reduced_density and
+density_util.tolerance (qh_reduced_density and its derived bound), zpoly_util.np_apply, np_moments, apply_bound and moment_bound
+(qh_apply_zpoly / qh_expect_zpoly and their derived bounds)."""
 import os
 import sys
 
 import numpy as np
 
 from qcc_amd import native
-from tests import oracle_lib, pauli_product_util as ppu, pauli_util, shard_util
+from tests import density_util as du, oracle_lib, pauli_product_util as ppu, pauli_util, shard_util, zpoly_util as zu
 from tests.fake_device import np_keep, np_marginal
 from tests.resize_util import np_extend, np_release
 from tests.select_util import fma_probs, np_select, np_topk
@@ -45,11 +47,13 @@ MAX_LIVE = 4
 LINEAR, TILES, GATHER = native.QH_INNER_LINEAR, native.QH_INNER_TILES, native.QH_INNER_GATHER
 
 BARRIERS = ('matrix', 'mux', 'diag', 'perm', 'scale', 'project_bit', 'project_bits')
-READERS = ('norm2', 'prob_bit', 'marginal', 'sample', 'expect', 'argmax', 'amplitude', 'amplitudes', 'select', 'topk')
+READERS = ('norm2', 'prob_bit', 'marginal', 'sample', 'expect', 'argmax', 'amplitude', 'amplitudes', 'select', 'topk', 'reduced_density',
+           'expect_zpoly')
 HANDLE_STEPS = ('clone', 'copy', 'extend', 'release', 'close')
 TWO_STATE = ('inner', 'axpby')
-# pauli_sum reads one handle and replaces another whole (or makes a new one); pauli_product works in place, in runs of kernels
-OPERATOR_STEPS = ('pauli_sum', 'pauli_product')
+# pauli_sum reads one handle and replaces another whole (or makes a new one); pauli_product works in place, in runs of kernels;
+# zpoly works in place in one kernel
+OPERATOR_STEPS = ('pauli_sum', 'pauli_product', 'zpoly')
 LAYOUT_STEPS = ('flush', 'set_relayout', 'remap')
 KINDS = ('gates',) + BARRIERS + READERS + HANDLE_STEPS + TWO_STATE + OPERATOR_STEPS + LAYOUT_STEPS + ('refused',)
 
@@ -58,10 +62,11 @@ KINDS = ('gates',) + BARRIERS + READERS + HANDLE_STEPS + TWO_STATE + OPERATOR_ST
 # each at both widths; the coverage table of the CPU test is what this seed list was chosen by
 # (re-chosen when 'perm' and then 'pauli_sum' became kinds: one stream draws the kinds, so a new kind changes every program of
 # every seed; no seed has left the list.  With 'pauli_product': own 44, 82, shard 25, 32, 64, attached 176 and mapped 56, 73 joined, each for
-# a condition of the coverage tables that the other programs no longer or never met -- HISTORY.md T4 names them)
-FIXED = [('own', seed) for seed in list(range(21)) + [42, 44, 48, 60, 82, 88, 92, 139]] + \
-        [('shard', seed) for seed in list(range(6)) + [15, 22, 24, 25, 32, 34, 54, 64]] + \
-        [('attached', seed) for seed in list(range(4)) + [5, 7, 11, 176]] + [('mapped', seed) for seed in list(range(4)) + [15, 42, 56, 73]]
+# a condition of the coverage tables that the other programs no longer or never met -- HISTORY.md T4 names them.  With 'reduced_density',
+# 'expect_zpoly' and 'zpoly': own 86, 138, shard 8, 67 and attached 29, 99, 235, 278 joined, likewise -- HISTORY.md T5 names them)
+FIXED = [('own', seed) for seed in list(range(21)) + [42, 44, 48, 60, 82, 86, 88, 92, 138, 139]] + \
+        [('shard', seed) for seed in list(range(6)) + [8, 15, 22, 24, 25, 32, 34, 54, 64, 67]] + \
+        [('attached', seed) for seed in list(range(4)) + [5, 7, 11, 29, 99, 176, 235, 278]] + [('mapped', seed) for seed in list(range(4)) + [15, 42, 56, 73]]
 # planner variants of tests/test_gpu_fuzz.py, each on 'own' programs whose first handle is large enough for sweeps
 ENV_VARIANTS = [{'QH_RELAYOUT': '0'}, {'QH_WAVE_BITS': '2', 'QH_LANE_VALU': '2'}, {'QH_SEATS': '2', 'QH_WAVE_BITS': '1'}]
 
@@ -206,6 +211,134 @@ def pauli_product_walk(nloc, bw, run):
   return 'lane' if xi and xi.bit_length() - 1 <= PAULI_LANE_PIVOT_MAX else 'pair'
 
 
+# ---- reduced density matrices: what qh_density_plan must say of a bit map (plan_density of density_plan.h) -----------------------
+DENSITY_MAX_BITS = native.QH_DENSITY_MAX_BITS
+DENSITY_TILE_BITS = 6         # kDensityTileBits: a tile has at most 64 rows; k = 7, 8 are cut into 2, 4 blocks of 64 rows
+DENSITY_LDS_BITS = 11         # kDensityLdsBits: amplitudes of (tiles x chunk) a workgroup keeps in LDS
+DENSITY_GATHER_BELOW = 8      # kDensityGatherBelow: fewer local bits take QH_DENSITY_GATHER
+DENSITY_MAX_WGS, DENSITY_SLAB_BYTES = 2048, 32 << 20
+DENSITY_TABLES = ('row_pos', 'row_bit', 'col_pos', 'rest_pos')
+
+
+def density_rule(nloc, bm, bits):
+  """qh_density_plan from a bit map, as include/qcc_hip.h states it: the register's positions ascending (row_pos) and which
+  listed bit each holds (row_bit); the environment's positions ascending, the lowest chunk_bits of them the columns of a chunk,
+  the others the chunk number; min(k, 6) row bits per tile, nb (nb + 1) / 2 block pairs of nb = 2^(k - tile_bits) row blocks;
+  the workgroups per pair a power of two bounded by the chunks, by 2048 workgroups and by 32 MiB of slab in all"""
+  k, pos = len(bits), [bm[b] for b in bits]
+  rows = sorted(pos)
+  env = [p for p in range(nloc) if p not in pos]
+  out = {'k': k, 'row_pos': rows, 'row_bit': [pos.index(p) for p in rows]}
+  if nloc < DENSITY_GATHER_BELOW:
+    out.update(path=native.QH_DENSITY_GATHER, tile_bits=k, chunk_bits=0, nrest=len(env), block_pairs=1, wg_per_pair=1,
+               chunks_per_wg=1 << len(env), slab_bytes=0, amps_swept=1 << nloc, col_pos=[], rest_pos=env)
+    return out
+  kt = min(k, DENSITY_TILE_BITS)
+  nb = 1 << (k - kt)
+  pairs = nb * (nb + 1) // 2
+  cb = min(DENSITY_LDS_BITS - kt - (1 if nb > 1 else 0), len(env))
+  nchunks, row_bytes = 1 << (len(env) - cb), 16 << (2 * kt)
+  cap = min(DENSITY_SLAB_BYTES // row_bytes, DENSITY_MAX_WGS) // pairs
+  wg = 1
+  while wg * 2 <= cap and wg * 2 <= nchunks:
+    wg *= 2
+  out.update(path=native.QH_DENSITY_TILES, tile_bits=kt, chunk_bits=cb, nrest=len(env) - cb, block_pairs=pairs, wg_per_pair=wg,
+             chunks_per_wg=nchunks // wg, slab_bytes=row_bytes * wg * pairs, amps_swept=1 << (nloc + k - kt), col_pos=env[:cb], rest_pos=env[cb:])
+  return out
+
+
+def density_plan_view(plan):
+  """a plan of qh_density_plan (QhDensityTiles.as_dict) with its four position tables cut to their lengths"""
+  out = dict(plan)
+  for name, count in zip(DENSITY_TABLES, (plan['k'], plan['k'], plan['chunk_bits'], plan['nrest'])):
+    out[name] = [int(x) for x in plan[name][:count]]
+  return out
+
+
+def local_view(vec, n, held):
+  """a shard's amplitudes in the logical order of its LOCAL bits (held bits dropped from the index), and the number every local
+  logical bit has there: what density_util.np_reduced_density takes for a shard"""
+  loc = [b for b in range(n) if b not in held]
+  return np.asarray(vec)[mine_of(n, held).astype(np.int64)], {b: j for j, b in enumerate(loc)}
+
+
+# ---- Z-polynomials: what qh_zpoly_plan must say of a bit map (zpoly_plan of zpoly_plan.h) ----------------------------------------
+ZPOLY_MAX_TERMS = native.QH_ZPOLY_MAX_TERMS
+ZPOLY_LANES = 64              # the kernels deal a segment's terms to 64 lanes before an xor tree
+ZPOLY_BLOCKS = 4096           # kPauliBlocks: blocks at most, each a contiguous run of chunks
+ZPOLY_MODEL_BUDGET = 1 << 25  # nterms * 2^nloc of a drawn step: the NumPy model evaluates f term by term
+ZPOLY_CLASSES = {native.QH_ZPOLY_CONST: 'CONST', native.QH_ZPOLY_HIGH: 'HIGH', native.QH_ZPOLY_LOW: 'LOW', native.QH_ZPOLY_STRADDLE: 'STRADDLE'}
+ZPOLY_GROUP_KINDS = ('thread-only', 'register-index/half-only', 'mixed')
+
+
+def zpoly_main_shape(nloc, bw):
+  return pauli_main_shape(nloc, bw)                          # whole chunks of 2^11 items; smaller states take k_zpoly_small
+
+
+def zpoly_rule(nloc, bw, bm, shard, weights, zmasks):
+  """qh_zpoly_plan from a bit map, as include/qcc_hip.h states it: per term the physical local mask, the weight negated where
+  the parity of shard & (the held z bits) is odd, and the class by where the mask lies about low_bits (11 item bits + the
+  half bit at complex64 on the main kernel, every local bit on the small one); the distinct low masks of the straddling terms
+  in order of first appearance; the grid of pauli_grid"""
+  ab = 0 if bw == 128 else 1
+  main = zpoly_main_shape(nloc, bw)
+  low_bits = PAULI_CHUNK_BITS + ab if main else nloc
+  pz, w, cls, groups = [], [], [], []
+  for wt, z in zip(weights, zmasks):
+    local = sum(1 << bm[b] for b in range(len(bm)) if (int(z) >> b) & 1 and bm[b] < nloc)
+    held = sum(1 << (bm[b] - nloc) for b in range(len(bm)) if (int(z) >> b) & 1 and bm[b] >= nloc)
+    lo, hi = local & ((1 << low_bits) - 1), local >> low_bits
+    c = native.QH_ZPOLY_CONST if local == 0 else native.QH_ZPOLY_STRADDLE if lo and hi else native.QH_ZPOLY_HIGH if hi else native.QH_ZPOLY_LOW
+    pz.append(local)
+    w.append(-float(wt) if _popcount(shard & held) & 1 else float(wt))
+    cls.append(c)
+    if c == native.QH_ZPOLY_STRADDLE and lo not in groups:
+      groups.append(lo)
+  nchunks = 1 << (nloc - low_bits) if main else 0
+  nblk = min(nchunks, ZPOLY_BLOCKS) if main else ((1 << nloc) + 255) // 256
+  return {'nterms': len(pz), 'nconst': cls.count(native.QH_ZPOLY_CONST), 'nhigh': cls.count(native.QH_ZPOLY_HIGH),
+          'nlow': cls.count(native.QH_ZPOLY_LOW), 'nstraddle': cls.count(native.QH_ZPOLY_STRADDLE), 'ngroups': len(groups), 'nblk': nblk,
+          'kernel': native.QH_ZPOLY_KERNEL_MAIN if main else native.QH_ZPOLY_KERNEL_SMALL, 'low_bits': low_bits, 'cpb': nchunks // nblk if main else 0,
+          'group_mask': groups, 'pz': pz, 'w': w, 'cls': cls}
+
+
+def zpoly_group_kind(low_mask, bw):
+  """where a group's low mask lies: on thread bits only (item bits 0-7), on register-index / half bits only, or on both"""
+  thread = 255 << (0 if bw == 128 else 1)
+  return ZPOLY_GROUP_KINDS[0 if not low_mask & ~thread else 1 if not low_mask & thread else 2]
+
+
+def zpoly_segments(plan):
+  """the term counts of the main kernel's segments: segment 0 the CONST and HIGH terms, then one per group"""
+  lowm = (1 << plan['low_bits']) - 1
+  seg = [plan['nconst'] + plan['nhigh']] + [0] * plan['ngroups']
+  for z, c in zip(plan['pz'], plan['cls']):
+    if c == native.QH_ZPOLY_STRADDLE:
+      seg[1 + plan['group_mask'].index(z & lowm)] += 1
+  return seg
+
+
+_ZPOLY_F = []                 # the last few (key, f): a step's f is asked by the generator's trial, the models and the runner
+
+
+def zpoly_f(n, held, weights, zmasks):
+  """zpoly_util.np_f at the global logical indices the shard holds (ascending), kept for the next caller that asks the same"""
+  key = (n, tuple(sorted(held.items())), np.asarray(weights, dtype=np.float64).tobytes(), tuple(int(z) for z in zmasks))
+  for k, f in _ZPOLY_F:
+    if k == key:
+      return f
+  f = zu.np_f(mine_of(n, held), weights, zmasks)
+  f.setflags(write=False)
+  _ZPOLY_F.insert(0, (key, f))
+  del _ZPOLY_F[3:]
+  return f
+
+
+def zpoly_c_kind(c):
+  c = complex(c)
+  return 'zero' if c == 0 else 're0' if c.real == 0 else 'im0' if c.imag == 0 else 'general'
+
+
 TOL = 1e-12                   # TOL of tests/test_gpu_inner.py: readers that accumulate in double from the stored amplitudes
 CHAIN_TOL_128 = 2e-11         # tools/fuzz_parity.py, complex128
 
@@ -304,6 +437,9 @@ class ModelState:
     # relayout mode as include/qcc_hip.h describes it: -1 undecided (decided by the first fused flush), 0 off, 1 on; and
     # whether the handle owns HBM memory (attached and host-mapped ones do not: they never re-lay out)
     self.mode, self.owns = {}, {}
+    # the bit map a handle would have if no relayout sweep ever moved it: what the generator aims physical positions by (the
+    # runner reads the real one; nothing is compared with this)
+    self.bm = {}
 
   def _rnd(self, x):
     return np.ascontiguousarray(x, dtype=np.complex128).astype(self.dtype) if self.dtype != np.complex128 else np.ascontiguousarray(x, dtype=np.complex128)
@@ -364,6 +500,7 @@ class ModelState:
       held = {b: (shard >> (bm[b] - nloc)) & 1 for b in range(n) if bm[b] >= nloc}
       mask, value = held_mask_value(held)
       self.put(h, np.where(np_keep(1 << n, mask, value), psi, 0), n, held)
+      self.bm[h] = list(bm)
       if s['mode'] in ('attached', 'mapped'):
         self.mode[h], self.owns[h] = 0, False
 
@@ -424,6 +561,18 @@ class ModelState:
     w = self.wide(s['h'])
     return np.array([np_expect(w, x, z) for x, z in zip(s['x'], s['z'])], dtype=np.float64)
 
+  def _reduced_density(self, s):
+    h = s['h']
+    self.run(h)
+    psi, number = local_view(self.wide(h), self.n[h], self.held[h])
+    return du.np_reduced_density(psi, [number[b] for b in s['bits']])
+
+  def _expect_zpoly(self, s):
+    h = s['h']
+    self.run(h)
+    mine = mine_of(self.n[h], self.held[h]).astype(np.int64)
+    return zu.np_moments(self.wide(h)[mine], s['w'], s['z'], f=zpoly_f(self.n[h], self.held[h], s['w'], s['z']))
+
   def _probs(self, h):
     mine = mine_of(self.n[h], self.held[h])
     a = self.wide(h)[mine.astype(np.int64)]
@@ -459,11 +608,13 @@ class ModelState:
   def _clone(self, s):
     self.run(s['h'])
     self.put(s['new'], self.v[s['h']].copy(), self.n[s['h']], self.held[s['h']])
+    self.bm[s['new']] = list(self.bm[s['h']])
 
   def _copy(self, s):
     self.run(s['src'])
     self.drop(s['h'])
     self.put(s['h'], self.v[s['src']].copy())
+    self.bm[s['h']] = list(self.bm[s['src']])
 
   def _extend(self, s):
     h, k = s['h'], s['k']
@@ -474,6 +625,8 @@ class ModelState:
     else:
       f = np.asarray(s['amps'], dtype=np.complex128)
     self.put(s['new'], np_extend(self.wide(h), f), self.n[h] + k, {b + k: v for b, v in self.held[h].items()})
+    nl = self.nloc(h)
+    self.bm[s['new']] = list(range(nl, nl + k)) + [p if p < nl else p + k for p in self.bm[h]]
 
   def _release(self, s):
     h, bits = s['h'], s['bits']
@@ -481,10 +634,12 @@ class ModelState:
     small, kept, dropped = np_release(self.wide(h), bits, s['value'])
     held = {b - sum(1 for x in bits if x < b): v for b, v in self.held[h].items()}
     self.put(s['new'], small, self.n[h] - len(bits), held)
+    gone = sorted(self.bm[h][b] for b in bits)
+    self.bm[s['new']] = [p - sum(1 for r in gone if r < p) for b, p in enumerate(self.bm[h]) if b not in bits]
     return kept, dropped
 
   def _close(self, s):
-    for d in (self.v, self.base, self.q, self.n, self.held, self.mode, self.owns):
+    for d in (self.v, self.base, self.q, self.n, self.held, self.mode, self.owns, self.bm):
       d.pop(s['h'])
 
   # -- two states ----------------------------------------------------------------------------------------------------------------
@@ -514,6 +669,7 @@ class ModelState:
       d = s['dst']
       self.drop(d)
       self.put(d, out)
+    self.bm[d] = list(self.bm[src])
     return self.norm(d)
 
   def _pauli_product(self, s):
@@ -522,6 +678,18 @@ class ModelState:
     h = s['h']
     self.run(h)
     self.put(h, ppu.np_pauli_product(self.wide(h), s['a'], s['b'], s['x'], s['z']))
+    return self.norm(h)
+
+  def _zpoly(self, s):
+    """a_i *= exp(c f(i)) in place on the amplitudes the shard holds, f over the GLOBAL logical index (a held z bit is the plain
+    sign of that index); no terms or c == (0, 0): nothing is touched"""
+    h = s['h']
+    self.run(h)
+    if len(s['z']) and complex(s['c']) != 0:
+      mine = mine_of(self.n[h], self.held[h]).astype(np.int64)
+      out = np.zeros(1 << self.n[h], dtype=np.complex128)
+      out[mine] = zu.np_apply(self.wide(h)[mine], s['w'], s['z'], s['c'], f=zpoly_f(self.n[h], self.held[h], s['w'], s['z']))
+      self.put(h, out)
     return self.norm(h)
 
   # -- layout -------------------------------------------------------------------------------------------------------------------
@@ -541,6 +709,8 @@ class ModelState:
     h = s['h']
     self.run(h)
     self.put(h, swap_logical_bits(self.v[h], self.n[h], s['a'], s['b']))
+    bm = self.bm[h]
+    bm[s['a']], bm[s['b']] = bm[s['b']], bm[s['a']]
 
   def _refused(self, s):
     pass
@@ -589,6 +759,7 @@ class _Gen:
     self.next_slot = 0
     self.refused = 0
     self.pp_calls = self.pp_rejected = 0                     # k_pauli_product: draws made, draws that missed M <= 8 or the norm range
+    self.zp_calls = self.zp_rejected = 0                     # k_zpoly: draws made, draws whose trial left the norm range
 
   def live(self):
     return sorted(self.m.v)
@@ -1160,6 +1331,126 @@ class _Gen:
     self.emit({'op': 'pauli_product', 'h': h, 'a': a, 'b': b, 'x': x, 'z': z, 'norm': bool(rng.integers(2))})
     return True
 
+  def pick_half_queued(self):
+    """a usable handle in whatever condition the program left it, half the time one with a burst queued"""
+    rng, m = self.rng, self.m
+    c = [x for x in self.live() if self.usable(x)]
+    if not c:
+      return None
+    queued = [x for x in c if m.q[x]]
+    return queued[int(rng.integers(len(queued)))] if queued and rng.random() < 0.5 else c[int(rng.integers(len(c)))]
+
+  def k_reduced_density(self):
+    """rho of k local logical bits in random list order; k from the bands whose edges are the kernels' (k <= 2 straight from memory,
+    k < 6 folded groups, 6 one tile, 7 and 8 three and ten block pairs) and the whole shard"""
+    rng, m = self.rng, self.m
+    h = self.pick_half_queued()
+    if h is None:
+      return False
+    last = self.steps[-1]                                    # half the time right behind extend or copy_from, on the handle they made or filled
+    fresh = last.get('new') if last['op'] == 'extend' else last['h'] if last['op'] == 'copy' else None
+    if fresh is not None and self.usable(fresh) and rng.random() < 0.5:
+      h = fresh
+    loc = m.local_bits(h)                                    # on a shard: only bits the shard index does not hold
+    nloc, kmax = len(loc), min(DENSITY_MAX_BITS, len(loc))
+    bands = [(lo, min(hi, kmax)) for lo, hi in ((0, 0), (1, 2), (3, 5), (6, 6), (7, 7), (8, 8)) if lo <= kmax]
+    if nloc <= DENSITY_MAX_BITS:
+      bands.append((nloc, nloc))                             # k = nloc: the outer product of the shard's state
+    lo, hi = bands[int(rng.integers(len(bands)))]
+    k = int(rng.integers(lo, hi + 1))
+    if nloc >= 18 and rng.random() < 0.6:
+      k = 8                                                  # with k = 7 from 19 bits on the only way to chunks_per_wg > 1 below MAX_BITS
+    if rng.random() < 1 / 3:                                 # the bits that sit lowest in the map (as far as the model knows it) among them
+      low = sorted(loc, key=lambda b: m.bm[h][b])[:min(k, int(rng.integers(1, 3)))]
+      rest = [b for b in loc if b not in low]
+      bits = low + [int(b) for b in rng.choice(rest, size=k - len(low), replace=False)]
+      bits = [int(bits[j]) for j in rng.permutation(len(bits))]
+    else:
+      bits = [int(b) for b in rng.choice(loc, size=k, replace=False)]      # in random order, not ascending: row_bit is no identity
+    self.emit({'op': 'reduced_density', 'h': h, 'bits': bits})
+    return True
+
+  ZP_BUDGET = 8.0              # E = exp(|c.re| F) <= 8, F = sum |w_t|, on every emitted 'zpoly' step: zpoly_util.apply_bound stays near the real rounding
+
+  def _zp_terms(self, h):
+    """(weights, z masks) of a cost function on handle h: the term counts about the 64 lanes a segment's terms are dealt to, the
+    masks in the shapes that make the planner's classes and groups -- aimed by the map as far as the model knows it"""
+    rng, m = self.rng, self.m
+    n, loc, held = m.n[h], m.local_bits(h), sorted(m.held[h])
+    nloc, bm = len(loc), m.bm[h]
+    lo, hi = ((0, 0), (1, 1), (2, 8), (9, 63), (64, 200), (ZPOLY_MAX_TERMS, ZPOLY_MAX_TERMS))[int(rng.choice(6, p=[0.06, 0.1, 0.28, 0.26, 0.24, 0.06]))]
+    nt = min(int(rng.integers(lo, hi + 1)), ZPOLY_MODEL_BUDGET >> nloc)      # the NumPy model evaluates f term by term
+    low_bits = PAULI_CHUNK_BITS + (0 if self.bw == 128 else 1)
+    below = [b for b in loc if bm[b] < low_bits]             # the low part of the index and the chunk part, in logical bits
+    above = [b for b in loc if bm[b] >= low_bits]
+    def mask(pool, lo_w, hi_w):
+      hi_w = min(hi_w, len(pool))
+      return sum(1 << int(b) for b in rng.choice(pool, size=int(rng.integers(min(lo_w, hi_w), hi_w + 1)), replace=False))
+    everything = list(range(n))
+    def any_shape():
+      r = rng.random()
+      if r < 0.08:
+        return 0                                             # a constant term
+      if r < 0.33:
+        return mask(everything, 1, 1)
+      if r < 0.63:
+        return mask(everything, 2, 2)                        # an edge
+      if r < 0.83:
+        return mask(everything, 3, n)
+      if r < 0.9 or not held:
+        return (1 << n) - 1 if r < 0.88 else sum(1 << b for b in loc)      # the full register, global or local
+      return mask(everything, 0, 3) | (1 << held[int(rng.integers(len(held)))])      # a held shard bit among them
+    shape = int(rng.integers(4)) if above and below else int(rng.integers(2))
+    if shape == 0:
+      z = [any_shape() for _ in range(nt)]
+    elif shape == 1:                                         # the edge list of a random graph, with fields on some vertices
+      z = [mask(everything, 2, 2) if rng.random() < 0.8 else mask(everything, 1, 1) for _ in range(nt)]
+    elif shape == 2:                                         # 1-4 low masks, each with several masks above it: as many groups
+      lows = [mask(below, 1, 3) for _ in range(int(rng.integers(1, 5)))]
+      z = [lows[int(rng.integers(len(lows)))] | mask(above, 1, 3) for _ in range(nt)]
+      z = [0 if rng.random() < 0.05 else v for v in z]
+    else:                                                    # constants and the chunk part alone: one long segment, wherever the bits lie
+      z = [0 if rng.random() < 0.5 else mask(above, 1, 3) for _ in range(nt)]
+    if held and rng.random() < 0.5:                          # held shard bits in a third of the masks: signs folded into the weights
+      z = [v | (1 << held[int(rng.integers(len(held)))]) if rng.random() < 1 / 3 else v for v in z]
+    if nt >= 2 and rng.random() < 0.3:                       # the same mask twice: equal masks are not merged
+      a, b = (int(x) for x in rng.choice(nt, size=2, replace=False))
+      z[a] = z[b]
+    w = rng.choice([-1.0, 1.0], size=nt) * 10.0 ** rng.uniform(-2.5, 0.5, size=nt)      # both signs, mixed magnitudes
+    return np.asarray(w, dtype=np.float64).reshape(nt), [int(v) for v in z]
+
+  def k_expect_zpoly(self):
+    h = self.pick_half_queued()
+    if h is None:
+      return False
+    w, z = self._zp_terms(h)
+    self.emit({'op': 'expect_zpoly', 'h': h, 'w': w, 'z': z, 'nloc': self.m.nloc(h)})
+    return True
+
+  def k_zpoly(self):
+    """h := exp(c f) h in place: c purely imaginary (no exp in the kernel), purely real, general or exactly (0, 0); c.re is drawn
+    inside the budget exp(|c.re| F) <= 8 as the Pauli products' factors are drawn inside M <= 8"""
+    rng, m = self.rng, self.m
+    h = self.pick_half_queued()
+    if h is None:
+      return False
+    w, z = self._zp_terms(h)
+    big_f = zu.big_f(w)
+    re = float(rng.uniform(-1, 1)) * float(np.log(self.ZP_BUDGET)) * (1 - 1e-9) / big_f if big_f > 0 else float(rng.uniform(-1, 1))
+    im = float(rng.uniform(-np.pi, np.pi)) / (big_f if big_f > 1 and rng.random() < 0.5 else 1.0)
+    kind = int(rng.choice(4, p=[0.35, 0.25, 0.3, 0.1]))
+    c = (complex(0, im), complex(re, 0), complex(re, im), 0j)[kind]
+    self.zp_calls += 1
+    if len(z) and c != 0:
+      mine = mine_of(m.n[h], m.held[h]).astype(np.int64)
+      trial = zu.np_apply(m.wide(h)[mine], w, z, c, f=zpoly_f(m.n[h], m.held[h], w, z))
+      if not (np.exp(abs(c.real) * big_f) <= self.ZP_BUDGET and 1e-3 <= float(np.vdot(trial, trial).real) <= 100):
+        self.zp_rejected += 1
+        return False
+    # (emit follows the step with a scale where the norm has left [0.25, 4])
+    self.emit({'op': 'zpoly', 'h': h, 'w': w, 'z': z, 'c': c, 'norm': bool(rng.integers(2)), 'nloc': m.nloc(h)})
+    return True
+
   def k_flush(self):
     h = self.pick(lambda x: self.m.q[x] > 0) or self.pick()
     self.emit({'op': 'flush', 'h': h})
@@ -1190,25 +1481,38 @@ class _Gen:
     loc = m.local_bits(h)
     whats = ['matrix_twice', 'mux_target_selected', 'marginal_twice', 'sample_descending', 'copy_self', 'axpby_self',
              'extend_basis', 'release_value', 'perm_not_bijection', 'perm_control_in_register', 'pauli_sum_self', 'pauli_sum_bad_qubit',
-             'pauli_product_nonfinite', 'pauli_product_bad_qubit']
+             'pauli_product_nonfinite', 'pauli_product_bad_qubit', 'density_same_qubit', 'density_bad_qubit', 'density_k_range',
+             'zpoly_nonfinite', 'zpoly_bad_qubit', 'zpoly_too_many', 'expect_zpoly_nonfinite', 'expect_zpoly_bad_qubit', 'expect_zpoly_too_many']
     if m.held[h]:
+      whats.append('density_nonlocal')                       # (a listed bit on the shard index: nothing runs, nothing is flushed)
       whats.append('perm_register_held')                     # (a register bit on the shard index: nothing is flushed)
       whats.append('pauli_sum_x_held')                       # (an x bit there: nothing runs, no handle comes into being)
       whats.append('pauli_product_x_held')                   # (likewise: the whole list is checked before anything is flushed)
     what = whats[int(rng.integers(len(whats)))]
-    if m.held[h] and rng.random() < 0.4:                     # (the three that only a shard can draw, and few programs are shards)
-      what = whats[len(whats) - 3 + int(rng.integers(3))]
-    if what.startswith('pauli_product_') and rng.random() < 0.5:
+    if m.held[h] and rng.random() < 0.4:                     # (the four that only a shard can draw, and few programs are shards)
+      what = whats[len(whats) - 4 + int(rng.integers(4))]
+    late = ('pauli_product_', 'density_', 'zpoly_', 'expect_zpoly_')      # calls that check everything before anything is flushed
+    if what.startswith(late) and rng.random() < 0.5:
       # half of them on a handle with a burst queued, where the pool has one: the checks of a refused step then show that nothing was flushed
       c = [x for x in self.live() if m.q[x] and m.nloc(x) >= 2 and bool(m.held[x]) == bool(m.held[h])]
       if c:
         h = c[int(rng.integers(len(c)))]
         loc = m.local_bits(h)
-    code = native.QH_ERR_SAME_QUBIT if what in ('matrix_twice', 'mux_target_selected', 'marginal_twice', 'perm_control_in_register') \
-        else native.QH_ERR_NONLOCAL if what in ('perm_register_held', 'pauli_sum_x_held', 'pauli_product_x_held') \
-        else native.QH_ERR_BAD_QUBIT if what in ('pauli_sum_bad_qubit', 'pauli_product_bad_qubit') else native.QH_ERR_ARG
+    code = native.QH_ERR_SAME_QUBIT if what in ('matrix_twice', 'mux_target_selected', 'marginal_twice', 'perm_control_in_register', 'density_same_qubit') \
+        else native.QH_ERR_NONLOCAL if what in ('perm_register_held', 'pauli_sum_x_held', 'pauli_product_x_held', 'density_nonlocal') \
+        else native.QH_ERR_BAD_QUBIT if what.endswith('_bad_qubit') else native.QH_ERR_ARG
     s = {'op': 'refused', 'h': h, 'what': what, 'code': code, 'bits': [int(loc[0]), int(loc[1])]}
-    if what in ('perm_register_held', 'pauli_sum_x_held', 'pauli_product_x_held'):
+    if what.startswith(('density_', 'zpoly_', 'expect_zpoly_')):
+      s['nbits'], s['queued'] = m.n[h], bool(m.q[h])
+    if what == 'density_k_range':                            # k = 9, and k = nloc + 1 on a handle of fewer than 8 local bits
+      s['k'] = min(DENSITY_MAX_BITS, len(loc)) + 1
+    if what.endswith('zpoly_nonfinite'):                     # NaN or an infinity in a weight of term 1 or 2 of 3 (and sometimes in the
+      s['term'], s['value'] = int(rng.integers(1, 3)), ('nan', 'inf', '-inf')[int(rng.integers(3))]      # next one too), or in c
+      s['also_next'], s['in_c'] = bool(rng.integers(2)), what == 'zpoly_nonfinite' and rng.random() < 0.3
+      s['says'] = 'c = ' if s['in_c'] else f"term {s['term']} "      # qh_last_error names the first offending term
+    if what.endswith('zpoly_bad_qubit'):
+      s['term'] = int(rng.integers(1, 3))
+    if what in ('perm_register_held', 'pauli_sum_x_held', 'pauli_product_x_held', 'density_nonlocal'):
       s['held'] = int(sorted(m.held[h])[int(rng.integers(len(m.held[h])))])
     if what.startswith('pauli_product_'):
       s['nbits'], s['queued'] = m.n[h], bool(m.q[h])
@@ -1225,8 +1529,8 @@ class _Gen:
     self.emit(s)
     return True
 
-  WEIGHTS = {'gates': 9.0, 'close': 0.6, 'refused': 0.8, 'remap': 1.6, 'flush': 0.7, 'clone': 1.3, 'inner': 1.8, 'axpby': 1.8, 'copy': 1.3,
-             'pauli_sum': 2.5, 'pauli_product': 2.5}
+  WEIGHTS = {'gates': 9.0, 'close': 0.6, 'refused': 2.0, 'remap': 1.6, 'flush': 0.7, 'clone': 1.3, 'inner': 1.8, 'axpby': 1.8, 'copy': 1.3,
+             'pauli_sum': 2.5, 'pauli_product': 2.5, 'reduced_density': 2.0, 'expect_zpoly': 1.5, 'zpoly': 2.5}
 
   def run(self):
     self.start()
@@ -1248,10 +1552,10 @@ def gen_program(seed, bw, mode='own'):
   return _Gen(seed, bw, mode).run()
 
 
-def gen_program_counted(seed, bw, mode='own'):
-  """(the steps of gen_program, draws of k_pauli_product, draws among them rejected because M or the trial's norm left its range)"""
+def gen_program_draws(seed, bw, mode='own'):
+  """(the steps of gen_program, {kind: (draws made, draws rejected)} of the two budgeted drawers k_pauli_product and k_zpoly)"""
   g = _Gen(seed, bw, mode)
-  return g.run(), g.pp_calls, g.pp_rejected
+  return g.run(), {'pauli_product': (g.pp_calls, g.pp_rejected), 'zpoly': (g.zp_calls, g.zp_rejected)}
 
 
 def describe(s):
@@ -1288,10 +1592,12 @@ class Check:
     self.bw = bw
     # (index, op, local bits out of canonical order, a queued burst ran in the step, inner path or None, the record of a
     # 'perm' step or None: what qh_perm_plan said of the layout the call worked on, and what kind of handle it was; for a
-    # 'pauli_sum' step the record of _Runner.run_pauli_sum: what qh_pauli_sum_plan said, and what src and dst were)
+    # 'pauli_sum' step the record of _Runner.run_pauli_sum: what qh_pauli_sum_plan said, and what src and dst were; likewise the
+    # records of run_pauli_product, run_reduced_density, run_zpoly and run_expect_zpoly)
     self.events = []
     self.relaid = 0             # barrier / reader steps whose own flush re-laid the handle out
     self.chain_err = self.chain_d = self.chain_tol = None
+    self.ratios = {}            # family of derived bound -> the largest error seen as a fraction of it
     self.nloc0 = None
 
 
@@ -1344,6 +1650,18 @@ class _Runner:
     self.chain = ModelState()                               # never re-read
     self.chain_r = ModelState(np.complex64) if self.bw == 64 else None
     self.i, self.s = 0, None
+    self.fresh = {}                                         # handle -> 'extend' | 'release' | 'copy' while nothing else has touched it since
+
+  def note(self, s):
+    """which handles are as extend / release made them or copy_from filled them, with no step on them since"""
+    if s['op'] in ('refused', 'init'):
+      return
+    for x in (s.get('h'), s.get('other'), s.get('src'), s.get('dst')):
+      self.fresh.pop(x, None)
+    if s['op'] in ('extend', 'release'):
+      self.fresh[s['new']] = s['op']
+    elif s['op'] == 'copy':
+      self.fresh[s['h']] = 'copy'
 
   def fail(self, what):
     raise StepFailure(self.i, self.s, what)
@@ -1534,6 +1852,24 @@ class _Runner:
       calls['pauli_product_bad_qubit'] = lambda: st.apply_pauli_product([0.6] * 3, [-0.8j] * 3, ok_x[:2] + [ok_x[2] | (high if s['in_x'] else 0)],
                                                                         ok_z[:2] + [ok_z[2] | (0 if s['in_x'] else high)], norm=True)
       calls['pauli_product_x_held'] = lambda: st.apply_pauli_product([0.6] * 3, [-0.8j] * 3, ok_x[:2] + [ok_x[2] | (1 << s.get('held', 0))], ok_z)
+    if s['what'].startswith('density_'):
+      k, high, loc = s.get('k', 0), s['nbits'], self.m.local_bits(s['h'])
+      calls['density_same_qubit'] = lambda: st.reduced_density([a, a])
+      calls['density_bad_qubit'] = lambda: st.reduced_density([a, high])
+      calls['density_k_range'] = lambda: st.reduced_density((loc * (DENSITY_MAX_BITS + 1))[:k])      # (k is checked before the list)
+      calls['density_nonlocal'] = lambda: st.reduced_density([a, s.get('held')])
+    if 'zpoly_' in s['what']:                                # three terms, the offending one never the first; 4097 for too many
+      ws, zs, t = [0.5, -0.25, 2.0], [1 << a, (1 << a) | (1 << b), 0], s.get('term', 1)
+      if s['what'].endswith('nonfinite') and not s['in_c']:
+        ws[t] = float(s['value'])
+        if s['also_next'] and t + 1 < 3:
+          ws[t + 1] = float('nan')
+      if s['what'].endswith('bad_qubit'):
+        zs[t] |= 1 << s['nbits']
+      if s['what'].endswith('too_many'):
+        ws, zs = [0.0] * (ZPOLY_MAX_TERMS + 1), [1 << a] * (ZPOLY_MAX_TERMS + 1)
+      c = complex(float(s['value']), 0.5) if s.get('in_c') else complex(0.25, -0.5)
+      calls[s['what']] = (lambda: st.expect_zpoly(ws, zs)) if s['what'].startswith('expect_') else (lambda: st.apply_zpoly(ws, zs, c, norm=True))
     # a refused Pauli sum: into a new handle (none may come into being) and, where the pool has one, into an existing one
     outs = [None] + ([self.dev[s['other']]] if s.get('other') is not None else []) if s['what'].startswith('pauli_sum_') else [()]
     for out in outs:
@@ -1568,12 +1904,17 @@ class _Runner:
       return
     if op == 'refused':
       k0 = {x: self.kernels(x) for x in involved}
+      stats0 = self.dev[h].stats()
       self.refused(s)
       for x in involved:                                     # (the handle, and the destination a refused Pauli sum was given)
         self.need(_pending(self.dev[x]) == q_before[x] and _bitmap(self.dev[x]) == bm_before[x] and self.kernels(x) == k0[x],
                   f'handle {x}: a refused call changed the queue, the bit map or launched a kernel')
         if q_before[x] == 0:
           self.need(self.read(x).tobytes() == m.wide(x).tobytes(), f'handle {x}: a refused call changed the state')
+      if s['what'].startswith(('density_', 'zpoly_', 'expect_zpoly_')):      # "nothing runs, nothing changes, nothing is flushed"
+        self.need(self.dev[h].stats() == stats0, f'a refused call changed the stats: {self.dev[h].stats()}, before {stats0}')
+        if q_before[h] == 0:                                 # (asking an attached handle for its pointer runs what is queued)
+          self.check_ptr(h)
       self.check.events.append((self.i, op, False, False, None, None))
       return
     for x in involved:                                     # the mode, read without changing it, where a plan exists to show it
@@ -1584,6 +1925,9 @@ class _Runner:
       return
     if op == 'pauli_product':
       self.run_pauli_product(s, q_before[h], bm_before[h])
+      return
+    if op in ('reduced_density', 'expect_zpoly', 'zpoly'):
+      getattr(self, 'run_' + op)(s, q_before[h], bm_before[h])
       return
     k_before = {x: self.kernels(x) for x in involved}
     n0 = {x: self.dev[x].marginal([]).tobytes() for x in involved} if quiet and op in READERS + ('inner',) else {}
@@ -1960,6 +2304,251 @@ class _Runner:
            'fixed': h in self.fixed_ptr, 'pz0': bool(ab) and any(t['pz'] & 1 for t in terms)}
     self.check.events.append((self.i, 'pauli_product', not _canonical(bm, nloc), not quiet, None, rec))
 
+  # -- reduced densities and Z-polynomials: the frame the three steps share -----------------------------------------------------------
+  def _behind(self, h, queued, bm_before, what):
+    """behind a call that runs what is queued and leaves the layout as it finds it: nothing pending, the bit map moved only by a
+    flush whose relayout mode is on, the held bits and the pointer as before.  Returns (bit map, moved)."""
+    st, m = self.dev[h], self.m
+    bm = _bitmap(st)
+    self.need(_pending(st) == 0, f'{_pending(st)} gates pending behind {what}')
+    moved = bm != bm_before
+    if not queued:
+      self.need(not moved, 'the bit map moved in a step that had nothing to flush')
+    elif moved:
+      self.need(m.mode[h] == 1, f'a flush re-laid the handle out, its relayout mode is {m.mode[h]}')
+      self.check.relaid += 1
+    self.need({x for x, p in enumerate(bm) if p >= st.nbits} == set(m.held[h]), 'the held bits changed')
+    self.check_ptr(h)
+    return bm, moved
+
+  def _read_behind_reader(self, h, quiet, bm):
+    """the amplitudes behind a reader, through a clone: as stored on a quiet step, within _amp_tol of the model behind a burst"""
+    m, st = self.m, self.dev[h]
+    after = self.read(h)
+    self.need(_bitmap(st) == bm, 'reading the handle through a clone moved its bit map')
+    w = m.wide(h)
+    if quiet:
+      self.need(np.array_equal(after, w), f'a reader changed the amplitudes (max diff {float(np.max(np.abs(after - w))):.3e})')
+    else:
+      err = float(np.max(np.abs(after - w)))
+      self.need(err <= amp_tol(self.bw), f'behind its queue: amplitudes off by {err:.3e} (limit {amp_tol(self.bw):.1e})')      # _amp_tol
+    m.put(h, after)
+    self.check_raw(h, after, bm)
+    return after
+
+  def _stats_grew(self, stats0, stats1, grow, what):
+    for k in stats0:
+      self.need(stats1[k] - stats0[k] == grow.get(k, 0), f'{k} grew by {stats1[k] - stats0[k]}, the header says {grow.get(k, 0)} for {what}')
+
+  def _ratio(self, family, err, bound):
+    """the largest error seen as a fraction of its bound, per family (HISTORY.md T5 records it)"""
+    r = float(np.max(np.where(bound > 0, err / np.maximum(bound, 1e-300), np.where(err > 0, np.inf, 0.0))))
+    self.check.ratios[family] = max(self.check.ratios.get(family, 0.0), r)
+
+  def run_reduced_density(self, s, queued, bm_before):
+    """One 'reduced_density' step: a reader on h in whatever condition the program left it.  The matrix is held to
+    density_util.np_reduced_density of the amplitudes read back behind the step, within density_util.tolerance."""
+    m, bw = self.m, self.bw
+    h, st, bits = s['h'], self.dev[s['h']], s['bits']
+    k, n, nloc = len(bits), m.n[h], st.nbits
+    quiet = queued == 0
+    stats0 = st.stats()
+    try:
+      rho = st.reduced_density(bits)
+    except native.QhError as e:
+      self.fail(f'the engine refused a valid step: {e}')
+    stats1 = st.stats()
+    plan = density_plan_view(st.density_plan(bits))          # right behind the call: the layout the call's own flush left
+    for mdl in (m, self.chain, self.chain_r):
+      if mdl is not None:
+        mdl.run(h)
+    bm, moved = self._behind(h, queued, bm_before, 'a reduced density')
+    # -- the plan, held to the bit map by the rule stated in Python ------------------------------------------------------------------
+    want_plan = density_rule(nloc, bm, bits)
+    self.need(plan == want_plan, f'qh_density_plan says {plan}, the rule on bit map {bm} gives {want_plan}')
+    # -- stats of a quiet step: one kernel (the fold is not counted), the shard once, the bytes the kernel requests -----------------
+    ab = 16 if bw == 128 else 8
+    if quiet:
+      self._stats_grew(stats0, stats1, {'kernels_launched': 1, 'bytes_algorithmic': (1 << nloc) * ab, 'bytes_swept': want_plan['amps_swept'] * ab},
+                       'a reduced density')
+    # -- the state: unchanged ------------------------------------------------------------------------------------------------------------
+    after = self._read_behind_reader(h, quiet, bm)
+    # -- the matrix ------------------------------------------------------------------------------------------------------------------------
+    self.need(rho.shape == (1 << k, 1 << k) and rho.dtype == np.complex128, f'the result has shape {rho.shape} and type {rho.dtype}')
+    psi, number = local_view(after, n, m.held[h])
+    want = du.np_reduced_density(psi, [number[b] for b in bits])
+    tol = du.tolerance(want, 1 << (nloc - k))
+    err = np.abs(rho - want)
+    self._ratio('reduced_density', err, tol)
+    self.need(bool(np.all(err <= tol)), f'rho off by up to {float(np.max(err / np.maximum(tol, 1e-300))):.3g} x density_util.tolerance '
+              f'(max error {float(np.max(err)):.3e}, k = {k}, {plan["block_pairs"]} block pairs, path {plan["path"]})')
+    # -- bit for bit: one triangle mirrored, a real diagonal ----------------------------------------------------------------------------------
+    off = ~np.eye(1 << k, dtype=bool)
+    self.need(rho.real.tobytes() == np.ascontiguousarray(rho.real.T).tobytes() and rho.imag[off].tobytes() == (-rho.imag.T)[off].tobytes(),
+              'rho[c][r] is not the bitwise conjugate of rho[r][c]')
+    d = np.diag(rho)
+    self.need(bool(np.all(d.imag == 0.0)) and not np.any(np.signbit(d.imag)), 'a diagonal imaginary part is not 0.0')
+    # -- the diagonal against marginal on the same bits, the trace against norm2 (k = 0: the norm itself) ------------------------------------
+    # (the bound holds each of two sums of m products to the exact value: rho_rr and the marginal, which sums the same m
+    # probabilities in another order, are each within it, so they lie within twice the bound of each other)
+    dtol = np.diag(tol)
+    p = st.marginal(bits)
+    self.need(bool(np.all(np.abs(d.real - p) <= 2 * dtol)),
+              f'the diagonal differs from marginal on the same bits by up to {float(np.max(np.abs(d.real - p))):.3e}')
+    n2 = st.norm2()
+    self.need(abs(float(np.sum(d.real)) - n2) <= float(np.sum(dtol)) + TOL * n2,      # (+ TOL: norm2 and this sum of the diagonal round on their own)
+              f'the trace {float(np.sum(d.real))!r} differs from norm2 {n2!r}')
+    if quiet:
+      self.need(st.reduced_density(bits).tobytes() == rho.tobytes(), 'two calls on the same state and layout, two answers')
+    self.need(_bitmap(st) == bm and _pending(st) == 0, 'the readers behind the step moved the bit map or queued something')
+    # -- the record ---------------------------------------------------------------------------------------------------------------------
+    rows = plan['row_pos']
+    rec = {'nloc': nloc, 'k': k, 'path': plan['path'], 'tile_bits': plan['tile_bits'], 'chunk_bits': plan['chunk_bits'], 'nrest': plan['nrest'],
+           'block_pairs': plan['block_pairs'], 'chunks_per_wg': plan['chunks_per_wg'], 'row_identity': plan['row_bit'] == list(range(k)),
+           'pos0': 0 in rows, 'pos01': 0 in rows and 1 in rows, 'queued': not quiet, 'relayout_on': m.mode[h] == 1,
+           'relaid': not quiet and moved and not _canonical(bm, nloc), 'shard': bool(m.held[h]), 'fixed': h in self.fixed_ptr,
+           'fresh': self.fresh.get(h)}
+    self.check.events.append((self.i, 'reduced_density', not _canonical(bm, nloc), not quiet, None, rec))
+
+  def _zpoly_record(self, s, plan, quiet, moved, bm):
+    m, bw, h = self.m, self.bw, s['h']
+    nloc = self.dev[h].nbits
+    main = plan['kernel'] == native.QH_ZPOLY_KERNEL_MAIN
+    segs = zpoly_segments(plan) if main else []
+    kinds = [zpoly_group_kind(g, bw) for g in plan['group_mask']] if main else []
+    return {'nloc': nloc, 'main': main, 'nterms': plan['nterms'], 'classes': sorted({ZPOLY_CLASSES[c] for c in plan['cls']}) if main else [],
+            'group_kinds': {kd: kinds.count(kd) for kd in ZPOLY_GROUP_KINDS}, 'seg_over_64': any(c > ZPOLY_LANES for c in segs),
+            'seg_2_to_63': any(2 <= c < ZPOLY_LANES for c in segs), 'duplicates': len(set(s['z'])) < len(s['z']),
+            'pz0': bw == 64 and any(z & 1 for z in plan['pz']), 'c': zpoly_c_kind(s['c']) if 'c' in s else None, 'norm': s.get('norm'),
+            'shard': bool(m.held[h]), 'neg_held': any(a != float(b) and (a or b) for a, b in zip(plan['w'], s['w'])),
+            'queued': not quiet, 'relayout_on': m.mode[h] == 1, 'relaid': not quiet and moved and not _canonical(bm, nloc),
+            'fixed': h in self.fixed_ptr}
+
+  def _zpoly_plan(self, st, s, bm, h):
+    """qh_zpoly_plan right now, held to the rule on the bit map"""
+    plan = st.zpoly_plan(s['w'], s['z'])
+    want = zpoly_rule(st.nbits, self.bw, bm, self.shard[h], s['w'], s['z'])
+    self.need(plan == want, f'qh_zpoly_plan differs from the rule on bit map {bm} in {[k for k in want if plan.get(k) != want[k]]}: '
+              f'{ {k: plan.get(k) for k in want if plan.get(k) != want[k] and k not in ("pz", "w", "cls")} }')
+    return plan
+
+  def run_expect_zpoly(self, s, queued, bm_before):
+    """One 'expect_zpoly' step: a reader; the three sums are held to zpoly_util.np_moments of the amplitudes read back behind the
+    step at the global logical indices the shard holds, within zpoly_util.moment_bound"""
+    m, bw = self.m, self.bw
+    h, st, ws, zs = s['h'], self.dev[s['h']], s['w'], s['z']
+    nt, n, nloc = len(zs), m.n[h], st.nbits
+    quiet = queued == 0
+    stats0 = st.stats()
+    try:
+      got = st.expect_zpoly(ws, zs)
+    except native.QhError as e:
+      self.fail(f'the engine refused a valid step: {e}')
+    stats1 = st.stats()
+    for mdl in (m, self.chain, self.chain_r):
+      if mdl is not None:
+        mdl.run(h)
+    bm, moved = self._behind(h, queued, bm_before, 'expect_zpoly')
+    plan = self._zpoly_plan(st, s, bm, h)                    # right behind the call: the layout the call's own flush left
+    sb = (1 << nloc) * (16 if bw == 128 else 8)
+    if quiet:                                                # one kernel and one read of the shard; no terms: the reader norm2, which counts nothing
+      self._stats_grew(stats0, stats1, {'kernels_launched': 1, 'bytes_swept': sb, 'bytes_algorithmic': sb} if nt else {}, f'expect_zpoly of {nt} terms')
+    after = self._read_behind_reader(h, quiet, bm)
+    mine = mine_of(n, m.held[h]).astype(np.int64)
+    want = zu.np_moments(after[mine], ws, zs, f=zpoly_f(n, m.held[h], ws, zs))
+    self.need(len(got) == 3, f'expect_zpoly returned {got!r}')
+    for k in range(3):
+      bound = zu.moment_bound(ws, k, want[0])
+      err = abs(got[k] - want[k])
+      self._ratio(f'expect_zpoly moment {k}', np.float64(err), np.float64(bound))
+      self.need(err <= bound, f'moment {k}: {got[k]!r}, the model gives {want[k]!r}: off by {err:.3e} (zpoly_util.moment_bound {bound:.3e}, {nt} terms)')
+    if nt == 0:
+      n2 = st.norm2()
+      self.need((got[1], got[2]) == (0.0, 0.0) and got[0] == n2, f'no terms: {got!r}, norm2 called next gives {n2!r}')
+    if quiet:
+      again = st.expect_zpoly(ws, zs)
+      self.need(tuple(again) == tuple(got), f'two calls on the same state and layout, two answers: {got!r}, {again!r}')
+    self.need(_bitmap(st) == bm and _pending(st) == 0, 'the readers behind the step moved the bit map or queued something')
+    self.check.events.append((self.i, 'expect_zpoly', not _canonical(bm, nloc), not quiet, None, self._zpoly_record(s, plan, quiet, moved, bm)))
+
+  def run_zpoly(self, s, queued, bm_before):
+    """One 'zpoly' step, in place on h in whatever condition the program left it: every check of _apply_checked of
+    tests/test_gpu_zpoly.py and those of run_pauli_product that apply.  On a QUIET step the plan is asked before the call too, the
+    stats are held exactly and the call is repeated from the same start (restored from a clone)."""
+    m, bw = self.m, self.bw
+    h, st, ws, zs, c = s['h'], self.dev[s['h']], s['w'], s['z'], complex(s['c'])
+    nt, n, nloc = len(zs), m.n[h], st.nbits
+    quiet = queued == 0
+    noop = nt == 0 or c == 0                                 # flushes and launches nothing; norm2 is then qh_norm2's
+    mine = mine_of(n, m.held[h]).astype(np.int64)
+    plan0 = self._zpoly_plan(st, s, bm_before, h) if quiet else None      # asked right before the call
+    keep = st.clone() if quiet and not noop else None        # the start, for the repeat
+    try:
+      stats0 = st.stats()
+      try:
+        n2 = st.apply_zpoly(ws, zs, c, norm=s['norm'])
+      except native.QhError as e:
+        self.fail(f'the engine refused a valid step: {e}')
+      stats1 = st.stats()
+      m.run(h)
+      before = m.wide(h)                                     # quiet: what the handle held, bit for bit; else the model behind the burst
+      want_n2 = m.step(s)
+      for mdl in (self.chain, self.chain_r):
+        if mdl is not None:
+          mdl.step(s)
+      bm, moved = self._behind(h, queued, bm_before, 'a Z-polynomial')
+      plan = self._zpoly_plan(st, s, bm, h)                  # right behind the call: the layout the call's own flush left
+      if quiet:
+        self.need(plan0 == plan, 'the plan asked before a quiet call differs from the plan asked behind it')
+      sb = (1 << nloc) * (16 if bw == 128 else 8)
+      if quiet:
+        grow = {} if noop else {'gates_submitted': 1, 'kernels_launched': 1, 'bytes_swept': 2 * sb, 'bytes_algorithmic': 2 * sb}
+        self._stats_grew(stats0, stats1, grow, f'apply_zpoly of {nt} terms with c = {c}')
+      # -- amplitudes ---------------------------------------------------------------------------------------------------------------------
+      after = self.read(h)
+      self.need(_bitmap(st) == bm, 'reading the handle through a clone moved its bit map')
+      want = m.wide(h)                                       # zpoly_util.np_apply of what the handle held
+      amax = float(np.max(np.abs(before)))
+      big_e = float(np.exp(abs(c.real) * zu.big_f(ws)))      # E
+      bound = zu.apply_bound(bw, ws, c, amax)
+      if not quiet:
+        bound += big_e * amp_tol(bw)                         # the burst's own rounding passes through the factor and grows by at most E
+      if quiet and noop:
+        self.need(after.tobytes() == before.tobytes(), 'no terms or c == (0, 0): the amplitudes changed')
+      else:
+        err = float(max(np.max(np.abs(after.real - want.real)), np.max(np.abs(after.imag - want.imag))))
+        self._ratio('zpoly' if quiet else 'zpoly behind a burst', np.float64(err), np.float64(bound))
+        self.need(err <= bound, f'amplitudes off by {err:.3e} per component (bound {bound:.3e}, {nt} terms, E = {big_e:.3g})')
+      self.need(not np.any(after[np.setdiff1d(np.arange(1 << n), mine)]), 'amplitudes another shard holds are not zero in what was read')
+      m.put(h, after)
+      self.check_raw(h, after, bm)
+      # -- norm2 --------------------------------------------------------------------------------------------------------------------------
+      if s['norm']:
+        n2_np = float(np.vdot(after, after).real)
+        self.need(abs(n2 - n2_np) <= TOL * n2_np, f'norm2 {n2!r}, the amplitudes read back give {n2_np!r}')
+        # against the model: every component within `bound` of the model's, so |sum |got|^2 - sum |want|^2| <= sum (2 |want_i| d + d^2)
+        # with d = sqrt(2) bound per amplitude, and sum |want_i| <= sqrt(N want_n2) (Cauchy-Schwarz); + the reader's own TOL
+        size = float(1 << nloc)
+        n2_tol = 2 * np.sqrt(2.0) * bound * np.sqrt(size * want_n2) + 2 * bound * bound * size + TOL * want_n2
+        self.need(abs(n2 - want_n2) <= n2_tol, f'norm2 {n2!r}, the model gives {want_n2!r} (tolerance {n2_tol:.3e})')
+        if noop:
+          nr = st.norm2()
+          self.need(n2 == nr, f'no terms or c == (0, 0): norm2 {n2!r}, qh_norm2 gives {nr!r}')
+      else:
+        self.need(n2 is None, f'norm2 was not asked for, the call returned {n2!r}')
+      # -- the same start again: the same bits --------------------------------------------------------------------------------------------
+      if keep is not None:
+        st.copy_from(keep)
+        self.need(_bitmap(st) == bm, 'copy_from a clone of the handle itself moved the bit map')
+        again = st.apply_zpoly(ws, zs, c, norm=s['norm'])
+        self.need(again == n2, f'norm2 {n2!r}, from the same call repeated {again!r}')
+        self.need(_bitmap(st) == bm and _pending(st) == 0, 'the repeated call moved the bit map or queued something')
+        self.need(self.read(h).tobytes() == after.tobytes(), 'the same call from the same start gave other amplitude bytes')
+    finally:
+      if keep is not None:
+        keep.close()
+    self.check.events.append((self.i, 'zpoly', not _canonical(bm, nloc), not quiet, None, self._zpoly_record(s, plan, quiet, moved, bm)))
+
   def perm_record(self, s, queued, bm_before):
     """What qh_perm_plan says of the step's bits right behind the call: the call does not move the bit map, so this is the
     layout it worked on (the one its own flush left).  The plan is held to the bit map by the tile rule."""
@@ -2038,6 +2627,7 @@ class _Runner:
           self.do_init(self.s)
         else:
           self.run_step(self.s)
+          self.note(self.s)
       self.finish()
     finally:
       for st in self.dev.values():
@@ -2643,3 +3233,179 @@ class NumpyDevice:
 
   def _pprod_norm2(self, stored, unrounded, first_stored):
     return float(np.vdot(stored, stored).real)               # of the final amplitudes as stored, summed by the last run
+
+  # -- reduced density matrices: clause by clause as the header describes them, through hooks a mutant overrides one at a time -----
+  def _dens_check(self, who, bits):
+    """k out of range, then the list (a bit beyond the register, a bit twice), then a listed bit the shard index holds"""
+    kmax = min(DENSITY_MAX_BITS, self.nbits)
+    if len(bits) > kmax:
+      raise native.QhError(native.QH_ERR_ARG, f'{who}: k = {len(bits)} outside [0,{kmax}]')
+    if any(not 0 <= b < self.nbits_global for b in bits):
+      raise native.QhError(native.QH_ERR_BAD_QUBIT, f'{who}: a bit beyond the register')
+    if len(set(bits)) != len(bits):
+      raise native.QhError(native.QH_ERR_SAME_QUBIT, f'{who}: a bit twice')
+    if any(not self._dens_local(b) for b in bits):
+      raise native.QhError(native.QH_ERR_NONLOCAL, f'{who}: a listed bit is held by the shard index; exchange first')
+
+  def density_plan(self, bits):
+    bits = [int(b) for b in bits]
+    self._dens_check('density_plan', bits)
+    return density_rule(self.nbits, self.bm, bits)
+
+  def reduced_density(self, bits):
+    bits = [int(b) for b in bits]
+    self._dens_check('reduced_density', bits)                # before anything is flushed
+    self._dens_enter()
+    plan = self.density_plan([b for b in bits if self._dens_is_local(b)])
+    vec = self.to_logical()
+    psi, number = local_view(vec, self.nbits_global, self.held())
+    rho = du.np_reduced_density(psi, self._dens_rows([number[b] for b in bits if b in number]))
+    rho = self._dens_mirror(self._dens_scale(self._dens_orient(rho)))
+    self._dens_layout()
+    ab = 16 if self.bit_width == 128 else 8
+    self.kernels += self._dens_kernels()
+    self.algorithmic += (1 << self.nbits) * ab
+    self.swept += self._dens_swept(plan, ab)
+    return rho
+
+  def _dens_is_local(self, b):
+    return self.bm[b] < self.nbits
+
+  def _dens_local(self, b):
+    return self._dens_is_local(b)                            # the refusal's view of it
+
+  def _dens_enter(self):
+    self.flush()                                             # a reader: what is queued runs first
+
+  def _dens_rows(self, bits):
+    return bits                                              # bits[t] is bit t of a row number
+
+  def _dens_orient(self, rho):
+    return rho                                               # rho[r][c] = sum_e a(r,e) conj(a(c,e))
+
+  def _dens_scale(self, rho):
+    return rho                                               # not normalised: the trace is the shard's norm
+
+  def _dens_mirror(self, rho):
+    """one triangle is computed, the other mirrored; the diagonal's imaginary parts are exactly 0.0"""
+    out = np.array(rho, dtype=np.complex128)
+    lower = np.tril_indices(out.shape[0], -1)
+    out[lower] = np.conj(out.T[lower])                       # (a negation of the imaginary part: the sign of a zero included)
+    d = np.diag_indices(out.shape[0])
+    out[d] = out[d].real
+    return out
+
+  def _dens_layout(self):
+    pass                                                     # reads only: the bit map is as the call found it
+
+  def _dens_kernels(self):
+    return 1                                                 # the fold is not counted
+
+  def _dens_swept(self, plan, amp_bytes):
+    return plan['amps_swept'] * amp_bytes                    # the bytes the kernel requests
+
+  # -- Z-polynomials: clause by clause as the header describes them, through hooks a mutant overrides one at a time -------------------
+  def _zp_check(self, who, ws, zs, c=None):
+    """the whole list, before anything is flushed"""
+    if len(zs) > ZPOLY_MAX_TERMS:
+      raise native.QhError(native.QH_ERR_ARG, f'{who}: {len(zs)} terms (at most {ZPOLY_MAX_TERMS})')
+    for t, (w, z) in enumerate(zip(ws, zs)):
+      if not np.isfinite(w):
+        raise native.QhError(native.QH_ERR_ARG, f'{who}: term {t} has a non-finite weight ({w})')
+      if z >> self.nbits_global:
+        raise native.QhError(native.QH_ERR_BAD_QUBIT, f'{who}: term {t} has bits >= {self.nbits_global}')
+    if c is not None and not (np.isfinite(c.real) and np.isfinite(c.imag)):
+      raise native.QhError(native.QH_ERR_ARG, f'{who}: c = {c} is not finite')
+
+  def zpoly_plan(self, weights, zmasks):
+    ws, zs = [float(w) for w in weights], [int(z) for z in zmasks]
+    self._zp_check('zpoly_plan', ws, zs)
+    return zpoly_rule(self.nbits, self.bit_width, self.bm, self.shard, ws, zs)
+
+  def _zp_f(self, ws, zs):
+    """f at the global logical indices the shard holds, from the terms as the kernels get them: masks cut to the local bits, the
+    sign the shard index gives a held z bit folded into the weight"""
+    held = self.held()
+    local = sum(1 << b for b in range(self.nbits_global) if b not in held)
+    terms = self._zp_terms([(self._zp_fold(w, z, held), z & local) for w, z in zip(ws, zs)])
+    return zpoly_f(self.nbits_global, held, [self._zp_parity(w, z) for w, z in terms], [z for _, z in terms])
+
+  def _zp_fold(self, w, z, held):
+    return -w if sum(v for b, v in held.items() if (z >> b) & 1) & 1 else w      # an exact negation
+
+  def _zp_terms(self, terms):
+    return terms                                             # as given: a constant term is applied, equal masks are not merged
+
+  def _zp_parity(self, w, z):
+    return w                                                 # w (-1)^popcount(i & z): + where the parity is even
+
+  def apply_zpoly(self, weights, zmasks, c, norm=False):
+    ws, zs, c = [float(w) for w in weights], [int(z) for z in zmasks], complex(c)
+    self._zp_check('apply_zpoly', ws, zs, c)
+    self._zp_enter()
+    if not zs or c == 0:                                     # flushes and launches nothing; norm2 is then the reader's
+      self.kernels += self._zp_noop_kernels()
+      return self._model(self._read(0)).norm(0) if norm else None
+    mine = mine_of(self.nbits_global, self.held()).astype(np.int64)
+    vec = self.to_logical()
+    first = float(np.vdot(self.phys.astype(np.complex128), self.phys.astype(np.complex128)).real)
+    cc = self._zp_c(c)
+    out = np.zeros_like(vec)
+    out[mine] = vec[mine] * self._zp_factor(cc, self._zp_f(ws, zs))
+    self.store(out)                                          # rounded once to the handle's width
+    self._zp_layout()
+    sb = (1 << self.nbits) * (16 if self.bit_width == 128 else 8)
+    self.submitted += 1
+    self.kernels += 1
+    self.swept += self._zp_bytes(sb)
+    self.algorithmic += self._zp_bytes(sb)
+    return self._zp_norm2(first, self.phys.astype(np.complex128)) if norm else None
+
+  def _zp_enter(self):
+    self.flush()                                             # a barrier: what is queued runs first
+
+  def _zp_noop_kernels(self):
+    return 0
+
+  def _zp_c(self, c):
+    return c
+
+  def _zp_factor(self, c, f):
+    return np.exp(c.real * f) * (np.cos(c.imag * f) + 1j * np.sin(c.imag * f))      # exp(c.re f) * (cos(c.im f), sin(c.im f))
+
+  def _zp_layout(self):
+    pass                                                     # the bit map is as the call found it
+
+  def _zp_bytes(self, shard_bytes):
+    return 2 * shard_bytes                                   # one read and one write of the state
+
+  def _zp_norm2(self, first, stored):
+    return float(np.vdot(stored, stored).real)               # of the final amplitudes as stored
+
+  def expect_zpoly(self, weights, zmasks):
+    ws, zs = [float(w) for w in weights], [int(z) for z in zmasks]
+    self._zp_check('expect_zpoly', ws, zs)
+    self._ezp_enter()
+    if not zs:
+      return self._model(self._read(0)).norm(0), 0.0, 0.0     # (the reader's sum; the call counts no kernel)
+    mine = mine_of(self.nbits_global, self.held()).astype(np.int64)
+    a = self.to_logical()[mine]
+    p, f = a.real * a.real + a.imag * a.imag, self._zp_f(ws, zs)
+    self._ezp_layout()
+    sb = (1 << self.nbits) * (16 if self.bit_width == 128 else 8)
+    self.kernels += 1
+    self.swept += self._ezp_bytes(sb)
+    self.algorithmic += self._ezp_bytes(sb)
+    return float(np.sum(p)), float(np.dot(p, f)), self._ezp_second(p, f)
+
+  def _ezp_enter(self):
+    self.flush()                                             # a reader: what is queued runs first
+
+  def _ezp_layout(self):
+    pass
+
+  def _ezp_bytes(self, shard_bytes):
+    return shard_bytes                                       # one read of the state
+
+  def _ezp_second(self, p, f):
+    return float(np.dot(p, f * f))                           # sum |a_i|^2 f(i)^2, not normalised

@@ -315,7 +315,7 @@ def test_supremacy30_marginal_and_readers_leave_the_state():
     m = st.marginal(bits)
     st.sample(np.sort(np.random.default_rng(0).random(100000)))
     st.marginal([3, 29])
-    assert st.marginal([]).tobytes() == n0.tobytes()          # (k_norm2 adds block sums atomically: compare to 1e-14)
+    assert st.marginal([]).tobytes() == n0.tobytes()          # (norm2 and marginal([]) sum in different orders: compare to 1e-14)
     assert abs(st.norm2() - n0[0]) < 1e-14
     assert [st.amplitude(i) for i in (0, 12345, 1 << 29, (1 << 30) - 1)] == amps0
     assert st.argmax() == a0

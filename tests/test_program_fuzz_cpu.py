@@ -8,13 +8,14 @@ from tests import program_model as pm
 from tests.fake_device import np_marginal
 
 WIDTHS = (128, 64)
-_PROGRAMS, _CHECKS, _DRAWS = {}, {}, {}
+_PROGRAMS, _CHECKS, _DRAWS, _ZDRAWS = {}, {}, {}, {}
 
 
 def program(mode, seed, bw):
   key = (mode, seed, bw)
   if key not in _PROGRAMS:
-    _PROGRAMS[key], *_DRAWS[key] = pm.gen_program_counted(seed, bw, mode)
+    _PROGRAMS[key], draws = pm.gen_program_draws(seed, bw, mode)
+    _DRAWS[key], _ZDRAWS[key] = draws['pauli_product'], draws['zpoly']
   return _PROGRAMS[key]
 
 
@@ -56,7 +57,8 @@ def test_pauli_product_draws_keep_their_conditions_and_are_rarely_rejected():
       prog = program(*key)
       c, r = _DRAWS[key]
     else:
-      prog, c, r = pm.gen_program_counted(key[1], key[2], key[0])      # (not kept: 400 programs)
+      prog, draws = pm.gen_program_draws(key[1], key[2], key[0])      # (not kept: 400 programs)
+      c, r = draws['pauli_product']
     calls, rejected = calls + c, rejected + r
     for s in prog:
       if s['op'] == 'pauli_product':
@@ -64,6 +66,34 @@ def test_pauli_product_draws_keep_their_conditions_and_are_rarely_rejected():
         assert len(s['a']) == len(s['b']) == len(s['x']) == len(s['z']) <= 3 * pm.PAULI_PRODUCT_BATCH
         assert pm.ppu.magnitude(s['a'], s['b']) <= 8.0, (key, pm.describe(s))
   print(f'k_pauli_product: {calls} draws in {len(keys)} programs, {rejected} rejected ({rejected / calls:.2%}), {steps} steps emitted')
+  assert steps == calls - rejected and 10 * rejected <= calls
+
+
+def test_zpoly_draws_keep_their_budget_and_are_rarely_rejected():
+  """every emitted 'zpoly' step has E = exp(|c.re| F) <= 8, F = sum |w_t| (zpoly_util.apply_bound stays near the real rounding),
+  its weights and c are finite and nterms * 2^nloc <= 2^25, and the drawer's trial leaves the norm range in at most one call in
+  ten: over the fixed programs and seeds 0..199 (the four modes in turn) at both widths"""
+  modes = ('own', 'shard', 'attached', 'mapped')
+  keys = [(mode, seed, bw) for bw in WIDTHS for mode, seed in pm.FIXED]
+  keys += [key for key in ((modes[seed % 4], seed, bw) for seed in range(200) for bw in WIDTHS) if key not in keys]
+  calls = rejected = steps = 0
+  for key in keys:
+    if key in _PROGRAMS:
+      prog = program(*key)
+      c, r = _ZDRAWS[key]
+    else:
+      prog, draws = pm.gen_program_draws(key[1], key[2], key[0])      # (not kept: 400 programs)
+      c, r = draws['zpoly']
+    calls, rejected = calls + c, rejected + r
+    for s in prog:
+      if s['op'] in ('zpoly', 'expect_zpoly'):
+        assert len(s['w']) == len(s['z']) <= pm.ZPOLY_MAX_TERMS and bool(np.all(np.isfinite(s['w']))), (key, pm.describe(s))
+        assert len(s['z']) << s['nloc'] <= pm.ZPOLY_MODEL_BUDGET, (key, pm.describe(s))
+      if s['op'] == 'zpoly':
+        steps += 1
+        assert np.isfinite(s['c'].real) and np.isfinite(s['c'].imag)
+        assert np.exp(abs(s['c'].real) * pm.zu.big_f(s['w'])) <= 8.0, (key, pm.describe(s))
+  print(f'k_zpoly: {calls} draws in {len(keys)} programs, {rejected} rejected ({rejected / calls:.2%}), {steps} steps emitted')
   assert steps == calls - rejected and 10 * rejected <= calls
 
 
@@ -447,6 +477,256 @@ class ProductBytesOncePerCall(pm.NumpyDevice):
     return 2 * shard_bytes
 
 
+# -- reduced densities (47-56, 72, 73, 78) and Z-polynomials (57-71, 74-77, 79-81): one mutant per hook of NumpyDevice, and one
+#    for every family of runner checks that none of those needed.  HISTORY.md T5 has the table: for every mutant the family of
+#    checks of _Runner.run_reduced_density / run_zpoly / run_expect_zpoly / the refused frame that catches it first, and what
+#    catches it once that family is deleted, and so on until it passes every fixed program or a check outside the new code
+#    (the next step's pending count, the final chain) takes over
+class DensityRowsReversed(pm.NumpyDevice):
+  """47. reduced_density takes bits[k-1-t], not bits[t], for bit t of a row number"""
+  def _dens_rows(self, bits):
+    return bits[::-1]
+
+
+class DensityTransposed(pm.NumpyDevice):
+  """48. reduced_density returns rho transposed (sum_e conj(a(r,e)) a(c,e))"""
+  def _dens_orient(self, rho):
+    return rho.T.copy()
+
+
+class DensityNormalised(pm.NumpyDevice):
+  """49. reduced_density divides by the trace"""
+  def _dens_scale(self, rho):
+    t = float(np.trace(rho).real)
+    return rho / t if t > 0 else rho
+
+
+class DensityHeldBitAccepted(pm.NumpyDevice):
+  """50. reduced_density drops a listed bit that the shard index holds instead of refusing the call"""
+  def _dens_local(self, b):
+    return True
+
+
+class DensityFoldCounted(pm.NumpyDevice):
+  """51. reduced_density counts its fold kernel"""
+  def _dens_kernels(self):
+    return 2
+
+
+class DensityDoesNotFlush(pm.NumpyDevice):
+  """52. reduced_density reads the state without running what is queued"""
+  def _dens_enter(self):
+    pass
+
+
+class DensityBothTrianglesComputed(pm.NumpyDevice):
+  """53. reduced_density computes the lower triangle on its own: an ulp away from the mirror of the upper one"""
+  def _dens_mirror(self, rho):
+    return np.triu(rho) + np.tril(rho, -1) * (1 + 2.0 ** -52)
+
+
+class DensityCanonicalises(pm.NumpyDevice):
+  """54. reduced_density leaves the local bits in canonical order"""
+  def _dens_layout(self):
+    self._canonicalize()
+
+
+class DensitySweptIsTheShard(pm.NumpyDevice):
+  """55. bytes_swept grows by the shard's bytes, not by the bytes the kernel requests (k = 7, 8 read the state 2, 4 times)"""
+  def _dens_swept(self, plan, amp_bytes):
+    return (1 << self.nbits) * amp_bytes
+
+
+class DensityRefusalFlushes(pm.NumpyDevice):
+  """56. reduced_density runs what is queued before it checks its arguments"""
+  def _dens_check(self, who, bits):
+    if who == 'reduced_density':
+      self.flush()
+    super()._dens_check(who, bits)
+
+
+class ZpolySignFlipped(pm.NumpyDevice):
+  """57. a term counts -w where the parity of i & z is even"""
+  def _zp_parity(self, w, z):
+    return -w if z else w
+
+
+class ZpolyConstantDropped(pm.NumpyDevice):
+  """58. a constant term (no local z bit) is dropped"""
+  def _zp_terms(self, terms):
+    return [(w, z) for w, z in terms if z]
+
+
+class ZpolyHeldSignNotFolded(pm.NumpyDevice):
+  """59. the sign the shard index gives a held z bit is not folded into the weight"""
+  def _zp_fold(self, w, z, held):
+    return w
+
+
+class ZpolyConjugatesC(pm.NumpyDevice):
+  """60. apply_zpoly multiplies by exp(conj(c) f)"""
+  def _zp_c(self, c):
+    return c.conjugate()
+
+
+class ZpolyLeavesOutExp(pm.NumpyDevice):
+  """61. apply_zpoly leaves exp(c.re f) out: the phase alone"""
+  def _zp_factor(self, c, f):
+    return np.cos(c.imag * f) + 1j * np.sin(c.imag * f)
+
+
+class ZpolyNormBeforeTheApply(pm.NumpyDevice):
+  """62. norm2 of apply_zpoly is summed from the amplitudes as they were before the call"""
+  def _zp_norm2(self, first, stored):
+    return first
+
+
+class ZpolyNoopCountsAKernel(pm.NumpyDevice):
+  """63. apply_zpoly with no terms or c == (0, 0) counts a kernel"""
+  def _zp_noop_kernels(self):
+    return 1
+
+
+class ZpolyCanonicalises(pm.NumpyDevice):
+  """64. apply_zpoly leaves the local bits in canonical order"""
+  def _zp_layout(self):
+    self._canonicalize()
+
+
+class ZpolyRefusalFlushes(pm.NumpyDevice):
+  """65. apply_zpoly / expect_zpoly run what is queued before they check their arguments"""
+  def _zp_check(self, who, ws, zs, c=None):
+    if who != 'zpoly_plan':
+      self.flush()
+    super()._zp_check(who, ws, zs, c)
+
+
+class ZpolyDoesNotFlush(pm.NumpyDevice):
+  """66. apply_zpoly works on the state without running what is queued"""
+  def _zp_enter(self):
+    pass
+
+
+class ZpolyBytesOnce(pm.NumpyDevice):
+  """67. the byte counters of apply_zpoly grow by 1 x the shard's bytes"""
+  def _zp_bytes(self, shard_bytes):
+    return shard_bytes
+
+
+class ExpectSecondIsMeanSquared(pm.NumpyDevice):
+  """68. the third sum of expect_zpoly is (sum p f)^2 / sum p"""
+  def _ezp_second(self, p, f):
+    return float(np.dot(p, f)) ** 2 / float(np.sum(p))
+
+
+class ExpectDoesNotFlush(pm.NumpyDevice):
+  """69. expect_zpoly reads the state without running what is queued"""
+  def _ezp_enter(self):
+    pass
+
+
+class ExpectCanonicalises(pm.NumpyDevice):
+  """70. expect_zpoly leaves the local bits in canonical order"""
+  def _ezp_layout(self):
+    self._canonicalize()
+
+
+class ExpectBytesTwice(pm.NumpyDevice):
+  """71. the byte counters of expect_zpoly grow by 2 x the shard's bytes"""
+  def _ezp_bytes(self, shard_bytes):
+    return 2 * shard_bytes
+
+
+class DensityNotRepeatable(pm.NumpyDevice):
+  """72. every second call of reduced_density sums in another order: an ulp away in one entry"""
+  def reduced_density(self, bits):
+    rho = super().reduced_density(bits)
+    self._dens_calls = getattr(self, '_dens_calls', 0) + 1
+    if self._dens_calls % 2 == 0 and rho.size > 1:
+      rho[0, 1] *= 1 + 2.0 ** -52
+      rho[1, 0] = np.conj(rho[0, 1])
+    elif self._dens_calls % 2 == 0:
+      rho[0, 0] *= 1 + 2.0 ** -52
+    return rho
+
+
+class DensityRefusalTouchesTheState(pm.NumpyDevice):
+  """73. a refused reduced_density negates the first stored amplitude"""
+  def _dens_check(self, who, bits):
+    try:
+      super()._dens_check(who, bits)
+    except pm.native.QhError:
+      if who == 'reduced_density':
+        self.phys[0] = -self.phys[0]
+      raise
+
+
+class ZpolyNotRepeatable(pm.NumpyDevice):
+  """74. every second apply_zpoly sums its norm2 in another order: an ulp away"""
+  def _zp_norm2(self, first, stored):
+    self._zp_calls = getattr(self, '_zp_calls', 0) + 1
+    return super()._zp_norm2(first, stored) * (1 + 2.0 ** -52 * (self._zp_calls % 2 == 0))
+
+
+class ZpolyRefusalCountsAGate(pm.NumpyDevice):
+  """75. a refused apply_zpoly / expect_zpoly counts gates_submitted + 1"""
+  def _zp_check(self, who, ws, zs, c=None):
+    try:
+      super()._zp_check(who, ws, zs, c)
+    except pm.native.QhError:
+      self.submitted += who != 'zpoly_plan'
+      raise
+
+
+class ExpectNotRepeatable(pm.NumpyDevice):
+  """76. every second expect_zpoly sums in another order: the second moment an ulp away"""
+  def _ezp_second(self, p, f):
+    self._ezp_calls = getattr(self, '_ezp_calls', 0) + 1
+    return super()._ezp_second(p, f) * (1 + 2.0 ** -52 * (self._ezp_calls % 2 == 0))
+
+
+class ExpectZeroTermsSumApart(pm.NumpyDevice):
+  """77. expect_zpoly with no terms sums |a|^2 in an order of its own: an ulp away from norm2"""
+  def expect_zpoly(self, weights, zmasks):
+    out = super().expect_zpoly(weights, zmasks)
+    return out if len(zmasks) else (out[0] * (1 + 2.0 ** -52), out[1], out[2])
+
+
+class DensityTouchesTheState(pm.NumpyDevice):
+  """78. reduced_density negates the first stored amplitude on its way out"""
+  def _dens_layout(self):
+    self.phys[0] = -self.phys[0]
+
+
+class ExpectTouchesTheState(pm.NumpyDevice):
+  """79. expect_zpoly negates the first stored amplitude on its way out"""
+  def _ezp_layout(self):
+    self.phys[0] = -self.phys[0]
+
+
+class ZpolyNoopNormSumsApart(pm.NumpyDevice):
+  """80. apply_zpoly with no terms or c == (0, 0) sums its norm2 in an order of its own: an ulp away from norm2"""
+  def apply_zpoly(self, weights, zmasks, c, norm=False):
+    n2 = super().apply_zpoly(weights, zmasks, c, norm)
+    return n2 * (1 + 2.0 ** -52) if norm and (not len(zmasks) or complex(c) == 0) else n2
+
+
+class ZpolyNamesAnotherTerm(pm.NumpyDevice):
+  """81. a refused apply_zpoly / expect_zpoly names the last term of the list, not the first offending one"""
+  def _zp_check(self, who, ws, zs, c=None):
+    try:
+      super()._zp_check(who, ws, zs, c)
+    except pm.native.QhError as e:
+      raise pm.native.QhError(e.code, f'{who}: term {len(zs) - 1} has a non-finite weight') if 'non-finite weight' in str(e) else e
+
+
+DENSITY_MUTANTS = [DensityRowsReversed, DensityTransposed, DensityNormalised, DensityHeldBitAccepted, DensityFoldCounted, DensityDoesNotFlush,
+                   DensityBothTrianglesComputed, DensityCanonicalises, DensitySweptIsTheShard, DensityRefusalFlushes,
+                   DensityNotRepeatable, DensityRefusalTouchesTheState, DensityTouchesTheState]
+ZPOLY_MUTANTS = [ZpolySignFlipped, ZpolyConstantDropped, ZpolyHeldSignNotFolded, ZpolyConjugatesC, ZpolyLeavesOutExp, ZpolyNormBeforeTheApply,
+                 ZpolyNoopCountsAKernel, ZpolyCanonicalises, ZpolyRefusalFlushes, ZpolyDoesNotFlush, ZpolyBytesOnce, ExpectSecondIsMeanSquared,
+                 ExpectDoesNotFlush, ExpectCanonicalises, ExpectBytesTwice, ZpolyNotRepeatable, ZpolyRefusalCountsAGate, ExpectNotRepeatable,
+                 ExpectZeroTermsSumApart, ExpectTouchesTheState, ZpolyNoopNormSumsApart, ZpolyNamesAnotherTerm]
 MUTANTS = [QueueBehindBarrier, CopyKeepsQueue, CopyDropsBitmap, ReleaseKeepsLogicalNumbers, ExtendOnTop, MuxSelectorsReversed,
            TopkTiesByPhysicalIndex, AxpbyReadsDstAnyway, SelectInPhysicalOrder, ReaderCanonicalises, MarginalIgnoresHeldBits,
            RoundsTwice, ReaderTurnsRelayoutOn, PermTableBackwards, PermBitsAscending, PermHeldControlMet, PermCanonicalises,
@@ -455,15 +735,25 @@ MUTANTS = [QueueBehindBarrier, CopyKeepsQueue, CopyDropsBitmap, ReleaseKeepsLogi
            PauliUnitComputes, PauliNormUnrounded, ProductTermsReversed, ProductSortsByX, ProductIgnoresHeldZ, ProductPlusI,
            ProductNeverFlips, ProductBeforeItsQueue, ProductChecksLateTermsLate, ProductCanonicalises, ProductRunsOf16,
            ProductZeroTermsCountAKernel, ProductZeroTermsDoNotFlush, ProductUnitComputes, ProductIdentityComputes, ProductNormUnrounded,
-           ProductNormByFirstRun, ProductBytesOncePerCall]
+           ProductNormByFirstRun, ProductBytesOncePerCall] + DENSITY_MUTANTS + ZPOLY_MUTANTS
 PERM_MUTANTS = MUTANTS[13:20]
 PAULI_MUTANTS = MUTANTS[20:30]
-PRODUCT_MUTANTS = MUTANTS[30:]
+PRODUCT_MUTANTS = MUTANTS[30:46]
 
 
 def _product_step(s):
   """a 'pauli_product' step, or a call of apply_pauli_product that is to be refused"""
   return s['op'] == 'pauli_product' or (s['op'] == 'refused' and s['what'].startswith('pauli_product_'))
+
+
+def _density_step(s):
+  """a 'reduced_density' step, or a call of reduced_density that is to be refused"""
+  return s['op'] == 'reduced_density' or (s['op'] == 'refused' and s['what'].startswith('density_'))
+
+
+def _zpoly_step(s, ops=('zpoly', 'expect_zpoly')):
+  """a 'zpoly' / 'expect_zpoly' step, or a call of apply_zpoly / expect_zpoly that is to be refused"""
+  return s['op'] in ops or (s['op'] == 'refused' and s['what'].startswith(tuple(op + '_' for op in ops)))
 
 
 @pytest.mark.parametrize('mutant', MUTANTS, ids=[m.__name__ for m in MUTANTS])
@@ -487,6 +777,18 @@ def test_the_runner_fails_on_a_broken_device(mutant):
       order = [key for key in order if key[2] == 64]
     if mutant is ProductZeroTermsDoNotFlush:                  # (it differs on a list of no terms alone)
       order = [key for key in order if any(s['op'] == 'pauli_product' and not s['x'] for s in program(*key))]
+  if mutant in DENSITY_MUTANTS:                               # (they differ from NumpyDevice in reduced_density alone)
+    order = [key for key in order if any(_density_step(s) for s in program(*key))]
+    if mutant is DensityHeldBitAccepted:
+      order = [key for key in order if key[0] == 'shard']
+    if mutant is DensitySweptIsTheShard:                      # (it differs where the state is read more than once alone)
+      order = [key for key in order if any(s['op'] == 'reduced_density' and len(s['bits']) >= 7 for s in program(*key))]
+  if mutant in ZPOLY_MUTANTS:                                 # (they differ from NumpyDevice in apply_zpoly / expect_zpoly alone)
+    ops = ('expect_zpoly',) if mutant.__name__.startswith('Expect') else \
+        ('zpoly',) if (mutant in ZPOLY_MUTANTS[3:11] and mutant is not ZpolyRefusalFlushes) or mutant in (ZpolyNotRepeatable, ZpolyNoopNormSumsApart) else ('zpoly', 'expect_zpoly')
+    order = [key for key in order if any(_zpoly_step(s, ops) for s in program(*key))]
+    if mutant is ZpolyHeldSignNotFolded:
+      order = [key for key in order if key[0] == 'shard']
   for key in order:
     try:
       run_on(mutant, *key)
@@ -499,6 +801,10 @@ def test_the_runner_fails_on_a_broken_device(mutant):
         assert e.step['op'] == 'pauli_sum', e.step['op']
       if mutant in PRODUCT_MUTANTS:                                                   # ... or a Pauli product (applied or refused)
         assert _product_step(e.step), e.step
+      if mutant in DENSITY_MUTANTS:                                                   # ... or a reduced density
+        assert _density_step(e.step), e.step
+      if mutant in ZPOLY_MUTANTS:                                                     # ... or a Z-polynomial
+        assert _zpoly_step(e.step), e.step
       return
   raise AssertionError(f'{mutant.__name__} ({mutant.__doc__}) passes every fixed program')
 
@@ -507,7 +813,7 @@ def test_the_runner_fails_on_a_broken_device(mutant):
 def coverage(bw):
   kinds = dict.fromkeys(pm.KINDS, 0)
   permuted = dict.fromkeys(pm.BARRIERS + pm.READERS, 0)
-  queued = dict.fromkeys(pm.BARRIERS + pm.READERS + ('clone', 'copy', 'extend', 'release', 'inner', 'axpby', 'pauli_sum', 'pauli_product', 'remap'), 0)
+  queued = dict.fromkeys(pm.BARRIERS + pm.READERS + ('clone', 'copy', 'extend', 'release', 'inner', 'axpby', 'pauli_sum', 'pauli_product', 'zpoly', 'remap'), 0)
   paths = {(op, p): 0 for op in pm.TWO_STATE for p in (pm.LINEAR, pm.TILES, pm.GATHER)}
   for (mode, seed, w), c in checks().items():
     if w != bw:
@@ -684,6 +990,110 @@ PAULI_PRODUCT_AT_LEAST_64 = {'main shape: half walk, few term slots': 1, 'main s
                              'complex64: physical bit 0 in X of a pair or lane run': 1, 'complex64: physical bit 0 in a z mask': 2}
 
 
+def density_counts(records, bw):
+  """what 'reduced_density' steps met, from (mode, non-identity local map, record of _Runner.run_reduced_density); shared with the
+  closing item of tests/test_gpu_program_fuzz.py, which counts what the real qh_density_plan and qh_get_bitmap said"""
+  n = {}
+  def count(name, cond):
+    n[name] = n.get(name, 0) + bool(cond)
+  for mode, permuted, r in records:
+    tiles = r['path'] == pm.native.QH_DENSITY_TILES
+    count('GATHER path', not tiles)
+    count('TILES path', tiles)
+    count('k = 0', r['k'] == 0)
+    count('k in 1-2', 1 <= r['k'] <= 2)
+    count('k in 3-5', 3 <= r['k'] <= 5)
+    count('k = 6', r['k'] == 6)
+    count('k = 7 (3 block pairs)', r['k'] == 7 and r['block_pairs'] == 3)
+    count('k = 8 (10 block pairs)', r['k'] == 8 and r['block_pairs'] == 10)
+    count('k = nloc', r['k'] == r['nloc'])
+    count('row_bit not the identity', not r['row_identity'])
+    count('the register holds physical position 0', r['pos0'])
+    count('the register holds physical positions 0 and 1', r['pos01'])
+    count('chunk_bits cut short by the environment', tiles and r['nrest'] == 0)      # cb == ne
+    count('chunks_per_wg > 1', tiles and r['chunks_per_wg'] > 1)
+    count('behind a queued burst', r['queued'])
+    count('on a non-identity local map its own flush left', r['relaid'])
+    count('on a non-identity local map', permuted)
+    count('on a shard', r['shard'])
+    count('on an attached handle', mode == 'attached' and r['fixed'])
+    count('on a host-mapped handle', mode == 'mapped' and r['fixed'])
+    count('right behind extend, release or copy', r['fresh'] is not None)
+  return n
+
+
+DENSITY_LINES = ('GATHER path', 'TILES path', 'k = 0', 'k in 1-2', 'k in 3-5', 'k = 6', 'k = 7 (3 block pairs)', 'k = 8 (10 block pairs)', 'k = nloc',
+                 'row_bit not the identity', 'the register holds physical position 0', 'the register holds physical positions 0 and 1',
+                 'chunk_bits cut short by the environment', 'behind a queued burst', 'on a non-identity local map its own flush left', 'on a shard',
+                 'on an attached handle', 'on a host-mapped handle', 'right behind extend, release or copy')      # ('chunks_per_wg > 1': at either width)
+DENSITY_AT_LEAST = dict({k: 1 for k in DENSITY_LINES}, **{'GATHER path': 2, 'TILES path': 3, 'row_bit not the identity': 3, 'behind a queued burst': 3,
+                                                          'on a non-identity local map': 3, 'refused: density_nonlocal': 1, 'refused: density_same_qubit': 1,
+                                                          'refused: density_bad_qubit': 1, 'refused: density_k_range': 1})
+
+
+def zpoly_counts(records, bw):
+  """what 'zpoly' or 'expect_zpoly' steps met, from (mode, non-identity local map, record of _Runner.run_zpoly / run_expect_zpoly);
+  shared with the closing item of tests/test_gpu_program_fuzz.py, which counts what the real qh_zpoly_plan and qh_get_bitmap said"""
+  n = {}
+  def count(name, cond):
+    n[name] = n.get(name, 0) + bool(cond)
+  for mode, permuted, r in records:
+    count('small kernel', not r['main'] and r['nterms'])
+    count('main kernel', r['main'] and r['nterms'])
+    for c in pm.ZPOLY_CLASSES.values():
+      count(f'main kernel: a {c} term', c in r['classes'])
+    for kd in pm.ZPOLY_GROUP_KINDS:
+      count(f'a {kd} group', r['group_kinds'][kd] >= 1)
+    count('two or more groups of one kind', any(v >= 2 for v in r['group_kinds'].values()))
+    count('a segment with more than 64 terms', r['seg_over_64'])
+    count('a segment with 2 to 63 terms', r['seg_2_to_63'])
+    count('4096 terms', r['nterms'] == pm.ZPOLY_MAX_TERMS)
+    count('duplicate masks', r['duplicates'])
+    count('zero terms', r['nterms'] == 0)
+    count('zero terms behind a queue', r['nterms'] == 0 and r['queued'])
+    count('behind a queued burst', r['queued'])
+    count('shard: a held bit in a mask where the sign is negative', r['shard'] and r['neg_held'])
+    count('on a non-identity local map its own flush left', r['relaid'])
+    count('on a non-identity local map', permuted)
+    count('on an attached handle', mode == 'attached' and r['fixed'])
+    count('on a host-mapped handle', mode == 'mapped' and r['fixed'])
+    if r['c'] is not None:                                   # apply_zpoly alone
+      for kind, name in (('re0', 'c.re == 0'), ('im0', 'c.im == 0'), ('general', 'general c'), ('zero', 'c == (0, 0)')):
+        count(name, r['c'] == kind)
+      count('norm2 asked', r['norm'])
+      count('norm2 not asked', not r['norm'])
+    if bw == 64:
+      count('complex64: physical bit 0 in a mask', r['pz0'])
+  return n
+
+
+ZPOLY_LINES = ('small kernel', 'main kernel') + tuple(f'main kernel: a {c} term' for c in pm.ZPOLY_CLASSES.values()) + \
+    tuple(f'a {kd} group' for kd in pm.ZPOLY_GROUP_KINDS) + ('two or more groups of one kind', 'a segment with more than 64 terms', 'a segment with 2 to 63 terms',
+                                                            '4096 terms', 'duplicate masks', 'shard: a held bit in a mask where the sign is negative',
+                                                            'on a non-identity local map its own flush left', 'on an attached handle', 'on a host-mapped handle')
+ZPOLY_APPLY_LINES = ZPOLY_LINES + ('c.re == 0', 'c.im == 0', 'general c', 'c == (0, 0)', 'zero terms behind a queue', 'norm2 asked', 'norm2 not asked')
+ZPOLY_LINES_64 = ('complex64: physical bit 0 in a mask',)
+ZPOLY_AT_LEAST = dict({k: 1 for k in ZPOLY_APPLY_LINES}, **{'small kernel': 3, 'main kernel': 3, 'behind a queued burst': 3, 'on a non-identity local map': 3,
+                                                            'refused: zpoly_nonfinite': 1, 'refused: zpoly_bad_qubit': 1, 'refused: zpoly_too_many': 1})
+EXPECT_ZPOLY_AT_LEAST = dict({k: 1 for k in ZPOLY_LINES}, **{'small kernel': 3, 'main kernel': 3, 'zero terms': 1, 'behind a queued burst': 3,
+                                                             'on a non-identity local map': 3, 'refused: expect_zpoly_nonfinite': 1,
+                                                             'refused: expect_zpoly_bad_qubit': 1, 'refused: expect_zpoly_too_many': 1})
+
+
+def new_kind_coverage(op, bw):
+  """what the steps of one of the three kinds met in the fixed programs, from the plans NumpyDevice gives on its own bit map, and
+  the refusals of its call from the programs themselves"""
+  records = [(mode, e[2], e[5]) for (mode, seed, w), c in checks().items() if w == bw for e in c.events if e[1] == op]
+  n = density_counts(records, bw) if op == 'reduced_density' else zpoly_counts(records, bw)
+  prefix = 'density_' if op == 'reduced_density' else op + '_'
+  for (mode, seed, w) in checks():
+    for s in program(mode, seed, w):
+      if w == bw and s['op'] == 'refused' and s['what'].startswith(prefix):
+        n['refused: ' + s['what']] = n.get('refused: ' + s['what'], 0) + 1
+        n['refused on a handle with a queue'] = n.get('refused on a handle with a queue', 0) + bool(s['queued'])
+  return n
+
+
 @pytest.mark.parametrize('bw', WIDTHS)
 def test_coverage_of_the_fixed_programs(bw):
   kinds, permuted, queued, paths = coverage(bw)
@@ -707,6 +1117,20 @@ def test_coverage_of_the_fixed_programs(bw):
   products = pauli_product_coverage(bw)
   print('  pauli_product steps: ' + ', '.join(f'{k} {n}' + (f' (>= {least[k]})' if k in least else '') for k, n in products.items()))
   assert all(products.get(k, 0) >= v for k, v in least.items()), {k: products.get(k, 0) for k, v in least.items() if products.get(k, 0) < v}
+  for op, table in (('reduced_density', DENSITY_AT_LEAST), ('zpoly', ZPOLY_AT_LEAST), ('expect_zpoly', EXPECT_ZPOLY_AT_LEAST)):
+    least = dict(table, **({k: 1 for k in ZPOLY_LINES_64} if bw == 64 and op != 'reduced_density' else {}))
+    met = new_kind_coverage(op, bw)
+    print(f'  {op} steps: ' + ', '.join(f'{k} {n}' + (f' (>= {least[k]})' if k in least else '') for k, n in met.items()))
+    assert all(met.get(k, 0) >= v for k, v in least.items()), (op, {k: met.get(k, 0) for k, v in least.items() if met.get(k, 0) < v})
+  both = sum(new_kind_coverage('reduced_density', w).get('chunks_per_wg > 1', 0) for w in WIDTHS)
+  print(f'  reduced_density steps with chunks_per_wg > 1, both widths together: {both}')
+  assert both >= 1
+  ratios = {}
+  for (mode, seed, w), c in checks().items():
+    if w == bw:
+      for k, v in c.ratios.items():
+        ratios[k] = max(ratios.get(k, 0.0), v)
+  print('  largest error as a fraction of its derived bound: ' + ', '.join(f'{k} {v:.3g}' for k, v in sorted(ratios.items())))
 
 
 def test_the_long_running_tool_ends_at_the_first_failure(monkeypatch, capsys):

@@ -39,18 +39,21 @@ def np_f(idx, weights, zmasks):
   return f
 
 
-def np_apply(psi, weights, zmasks, c, idx=None):
-  """exp(c f) psi in complex128; psi holds the amplitudes at idx (default: every index in order)"""
+def np_apply(psi, weights, zmasks, c, idx=None, f=None):
+  """exp(c f) psi in complex128; psi holds the amplitudes at idx (default: every index in order); f: np_f at idx where the
+  caller has it already (the program fuzzer evaluates a step's f once)"""
   v = np.asarray(psi).reshape(-1).astype(np.complex128)
-  f = np_f(np.arange(v.size, dtype=np.uint64) if idx is None else idx, weights, zmasks)
+  if f is None:
+    f = np_f(np.arange(v.size, dtype=np.uint64) if idx is None else idx, weights, zmasks)
   return v * np.exp(complex(c) * f)
 
 
-def np_moments(psi, weights, zmasks, idx=None):
-  """(sum p, sum p f, sum p f^2) in float64"""
+def np_moments(psi, weights, zmasks, idx=None, f=None):
+  """(sum p, sum p f, sum p f^2) in float64; f as for np_apply"""
   v = np.asarray(psi).reshape(-1).astype(np.complex128)
   p = v.real * v.real + v.imag * v.imag
-  f = np_f(np.arange(v.size, dtype=np.uint64) if idx is None else idx, weights, zmasks)
+  if f is None:
+    f = np_f(np.arange(v.size, dtype=np.uint64) if idx is None else idx, weights, zmasks)
   return float(np.sum(p)), float(np.dot(p, f)), float(np.dot(p, f * f))
 
 

@@ -4,7 +4,8 @@
 The generator and the runner are the suite's (tests/program_model.py; tests/test_gpu_program_fuzz.py runs a fixed list):
 queued gate bursts, barrier mutators (dense matrices, table-selected gates, diagonals, register permutations, scalings,
 projections), readers, handle steps, two-state steps, Pauli-sum operators (qh_apply_pauli_sum / qh_pauli_sum_new), in-place Pauli
-products (qh_apply_pauli_product) and layout steps, program after program, seeds SEED, SEED + 1, ...,
+products (qh_apply_pauli_product), reduced density matrices (qh_reduced_density), Z-polynomials (qh_apply_zpoly /
+qh_expect_zpoly) and layout steps, program after program, seeds SEED, SEED + 1, ...,
 each at both widths, until SECONDS have passed.  It ENDS AT THE FIRST FAILURE of any kind -- a step the model disagrees
 with, or an exception such as a QhError that wraps a HIP fault: no further program is started on a device that may have
 faulted.  The failure prints one JSON line with the seed, the width, the mode, the index of the failing step and the step,
