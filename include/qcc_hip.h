@@ -647,6 +647,42 @@ typedef struct {
 } qh_zpoly_info;
 int qh_zpoly_plan(qh_handle h, uint64_t nterms, const double *w, const uint64_t *zmask, qh_zpoly_info *out);
 
+/* ---- matrix elements between two states (kernels_transition.hip.h) -------- */
+/* out[2t], out[2t + 1] = Re, Im of <a|P_t|b> for Pauli strings given as in qh_expect_pauli, over LOGICAL bits:
+ *   <a|P|b> = (-i)^nY * sum_i (-1)^popcount(i & z) * conj(a_i) * b_{i ^ x},   nY = popcount(x & z)
+ * summed over this shard's amplitudes matched by logical index, not normalised, in the caller's term order.  x = z = 0 is
+ * qh_inner(a, b); a == b is allowed (the real part is then what qh_expect_pauli returns).
+ * Handles as in qh_inner: what both have queued runs first, a's stream waits for b's flushed work, the reads run on a's
+ * stream and the host waits; nothing of either handle changes.  Both states are read where they lie, through the walk
+ * qh_inner_plan(a, b) names, b's index XORed with x in b's physical positions, the sign taken from a's physical index.  No
+ * allocation proportional to the state.
+ * Shards: as qh_inner, the handles must hold the same logical bits in the shard index, at the same positions, with the same
+ * shard index (QH_ERR_NONLOCAL).  A z bit the shard index holds is a sign fixed on this shard, folded in on the host; an x
+ * bit there is QH_ERR_NONLOCAL.
+ * Passes: terms are stably sorted by x mask and every group is cut each QH_TRANSITION_BATCH terms at complex128, each
+ * QH_TRANSITION_BATCH / 2 at complex64 (qh_transition_plan reports the passes actually cut); one kernel per pass, one pass
+ * reads each state once.  a's qh_stats: kernels_launched += passes (the folds are not counted), bytes_swept and
+ * bytes_algorithmic += 2 x the shard's bytes per pass; b's are unchanged.
+ * Every product and sum is formed in double from the amplitudes as stored, in a fixed order without float atomics: the same
+ * states, layouts and term list give the same bits.  (-i)^nY and the shard sign are swaps and negations.  nterms = 0 flushes
+ * both handles and launches nothing.
+ * Errors, nothing runs, out untouched, the whole list checked first: QH_ERR_ARG (null handle, null arrays or out with
+ * nterms > 0, dry handle, another device, different nbits (local or global) or width), QH_ERR_BAD_QUBIT (mask bits >=
+ * nbits_global; checked before the dry-handle refusal), QH_ERR_NONLOCAL as above (nothing is flushed).                    */
+#define QH_TRANSITION_BATCH 16
+int qh_transition_pauli(qh_handle a, qh_handle b, uint64_t nterms, const uint64_t *xmask, const uint64_t *zmask,
+                        double *out /* 2 per term: re, im */);
+/* How qh_transition_pauli would run these strings right now: host arithmetic on the two bit maps, runs nothing, flushes
+ * nothing, planner-only handles are allowed and the devices are not compared.  terms (sorted order; may be NULL): px is the x
+ * mask in B's physical local positions, pz the z mask in A's, neg the shard sign, ny = nY mod 4, index the caller's term.
+ * passes (at most cap are written, *npasses is their number): terms [first, first + count) in one kernel, px their common x
+ * mask, walk the QH_INNER_* path.  The engine launches from this very function.  Errors: QH_ERR_ARG (null, different nbits
+ * or width), QH_ERR_BAD_QUBIT, QH_ERR_NONLOCAL as above.                                                                   */
+typedef struct { uint64_t first, count, px; uint32_t walk /* QH_INNER_* */, pad; } qh_transition_pass;
+int qh_transition_plan(qh_handle a, qh_handle b, uint64_t nterms, const uint64_t *xmask, const uint64_t *zmask,
+                       qh_pauli_term *terms /* nterms, sorted order; may be NULL */,
+                       qh_transition_pass *passes, uint64_t cap, uint64_t *npasses);
+
 /* ---- growing and shrinking a state (kernels_resize.hip.h) ----------------- */
 /* Both calls make a NEW handle and leave src as qh_clone leaves it: what src has queued runs first (exchange arrivals are
  * waited for); src keeps its amplitudes, bit map, relayout mode and device pointer.  The new handle lives on src's device with

@@ -44,6 +44,8 @@
 #include "kernels_two_state.hip.h"
 #include "kernels_inner.hip.h"
 #include "kernels_axpby.hip.h"
+#include "kernels_transition.hip.h"
+#include "transition_plan.h"
 #include "kernels_resize.hip.h"
 #include "planner.h"
 #include "kernels_sweep.hip.h"
@@ -768,7 +770,7 @@ int select_device(int device) {
 extern "C" {
 
 const char *qh_last_error(void) { return g_err.c_str(); }
-int qh_version(void) { return 118; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
+int qh_version(void) { return 119; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
 
 int qh_device_count(int *count) {
   if (!count) return fail(QH_ERR_ARG, "null");
@@ -2446,6 +2448,30 @@ int order_after(qh_state_s *a, qh_state_s *b) {
   return QH_OK;
 }
 
+// The geometry of the linear walk: 2^items 16-byte items in chunks of 256 threads x kInnerLoads, at most kInnerBlocks blocks,
+// a whole number of chunks per block
+struct LinearGrid { int cw; uint32_t cpb; uint64_t nblk; };
+LinearGrid linear_grid(int items) {
+  const int cw = std::min(8 + 3, items);
+  const uint64_t nchunks = 1ull << (items - cw), nblk = std::min(nchunks, kInnerBlocks);
+  return {cw, (uint32_t)(nchunks / nblk), nblk};
+}
+// ... and of the tiles walk: the plan's tables as the kernels take them, chunks of 2^cbits tiles; *nblk = the blocks
+qh::InnerTileArgs tile_args(const qh_inner_tiles &pl, uint64_t *nblk) {
+  qh::InnerTileArgs t{};
+  memcpy(t.tile_a, pl.tile_a, 8);
+  memcpy(t.tile_b, pl.tile_b, 8);
+  memcpy(t.shuffle, pl.shuffle, 8);
+  memcpy(t.rest_a, pl.rest_a, sizeof t.rest_a);
+  memcpy(t.rest_b, pl.rest_b, sizeof t.rest_b);
+  t.nrest = (int)pl.nrest;
+  t.cbits = std::min(qh::kInnerChunkBits, t.nrest);
+  const uint64_t nchunks = 1ull << (t.nrest - t.cbits);
+  *nblk = std::min(nchunks, kInnerBlocks);
+  t.cpb = (uint32_t)(nchunks / *nblk);
+  return t;
+}
+
 // The one dispatch of the two-state walks (kernels_two_state.hip.h): the walk pl names, with its geometry (at most
 // kInnerBlocks blocks, a whole number of chunks per block), on a's stream.  Returns the blocks launched: the slab rows an
 // operation that sums has written.
@@ -2455,24 +2481,13 @@ template <typename Op> uint64_t launch_two_state(qh_state_s *a, const qh_state_s
     using R = decltype(x);
     qh::TwoDst<R, Op> *pa = (qh::TwoDst<R, Op> *)a->d_psi;
     const typename qh::AmpT<R>::type *pb = (const typename qh::AmpT<R>::type *)b->d_psi;
-    if (pl.path == QH_INNER_LINEAR) {      // 2^items 16-byte items in chunks of 256 threads x kInnerLoads
-      const int items = a->nloc - qh::Item16<R>::kAmpBits, cw = std::min(8 + 3, items);
-      const uint64_t nchunks = 1ull << (items - cw);
-      nblk = std::min(nchunks, kInnerBlocks);
-      hipLaunchKernelGGL((qh::k_two_linear<R, Op>), dim3((unsigned)nblk), dim3(256), 0, a->stream, pa, pb, op, cw, (uint32_t)(nchunks / nblk), slab);
+    if (pl.path == QH_INNER_LINEAR) {
+      const LinearGrid g = linear_grid(a->nloc - qh::Item16<R>::kAmpBits);
+      nblk = g.nblk;
+      hipLaunchKernelGGL((qh::k_two_linear<R, Op>), dim3((unsigned)nblk), dim3(256), 0, a->stream, pa, pb, op, g.cw, g.cpb, slab);
     } else if constexpr (Op::RS) {      // (the other two walks read b)
       if (pl.path == QH_INNER_TILES) {
-        qh::InnerTileArgs t{};
-        memcpy(t.tile_a, pl.tile_a, 8);
-        memcpy(t.tile_b, pl.tile_b, 8);
-        memcpy(t.shuffle, pl.shuffle, 8);
-        memcpy(t.rest_a, pl.rest_a, sizeof t.rest_a);
-        memcpy(t.rest_b, pl.rest_b, sizeof t.rest_b);
-        t.nrest = (int)pl.nrest;
-        t.cbits = std::min(qh::kInnerChunkBits, t.nrest);
-        const uint64_t nchunks = 1ull << (t.nrest - t.cbits);
-        nblk = std::min(nchunks, kInnerBlocks);
-        t.cpb = (uint32_t)(nchunks / nblk);
+        const qh::InnerTileArgs t = tile_args(pl, &nblk);
         hipLaunchKernelGGL((qh::k_two_tiles<R, Op>), dim3((unsigned)nblk), dim3(256), 0, a->stream, pa, pb, op, t, slab);
       } else {
         qh::InnerGatherArgs g{};
@@ -3296,6 +3311,157 @@ int qh_expect_zpoly(qh_handle h, uint64_t nterms, const double *w, const uint64_
   h->stats.kernels_launched += 1;
   h->stats.bytes_swept += shard_bytes;
   h->stats.bytes_algorithmic += shard_bytes;
+  return QH_OK;
+}
+
+}  // extern "C"
+
+// ---- matrix elements between two states: qh_transition_pauli, qh_transition_plan (kernels_transition.hip.h, transition_plan.h)
+namespace {
+
+struct TransitionPlan {
+  qh_inner_tiles walk;
+  std::vector<qh_pauli_term> terms;
+  std::vector<qh_transition_pass> passes;
+};
+
+int check_transition_args(const qh_state_s *a, const qh_state_s *b, const char *who, uint64_t nterms, const uint64_t *xmask,
+                          const uint64_t *zmask) {
+  if (!a || !b) return fail(QH_ERR_ARG, "%s: null handle", who);
+  if (nterms && (!xmask || !zmask)) return fail(QH_ERR_ARG, "%s: null masks with %llu terms", who, (unsigned long long)nterms);
+  if (a->nloc != b->nloc || a->nglob != b->nglob || a->bw != b->bw)
+    return fail(QH_ERR_ARG, "%s: %d of %d qubits at width %d against %d of %d at width %d", who, a->nloc, a->nglob, a->bw, b->nloc,
+                b->nglob, b->bw);
+  return QH_OK;
+}
+
+// The strings on the two bit maps as they are now (transition_plan.h).  Host arithmetic only: valid on dry handles.
+int plan_transition_for(const qh_state_s *a, const qh_state_s *b, const char *who, uint64_t nterms, const uint64_t *xmask,
+                        const uint64_t *zmask, TransitionPlan *p) {
+  qh::TransitionRefusal why;
+  const int rc = qh::plan_transition(a->nloc, a->nglob, a->bw, a->perm, b->perm, a->shard, b->shard, nterms, xmask, zmask, &p->walk,
+                                     &p->terms, &p->passes, &why);
+  switch (why.kind) {
+    case qh::TransitionRefusal::kNone: break;
+    case qh::TransitionRefusal::kMaskRange:
+      return fail(rc, "%s: term %llu (x 0x%llx, z 0x%llx) has bits >= %d", who, (unsigned long long)why.term,
+                  (unsigned long long)xmask[why.term], (unsigned long long)zmask[why.term], a->nglob);
+    case qh::TransitionRefusal::kShardIndex:
+      return fail(rc, "%s: shard %llu against shard %llu; exchange first", who, (unsigned long long)a->shard, (unsigned long long)b->shard);
+    case qh::TransitionRefusal::kSplitBit:
+      return fail(rc, "%s: logical bit %d is at physical bit %d of one handle and %d of the other, and the shard index holds one of "
+                  "them (local bits: %d); exchange first", who, why.bit, a->perm[why.bit], b->perm[why.bit], a->nloc);
+    case qh::TransitionRefusal::kXHeld:
+      return fail(rc, "%s: term %llu has X or Y on logical bit %d, held by the shard index (physical bit %d, local bits: %d); "
+                  "exchange first", who, (unsigned long long)why.term, why.bit, b->perm[why.bit], a->nloc);
+  }
+  return rc;
+}
+
+template <typename R, int TT>
+void launch_transition_tt(qh_state_s *a, const qh_state_s *b, const qh_inner_tiles &walk, qh::TransArgs ta, double *slab, uint64_t *nblk) {
+  using A = typename qh::AmpT<R>::type;
+  const A *pa = (const A *)a->d_psi, *pb = (const A *)b->d_psi;
+  *nblk = 1;
+  if (walk.path == QH_INNER_LINEAR) {
+    const LinearGrid g = linear_grid(a->nloc - qh::Item16<R>::kAmpBits);
+    ta.cw = g.cw;
+    ta.cpb = g.cpb;
+    *nblk = g.nblk;
+    hipLaunchKernelGGL((qh::k_trans_linear<R, TT>), dim3((unsigned)g.nblk), dim3(256), 0, a->stream, pa, pb, ta, slab);
+  } else if (walk.path == QH_INNER_TILES) {
+    const qh::InnerTileArgs t = tile_args(walk, nblk);
+    hipLaunchKernelGGL((qh::k_trans_tiles<R, TT>), dim3((unsigned)*nblk), dim3(256), 0, a->stream, pa, pb, ta, t, slab);
+  } else {
+    qh::InnerGatherArgs g{};
+    g.nloc = a->nloc;
+    memcpy(g.pos_b, walk.pos_b, sizeof g.pos_b);
+    hipLaunchKernelGGL((qh::k_trans_gather<R, TT>), dim3(1), dim3(256), 0, a->stream, pa, pb, ta, g, slab);
+  }
+}
+
+// one pass on a's stream: its strings' signs split as the walk's kernel takes them.  Returns the columns of a slab row
+// (2 per string of the instantiation) and the blocks launched.
+int launch_transition_pass(qh_state_s *a, const qh_state_s *b, const TransitionPlan &p, const qh_transition_pass &pass, double *slab,
+                           uint64_t *nblk) {
+  qh::TransArgs ta{};
+  ta.px = pass.px;
+  const int ab = a->bw == 128 ? 0 : 1;
+  for (uint64_t k = 0; k < pass.count; ++k) {
+    const uint64_t pz = p.terms[pass.first + k].pz;
+    qh::TransZSplit z{};
+    if (p.walk.path == QH_INNER_LINEAR) z = qh::transition_split_linear(pz, ab);
+    else if (p.walk.path == QH_INNER_TILES) z = qh::transition_split_tiles(pz, p.walk);
+    else z.thread = (uint32_t)pz;
+    ta.zc[k] = z.uniform;
+    ta.zu[k] = (uint8_t)z.reg;
+    ta.zt[k] = (uint8_t)z.thread;
+    ta.zh |= z.half << k;
+  }
+  const bool few = pass.count <= (uint64_t)qh::kTransSmallT;
+  if (a->bw == 128) {
+    if (few) launch_transition_tt<double, qh::kTransSmallT>(a, b, p.walk, ta, slab, nblk);
+    else launch_transition_tt<double, qh::kTransT>(a, b, p.walk, ta, slab, nblk);
+    return 2 * (few ? qh::kTransSmallT : qh::kTransT);
+  }
+  if (few) launch_transition_tt<float, qh::kTransSmallT>(a, b, p.walk, ta, slab, nblk);
+  else launch_transition_tt<float, qh::kTransT64>(a, b, p.walk, ta, slab, nblk);
+  return 2 * (few ? qh::kTransSmallT : qh::kTransT64);
+}
+
+}  // namespace
+
+extern "C" {
+
+int qh_transition_plan(qh_handle a, qh_handle b, uint64_t nterms, const uint64_t *xmask, const uint64_t *zmask, qh_pauli_term *terms,
+                       qh_transition_pass *passes, uint64_t cap, uint64_t *npasses) {
+  int rc = check_transition_args(a, b, "transition_plan", nterms, xmask, zmask);
+  if (rc) return rc;
+  if (!npasses || (cap && !passes)) return fail(QH_ERR_ARG, "transition_plan: null passes or npasses");
+  TransitionPlan p;
+  if ((rc = plan_transition_for(a, b, "transition_plan", nterms, xmask, zmask, &p))) return rc;
+  if (terms && nterms) memcpy(terms, p.terms.data(), nterms * sizeof(qh_pauli_term));
+  for (uint64_t k = 0; k < p.passes.size() && k < cap; ++k) passes[k] = p.passes[k];
+  *npasses = p.passes.size();
+  return QH_OK;
+}
+
+int qh_transition_pauli(qh_handle a, qh_handle b, uint64_t nterms, const uint64_t *xmask, const uint64_t *zmask, double *out) {
+  int rc = check_transition_args(a, b, "transition_pauli", nterms, xmask, zmask);
+  if (rc) return rc;
+  if (nterms && !out) return fail(QH_ERR_ARG, "transition_pauli: null out with %llu terms", (unsigned long long)nterms);
+  if (a->nglob < 64)
+    for (uint64_t t = 0; t < nterms; ++t)
+      if ((xmask[t] | zmask[t]) >> a->nglob)
+        return fail(QH_ERR_BAD_QUBIT, "transition_pauli: term %llu (x 0x%llx, z 0x%llx) has bits >= %d", (unsigned long long)t,
+                    (unsigned long long)xmask[t], (unsigned long long)zmask[t], a->nglob);
+  if ((rc = check_pair(a, b, "transition_pauli"))) return rc;      // (dry handles, another device)
+  TransitionPlan p;
+  // which bits the shard index holds is not something a flush changes: refused before anything runs
+  if ((rc = plan_transition_for(a, b, "transition_pauli", nterms, xmask, zmask, &p))) return rc;
+  if ((rc = enter(a))) return rc;
+  if (b != a && (rc = enter(b))) return rc;
+  if (nterms == 0) return QH_OK;
+  if ((rc = plan_transition_for(a, b, "transition_pauli", nterms, xmask, zmask, &p))) return rc;      // the layouts the flushes left
+  SlabSum sum{a};
+  HIP_TRY(sum.reserve(kInnerBlocks, 2 * qh::kTransT, 2 * nterms));
+  if (b != a && (rc = order_after(a, b))) return rc;      // a's stream reads b: behind everything b's stream has been given
+  for (const qh_transition_pass &pass : p.passes) {
+    uint64_t nblk = 1;
+    const int cols = launch_transition_pass(a, b, p, pass, sum.slab, &nblk);
+    sum.fold(nblk, cols, (unsigned)(2 * pass.count), 1.0, 2 * pass.first);
+    if ((rc = check_launch(a))) return rc;
+  }
+  std::vector<double> vals(2 * nterms);
+  if ((rc = sum.get(vals.data(), vals.size(), "qh_transition_pauli"))) return rc;
+  for (uint64_t k = 0; k < nterms; ++k) {      // (-i)^nY and the shard sign: swaps and negations
+    const qh_pauli_term &tm = p.terms[k];
+    qh::pauli_coef(vals[2 * k], vals[2 * k + 1], tm.ny, tm.neg, out + 2 * tm.index);
+  }
+  const uint64_t bytes = p.passes.size() * 2 * ((1ull << a->nloc) * a->amp_bytes());
+  a->stats.kernels_launched += p.passes.size();      // reads of the two states: one per pass (the folds are not counted)
+  a->stats.bytes_swept += bytes;
+  a->stats.bytes_algorithmic += bytes;
   return QH_OK;
 }
 

@@ -631,6 +631,38 @@ class DeviceState:
     native.check(self.lib.qh_inner_plan(self.h, other.h, ctypes.byref(t)))
     return t.as_dict()
 
+  # -- matrix elements between two states -------------------------------------------
+  @staticmethod
+  def _mask_arrays(who, xmasks, zmasks):
+    x = np.ascontiguousarray([int(v) for v in xmasks], dtype=np.uint64)
+    z = np.ascontiguousarray([int(v) for v in zmasks], dtype=np.uint64)
+    if x.size != z.size:
+      raise ValueError(f'{who}: {x.size} x masks, {z.size} z masks')
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    return (x, z), x.ctypes.data_as(u64p), z.ctypes.data_as(u64p)
+
+  def transition_pauli(self, other, xmasks, zmasks):
+    """(T,) complex128: <self|P_t|other> of the Pauli strings given as LOGICAL bit masks (x: X or Y on the bit, z: Z or Y),
+    as in expect_pauli, summed over this shard by LOGICAL index, not normalised (qh_transition_pauli: both states are read
+    where they lie, strings that share an x mask share a read of them)."""
+    keep, xp, zp = self._mask_arrays('transition_pauli', xmasks, zmasks)
+    out = np.zeros(keep[0].size, dtype=np.complex128)
+    native.check(self.lib.qh_transition_pauli(self.h, other.h, int(keep[0].size), xp, zp, out.view(np.float64).ctypes.data_as(_dp)))
+    return out
+
+  def transition_plan(self, other, xmasks, zmasks):
+    """How transition_pauli(other, ...) would run these strings right now (qh_transition_plan): (terms, passes), lists of
+    dicts; px is in other's physical positions, pz in this state's."""
+    keep, xp, zp = self._mask_arrays('transition_plan', xmasks, zmasks)
+    n = int(keep[0].size)
+    terms = (native.QhPauliTerm * max(n, 1))()
+    cap = max(n, 1)
+    passes = (native.QhTransitionPass * cap)()
+    npass = ctypes.c_uint64()
+    native.check(self.lib.qh_transition_plan(self.h, other.h, n, xp, zp, terms, passes, cap, ctypes.byref(npass)))
+    tl = [{k: int(getattr(terms[j], k)) for k, _ in native.QhPauliTerm._fields_} for j in range(n)]
+    return tl, [passes[p].as_dict() for p in range(npass.value)]
+
   def project_bits(self, mask, value):
     """Zero every amplitude whose LOGICAL bits under mask differ from value (qh_project_bits); renormalise with scale."""
     native.check(self.lib.qh_project_bits(self.h, int(mask), int(value)))

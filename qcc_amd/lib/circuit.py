@@ -1589,6 +1589,111 @@ class qc:
         self.combine(other, 1.0, -c)
         return c
 
+    # Matrix elements between two states (extensions).  <a|P|b> for a Pauli string between two states that both live in HBM
+    # is one read of each (qh_transition_pauli); without the call on the device, and in aliased mode, the same formula runs
+    # on the host.
+    @staticmethod
+    def _pauli_string_host(v, x, z):
+        """P v for one Pauli string as (x, z) masks over LOGICAL bits: (P v)_i = (-i)^nY (-1)^popcount(i & z) v_{i ^ x},
+        complex128."""
+        v = np.asarray(v).reshape(-1).astype(np.complex128)
+        idx = np.arange(v.size, dtype=np.uint64)
+        par = np.zeros(v.size, dtype=np.uint64)
+        for bit in range(max(int(z).bit_length(), 1)):
+            if (z >> bit) & 1:
+                par ^= (idx >> np.uint64(bit)) & np.uint64(1)
+        return (-1j) ** (bin(x & z).count('1') % 4) * (1.0 - 2.0 * par.astype(np.float64)) * v[idx ^ np.uint64(x)]
+
+    def matrix_element(self, other, terms, *, per_term=False):
+        """complex sum_t c_t <self|P_t|other> for terms = [(c_t, paulis_t), ...] as in expectation() and another circuit or
+        a Snapshot of the same size and width (other may be this circuit), in one device call for the whole list
+        (qh_transition_pauli: both states are read where they lie, strings with the same X/Y positions share a read).
+        per_term=True returns the complex128 array of the <self|P_t|other> instead.  Not divided by the norms."""
+        self._same_shape(other, 'matrix_element')
+        coeffs, xs, zs = self._pauli_terms(terms, 'matrix_element')
+        dev = self._ensure_device()
+        if other is self:
+            odev = dev
+        else:
+            odev = other._ensure_device() if isinstance(other, qc) else other._dev      # pylint: disable=protected-access
+        aliased = self._alias or (isinstance(other, qc) and other._alias)      # pylint: disable=protected-access
+        on_device = odev is not None and not aliased
+        if not xs:
+            vals = np.zeros(0, dtype=np.complex128)
+        elif on_device and hasattr(dev, 'transition_pauli') and hasattr(odev, 'transition_pauli'):
+            vals = np.asarray(dev.transition_pauli(odev, xs, zs), dtype=np.complex128)
+        elif on_device and hasattr(dev, 'inner') and hasattr(odev, 'inner') and hasattr(odev, 'apply_pauli_sum'):
+            vals = np.zeros(len(xs), dtype=np.complex128)
+            for t, (x, z) in enumerate(zip(xs, zs)):
+                w = odev.apply_pauli_sum([1.0], [x], [z])
+                try:
+                    vals[t] = complex(dev.inner(w))
+                finally:
+                    w.close()
+        else:
+            a = np.asarray(self.psi).reshape(-1).astype(np.complex128)
+            b = a if other is self else np.asarray(self._host_amps(other)).reshape(-1)
+            vals = np.array([np.vdot(a, self._pauli_string_host(b, x, z)) for x, z in zip(xs, zs)], dtype=np.complex128)
+        if per_term:
+            return vals
+        return complex(np.dot(np.asarray(coeffs, dtype=np.complex128), vals)) if coeffs else 0j
+
+    def rotation_gradients(self, rotations, terms):
+        """Applies exp(-i theta_k/2 P_k) for rotations = [(paulis_k, theta_k), ...] in order, exactly as pauli_rot would, and
+        returns (E, grad): E = expectation(terms) on the rotated state, which the circuit keeps, and the float64 array
+        grad[k] = dE/dtheta_k, by the adjoint method.  terms is a Hamiltonian with real coefficients (ValueError otherwise).
+
+        With phi_k the state after rotation k and lam_k = (U_{K-1} ... U_{k+1})^+ H |phi_{K-1}>,
+            dE/dtheta_k = 2 Re <lam_k| (-i/2) P_k |phi_k> = Im <lam_k|P_k|phi_k>.
+        lam := hamiltonian_times(terms) and phi := snapshot() are un-evolved in step, exp(+i theta_k/2 P_k) on both, from
+        k = K - 1 down: one matrix element and two in-place passes per rotation, against the 2K circuit executions of the
+        parameter-shift rule.  The two scratch states are closed before returning.  Not recorded in the IR, like evolve."""
+        terms = list(terms)
+        coeffs, hx, hz = self._pauli_terms(terms, 'rotation_gradients')
+        if any(c.imag != 0 for c in coeffs):
+            raise ValueError('rotation_gradients: real coefficients only (H must be Hermitian)')
+        rots = []
+        for rot in rotations:
+            try:
+                paulis, theta = rot
+            except (TypeError, ValueError):
+                raise ValueError(f'rotation_gradients: rotation {rot!r} is not a (paulis, theta) pair') from None
+            rots.append(self._pauli_masks(paulis) + (float(theta),))
+        for x, z, theta in rots:
+            self._pauli_product([math.cos(theta / 2)], [-1j * math.sin(theta / 2)], [x], [z])
+        energy = self.expectation(terms)
+        grad = np.zeros(len(rots), dtype=np.float64)
+        dev = self._ensure_device()
+        if not self._alias and all(hasattr(dev, m) for m in ('transition_pauli', 'apply_pauli_sum', 'apply_pauli_product', 'clone')):
+            lam = dev.apply_pauli_sum(coeffs, hx, hz)
+            phi = None
+            try:
+                phi = dev.clone()
+                for k in range(len(rots) - 1, -1, -1):
+                    x, z, theta = rots[k]
+                    grad[k] = complex(lam.transition_pauli(phi, [x], [z])[0]).imag
+                    if k:
+                        a, b = [math.cos(theta / 2)], [1j * math.sin(theta / 2)]
+                        lam.apply_pauli_product(a, b, [x], [z])
+                        phi.apply_pauli_product(a, b, [x], [z])
+            finally:
+                lam.close()
+                if phi is not None:
+                    phi.close()
+            return energy, grad
+        phi = np.asarray(self.psi).reshape(-1).astype(np.complex128)
+        lam = np.zeros(phi.size, dtype=np.complex128)
+        for c, x, z in zip(coeffs, hx, hz):
+            lam += c * self._pauli_string_host(phi, x, z)
+        for k in range(len(rots) - 1, -1, -1):
+            x, z, theta = rots[k]
+            grad[k] = complex(np.vdot(lam, self._pauli_string_host(phi, x, z))).imag
+            if k:
+                a, b = math.cos(theta / 2), 1j * math.sin(theta / 2)
+                lam = a * lam + b * self._pauli_string_host(lam, x, z)
+                phi = a * phi + b * self._pauli_string_host(phi, x, z)
+        return energy, grad
+
     def pauli_expectation(self, idx):
         p0, _ = self.measure_bit(idx, 0, False)
         return p0 - (1 - p0)

@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB_PATH = os.environ.get('QCC_HIP_LIB') or os.path.join(PKG, 'libqcc_hip.so')  # env: A/B builds only
 SOURCES = [os.path.join(PKG, 'csrc', f) for f in
-           ('engine.hip', 'buffers.hip.h', 'kernels_common.hip.h', 'kernels_gate.hip.h', 'kernels_argmax.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_perm.hip.h', 'perm_plan.h', 'kernels_measure.hip.h', 'kernels_select.hip.h', 'select_plan.h', 'kernels_expect.hip.h', 'kernels_density.hip.h', 'density_plan.h', 'kernels_pauli.hip.h', 'pauli_plan.h', 'kernels_pauli_product.hip.h', 'pauli_product_plan.h', 'kernels_zpoly.hip.h', 'zpoly_plan.h', 'kernels_two_state.hip.h', 'kernels_inner.hip.h', 'kernels_axpby.hip.h', 'inner_plan.h', 'kernels_resize.hip.h', 'resize_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h', 'exchange_plan.h',
+           ('engine.hip', 'buffers.hip.h', 'kernels_common.hip.h', 'kernels_gate.hip.h', 'kernels_argmax.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_perm.hip.h', 'perm_plan.h', 'kernels_measure.hip.h', 'kernels_select.hip.h', 'select_plan.h', 'kernels_expect.hip.h', 'kernels_density.hip.h', 'density_plan.h', 'kernels_pauli.hip.h', 'pauli_plan.h', 'kernels_pauli_product.hip.h', 'pauli_product_plan.h', 'kernels_zpoly.hip.h', 'zpoly_plan.h', 'kernels_two_state.hip.h', 'kernels_inner.hip.h', 'kernels_axpby.hip.h', 'inner_plan.h', 'kernels_transition.hip.h', 'transition_plan.h', 'kernels_resize.hip.h', 'resize_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h', 'exchange_plan.h',
             'sweep_island_rb2.inc', 'sweep_island_rb3.inc', 'sweep_island_rb4.inc',
             'sweep_island_rb5.inc', 'sweep_island_f32_rb2.inc', 'sweep_island_f32_rb3.inc',
             'sweep_island_f32_rb4.inc', 'sweep_island_f32_rb5.inc', 'sweep_island_f32_rb6.inc', 'sweep_handlers.inc',
@@ -118,6 +118,17 @@ class QhPauliRun(ctypes.Structure):
     return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != 'pad'}
 
 
+QH_TRANSITION_BATCH = 16
+
+
+class QhTransitionPass(ctypes.Structure):
+  """include/qcc_hip.h qh_transition_pass: one kernel of qh_transition_pauli."""
+  _fields_ = [('first', _u64), ('count', _u64), ('px', _u64), ('walk', ctypes.c_uint32), ('pad', ctypes.c_uint32)]
+
+  def as_dict(self):
+    return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != 'pad'}
+
+
 QH_ZPOLY_MAX_TERMS = 4096
 QH_ZPOLY_CONST, QH_ZPOLY_HIGH, QH_ZPOLY_LOW, QH_ZPOLY_STRADDLE = 0, 1, 2, 3
 QH_ZPOLY_KERNEL_MAIN, QH_ZPOLY_KERNEL_SMALL = 0, 1
@@ -207,6 +218,9 @@ SIGNATURES = {
     'qh_apply_zpoly': (_i32, [_vp, _u64, _dp, ctypes.POINTER(_u64), _dp, _dp]),
     'qh_expect_zpoly': (_i32, [_vp, _u64, _dp, ctypes.POINTER(_u64), _dp]),
     'qh_zpoly_plan': (_i32, [_vp, _u64, _dp, ctypes.POINTER(_u64), ctypes.POINTER(QhZpolyInfo)]),
+    'qh_transition_pauli': (_i32, [_vp, _vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _dp]),
+    'qh_transition_plan': (_i32, [_vp, _vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(QhPauliTerm),
+                                  ctypes.POINTER(QhTransitionPass), _u64, ctypes.POINTER(_u64)]),
     'qh_extend': (_i32, [_vp, _i32, _dp, _u64, ctypes.POINTER(_vp)]),
     'qh_release': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _u64, _dp, ctypes.POINTER(_vp)]),
     'qh_get_stats': (_i32, [_vp, ctypes.POINTER(QhStats)]),
