@@ -193,6 +193,63 @@ typedef struct {
 } qh_perm_tiles;
 int qh_perm_plan(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, qh_perm_tiles *out);
 
+/* Rank-one register update (kernels_rank1.hip.h): a I + b |u><v| on the register made of LOGICAL bits bits[0..k-1] (bits[0]
+ * least significant, as in qh_apply_diag), identity on every other bit.  A fibre r is one setting of all other bits; for every
+ * fibre whose bits under ctl_mask are all 1
+ *     m_r = sum_s conj(v[s]) psi[s, r],      psi'[s, r] = a psi[s, r] + b u[s] m_r.
+ * u, v: 2^k complex numbers each (interleaved re,im).  u == NULL means u = v.  v == NULL (then u must be NULL too) is the
+ * UNIFORM form: u = v = the vector of 2^(-k/2).  Table form: 1 <= k <= QH_RANK1_MAX_BITS; uniform form: 1 <= k <= nbits_local.
+ * a = -1, b = 2 with a normalised v is the reflection 2|v><v| - I (uniform form: Grover's inversion about the mean), a = 0,
+ * b = 1 the projector |v><v|.  Any finite complex a and b and any finite tables: neither unitarity nor normalisation is checked.
+ * A barrier like qh_apply_perm: what is queued runs first, and the call works on the layout it finds.  Bit map, relayout mode
+ * and device pointer are as before; the caller's arrays are not referenced after the call returns.  Attached, host-mapped and
+ * shard handles, from one local bit up, at both widths.
+ * Arithmetic: in double, from the amplitudes as stored (complex64 widened unrounded); the tables are used as conj(v) and the
+ * double-precision products b * u.  m_r is summed in a fixed order that depends only on the plan and the layout (a pairwise
+ * tree over the register bits inside a tile or chunk, ascending position; the chunks of a fibre group in ascending order; the
+ * segments of a split walk in order), without atomics; every new component is rounded once to the handle's width.  Amplitudes
+ * where a control is 0 keep their bits.  The same state, layout and arguments give the same bits.
+ * sums (may be NULL): sums[0] = the sum of |psi'|^2 over the amplitudes whose controls are met, as stored; sums[1] = the sum of
+ * |m_r|^2 over those fibres (for a normalised v: the probability of finding the register in v).  This shard only, in double,
+ * in the readers' fixed order, bitwise reproducible.  With sums the call waits for the stream.
+ * Two paths (qh_rank1_info below): QH_RANK1_TILE, in place, one read and one write of the tiles whose out-of-tile controls are
+ * met; QH_RANK1_TWO_PASS, two reads and one write of the shard, m_r kept in a scratch buffer of scratch_bytes (QH_ERR_NOMEM,
+ * state unchanged, when there is no room).
+ * qh_stats: gates_submitted + 1, kernels_launched + the plan's kernels (the fold of sums is not counted), bytes_swept + the
+ * plan's bytes_swept, bytes_algorithmic + 2 x the shard's bytes / 2^(local controls).
+ * A control on a shard bit is dropped where met, and the call is a counted no-op (gates_noop; sums = 0, 0) where not.
+ * Errors, nothing runs, nothing changes, nothing is flushed: QH_ERR_ARG (null handle, bits, a or b; u without v; k out of range
+ * for the form; a non-finite coefficient or table entry: qh_last_error names the first offending entry; dry handle),
+ * QH_ERR_BAD_QUBIT, QH_ERR_SAME_QUBIT (a bit twice, a control inside the register), QH_ERR_NONLOCAL (a register bit held by
+ * the shard index), QH_ERR_NOMEM.                                                                                          */
+#define QH_RANK1_MAX_BITS 16
+int qh_apply_rank1(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, const double *u, const double *v,
+                   const double a[2], const double b[2], double *sums /* may be NULL: 2 doubles */);
+/* How qh_apply_rank1 would run right now (nothing runs, nothing is flushed; planner-only handles too; uniform != 0: the
+ * uniform form).  tile: the tile of qh_perm_plan on the register's positions (its path field says only whether it fits LDS;
+ * reg_pos and reg_rank are filled for k <= QH_PERM_MAX_BITS).  QH_RANK1_TILE when tile.lds_bytes <= 128 KiB and, in the table form,
+ * k <= 10 (the tables are staged in LDS behind the tile's products).  Otherwise pass 1
+ * cuts the shard into chunks of 2^chunk_bits consecutive amplitudes; reg_in_chunk register bits lie below chunk_bits and are
+ * summed inside a block, the 2^reg_above chunks that differ only in the other register bits form one of `groups` fibre groups
+ * of fibres_per_chunk fibres each and are walked in ascending order, by `split` blocks of `walk` chunks each; split > 1 adds a
+ * kernel that folds the partial sums in segment order.  Fibre f of the scratch is the physical index with the register bits
+ * taken out.  The engine launches from this very function.  Errors as qh_apply_rank1, without those of tables, coefficients
+ * and dry handles.                                                                                                          */
+#define QH_RANK1_TILE 0         /* in place, tile by tile: registers, fibre sums through LDS   */
+#define QH_RANK1_TWO_PASS 1     /* m_r into scratch, then one update stream                    */
+typedef struct {
+  uint32_t path;               /* QH_RANK1_*                                                  */
+  uint32_t uniform;
+  qh_perm_tiles tile;
+  uint64_t scratch_bytes;      /* TWO_PASS: 16 x nfibres x (1, or 1 + split when split > 1)   */
+  uint64_t bytes_swept;        /* bytes the kernels request                                   */
+  uint64_t nfibres;            /* 2^(nbits_local - k)                                         */
+  uint64_t groups, fibres_per_chunk, walk;      /* pass 1 (0 on the TILE path)                */
+  uint32_t kernels;            /* kernels the call launches                                   */
+  uint32_t chunk_bits, reg_in_chunk, reg_above, split, pad;
+} qh_rank1_info;
+int qh_rank1_plan(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, int uniform, qh_rank1_info *out);
+
 /* The whole stream in one call: ops[2k] = control qubit of gate k or QH_NO_CTL (then qh_apply1), ops[2k+1] =
  * target qubit, gates + 8k = its 8 doubles -- exactly `count` qh_apply1/qh_applyc calls (xgates.cc:89-145), without
  * the per-call cost of the host language's FFI (ctypes: ~3 us per gate).  Stops at the first error.          */

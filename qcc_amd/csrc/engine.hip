@@ -29,6 +29,8 @@
 #include "kernels_mux.hip.h"
 #include "kernels_perm.hip.h"
 #include "perm_plan.h"
+#include "kernels_rank1.hip.h"
+#include "rank1_plan.h"
 #include "kernels_measure.hip.h"
 #include "kernels_select.hip.h"
 #include "select_plan.h"
@@ -111,6 +113,7 @@ struct qh_state_s {
   // qh_apply_zpoly / qh_expect_zpoly: the term block (zpoly_plan.h), written on the host, read by one kernel; one slot of a
   // fixed size, reused only after the event recorded behind that kernel
   qh::StagedUpload<1> zpoly;
+  qh::DeviceBuffer rank1;      // qh_apply_rank1, second path: m_r per fibre and the partial sums of a split walk
   qh::DeviceBuffer meas;       // the readers' scratch (slabs, chunk sums, shot lists, results), grown on demand
   double *d_red() const { return red.as<double>(); }
   uint64_t *d_redi() const { return redi.as<uint64_t>(); }
@@ -770,7 +773,7 @@ int select_device(int device) {
 extern "C" {
 
 const char *qh_last_error(void) { return g_err.c_str(); }
-int qh_version(void) { return 119; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
+int qh_version(void) { return 120; }   // 100 + round: bumped whenever plans, exchange geometry or the C-ABI change
 
 int qh_device_count(int *count) {
   if (!count) return fail(QH_ERR_ARG, "null");
@@ -1859,6 +1862,242 @@ int qh_apply_perm(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, co
   qh::perm_order(k, t.reg_pos, order);
   const std::vector<uint32_t> inv = qh::perm_inverse(k, table, order);
   return t.path == QH_PERM_LDS ? run_perm_lds(h, t, inv) : run_perm_gather(h, t, inv);
+}
+
+}  // extern "C"
+
+// ---- rank-one register updates: qh_apply_rank1, qh_rank1_plan (kernels_rank1.hip.h, rank1_plan.h) --------------------
+namespace {
+
+// The argument checks both calls share, then the plan (rank1_plan.h) on the bit map as it is now.
+int plan_rank1_call(const qh_state_s *h, const char *who, int k, const int32_t *bits, uint64_t ctl_mask, int uniform, qh_rank1_info *out) {
+  const int kmax = uniform ? h->nloc : QH_RANK1_MAX_BITS;
+  if (k < 1 || k > kmax)
+    return fail(QH_ERR_ARG, "%s: k = %d outside [1,%d] (%s)", who, k, kmax, uniform ? "uniform form: the local bits" : "table form");
+  if (h->nglob < 64 && (ctl_mask >> h->nglob))
+    return fail(QH_ERR_BAD_QUBIT, "%s: control mask 0x%llx has bits >= %d", who, (unsigned long long)ctl_mask, h->nglob);
+  uint64_t rmask = 0;
+  const int rc = check_bit_list(h, who, k, bits, &rmask);
+  if (rc) return rc;
+  if (ctl_mask & rmask)
+    return fail(QH_ERR_SAME_QUBIT, "%s: control and register share bits 0x%llx", who, (unsigned long long)(ctl_mask & rmask));
+  // (a logical bit stays local or in the shard index whatever the relayout sweeps do)
+  int pos[64];
+  for (int j = 0; j < k; ++j) {
+    pos[j] = h->perm[bits[j]];
+    if (pos[j] >= h->nloc)
+      return fail(QH_ERR_NONLOCAL, "%s: register bit %d is held by the shard index (physical bit %d, local bits: %d); exchange first",
+                  who, bits[j], pos[j], h->nloc);
+  }
+  const Placed ctl = place(h, to_phys(h, ctl_mask));
+  qh::plan_rank1(h->nloc, h->bw, k, pos, ctl.local, uniform, out);
+  out->tile.k = (uint32_t)k;
+  out->tile.ctl_met = (h->shard & ctl.held) == ctl.held;
+  return QH_OK;
+}
+
+// what the call computes with besides the plan: a, and the tables (empty: the uniform form, conj(v_s) = vr, b u_s = ub)
+struct Rank1Op {
+  double a[2], vr, ub[2];
+  std::vector<double> tab;      // conj(v), then b u: compressed order, interleaved re, im
+  bool uniform() const { return tab.empty(); }
+};
+
+template <typename R, int TAB, int U> int allow_big_lds_rank1() {
+  const hipError_t e =
+      hipFuncSetAttribute((const void *)qh::k_rank1_tile<R, TAB, U>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(QH_ERR_HIP, "apply_rank1: hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(e));
+  }
+  return QH_OK;
+}
+
+// the tail of both paths: the two sums from the slab rows of `nblk` blocks
+int finish_rank1(qh_state_s *h, const qh_rank1_info &pl, const SlabSum &sum, unsigned nblk, double *sums) {
+  h->stats.gates_submitted++;
+  h->stats.kernels_launched += pl.kernels;
+  h->stats.bytes_swept += pl.bytes_swept;
+  h->stats.bytes_algorithmic += (2 * h->amp_bytes() << h->nloc) >> __builtin_popcountll(pl.tile.ctl_in | pl.tile.ctl_out);
+  if (!sums) return QH_OK;
+  sum.fold(nblk, 2, 2);
+  return sum.get(sums, 2, "apply_rank1 sums");
+}
+
+int run_rank1_tile(qh_state_s *h, const qh_rank1_info &pl, const Rank1Op &op, double *sums) {
+  const qh_perm_tiles &t = pl.tile;
+  const int k = (int)t.k;
+  uint8_t ranks[QH_PERM_MAX_BITS];
+  memcpy(ranks, t.reg_rank, sizeof ranks);
+  std::sort(ranks, ranks + k);
+  qh::Rank1TileArgs a{};
+  a.g.n = qh::perm_runs(k, ranks, a.g.run);
+  a.tile_mask = t.tile_mask;
+  a.rest_mask = h->local_mask() & ~t.tile_mask & ~t.ctl_out;
+  a.ctl_out = t.ctl_out;
+  a.ntiles = t.ntiles - t.tiles_skipped;
+  a.m = t.tile_bits;
+  a.nent = op.uniform() ? 0u : 1u << k;
+  for (int p = 0, r = 0; p < h->nloc; ++p) {
+    if (!((t.tile_mask >> p) & 1ull)) continue;
+    if ((t.reg_mask >> p) & 1ull) a.reg_tile |= 1u << r;
+    if ((t.ctl_in >> p) & 1ull) a.ctl_tile |= 1u << r;
+    ++r;
+  }
+  a.ar = op.a[0]; a.ai = op.a[1];
+  a.vr = op.vr; a.ubr = op.ub[0]; a.ubi = op.ub[1];
+  const uint64_t nitems = std::max<uint64_t>(t.lds_bytes / 16, 1);
+  unsigned threads = 64;                                   // four items per thread (eight in the largest tiles), one to sixteen waves
+  while (threads < 1024 && threads * 4ull < nitems) threads *= 2;
+  if ((uint64_t)threads * qh::kPermItems < nitems) return fail(QH_ERR_ARG, "apply_rank1: a tile of %llu items", (unsigned long long)nitems);
+  const uint32_t lbits = (uint32_t)log2_u64((uint64_t)threads * (16 / h->amp_bytes()));
+  const uint32_t ureg = lbits < 32 ? (a.reg_tile >> lbits) & (uint32_t)(qh::kPermItems - 1) : 0u;
+  a.nslots = (1u << a.m) >> __builtin_popcount(ureg);
+  const int tab = op.uniform() ? 0 : 1;
+  const bool eight = (uint64_t)threads * 4 < nitems;       // (then every bit of the item number is a register bit: checked below)
+  const size_t lds = std::max<size_t>((size_t)a.nslots * 16 + (tab == 1 ? (size_t)a.nent * 32 : 0), 256);
+  if ((size_t)a.nslots * 16 > qh::kPermLdsBytes || lds > (160u << 10))
+    return fail(QH_ERR_ARG, "apply_rank1: %zu bytes of LDS for a tile of %u bits", lds, a.m);
+  int rc = QH_OK;
+  if (eight && ureg != (uint32_t)(qh::kPermItems - 1)) return fail(QH_ERR_ARG, "apply_rank1: a tile of %u bits with free top bits", a.m);
+  auto with_kernel = [&](auto &&f) {       // f(R, TAB, U)
+    with_real(h, [&](auto x) {
+      using I0 = std::integral_constant<int, 0>;
+      using I1 = std::integral_constant<int, 1>;
+      using U4 = std::integral_constant<int, 4>;
+      using U8 = std::integral_constant<int, qh::kPermItems>;
+      if (tab == 0 && !eight) f(x, I0{}, U4{});
+      else if (tab == 0) f(x, I0{}, U8{});
+      else if (!eight) f(x, I1{}, U4{});
+      else f(x, I1{}, U8{});
+    });
+  };
+  if (lds > (64u << 10)) with_kernel([&](auto x, auto tb, auto uu) { rc = allow_big_lds_rank1<decltype(x), decltype(tb)::value, decltype(uu)::value>(); });
+  if (rc) return rc;
+  const unsigned grid = (unsigned)std::min<uint64_t>(a.ntiles, (uint64_t)std::max(1, env_int("QH_RANK1_GRID", 2048)));
+  SlabSum sum{h};
+  if (sums) HIP_TRY(sum.reserve(std::max<uint64_t>(grid, 8), 2, 2));
+  const void *dtab = nullptr;
+  if (tab && (rc = stage_perm_table(h, op.tab.data(), op.tab.size() * sizeof(double), &dtab))) return rc;
+  with_kernel([&](auto x, auto tb, auto uu) {
+    using R = decltype(x);
+    hipLaunchKernelGGL((qh::k_rank1_tile<R, decltype(tb)::value, decltype(uu)::value>), dim3(grid), dim3(threads), lds, h->stream,
+                       (typename qh::AmpT<R>::type *)h->d_psi, (const qh::perm_item *)dtab, a, sums ? sum.slab : nullptr);
+  });
+  if ((rc = check_launch(h))) return rc;
+  if (tab) HIP_TRY(h->tab.commit(h->stream, 0));
+  return finish_rank1(h, pl, sum, grid, sums);
+}
+
+int run_rank1_two_pass(qh_state_s *h, const qh_rank1_info &pl, const Rank1Op &op, double *sums) {
+  const qh_perm_tiles &t = pl.tile;
+  const int k = (int)t.k, cb = (int)pl.chunk_bits;
+  const uint64_t items = ((uint64_t)h->amp_bytes() << h->nloc) / 16, ci = ((uint64_t)h->amp_bytes() << cb) / 16, nchunks = items / ci;
+  if (ci < 256 || ci > (uint64_t)qh::kRank1ChunkItems || items % ci)      // (the second path starts at 11 register bits)
+    return fail(QH_ERR_ARG, "apply_rank1: a shard of %llu items on the second path", (unsigned long long)items);
+  if (h->rank1.reserve(pl.scratch_bytes) != hipSuccess)
+    return fail(QH_ERR_NOMEM, "apply_rank1: no room for the %llu bytes of fibre sums that a register of %d bits on these positions needs "
+                "(the state is unchanged)", (unsigned long long)pl.scratch_bytes, k);
+  qh::perm_item *m = h->rank1.as<qh::perm_item>(), *part = pl.split > 1 ? m + pl.nfibres : m;
+  uint8_t pos[64];
+  int np = 0;
+  for (int p = 0; p < h->nloc; ++p)
+    if ((t.reg_mask >> p) & 1ull) pos[np++] = (uint8_t)p;
+  qh::Rank1DotArgs d{};
+  qh::Rank1AxpyArgs x{};
+  if (!op.uniform()) {
+    d.g.n = qh::perm_runs((int)pl.reg_in_chunk, pos, d.g.run);
+    x.g.n = qh::perm_runs(k, pos, x.g.run);
+  }
+  d.abv_mask = t.reg_mask >> cb;
+  d.grp_mask = (h->local_mask() >> cb) & ~d.abv_mask;
+  d.nunits = pl.groups * pl.split;
+  d.walk = pl.walk;
+  d.nfib = pl.nfibres;
+  d.split = pl.split;
+  d.nin = pl.reg_in_chunk;
+  d.reg_low = (uint32_t)(t.reg_mask & ((1ull << cb) - 1ull));
+  d.fpc = (uint32_t)pl.fibres_per_chunk;
+  d.cb = x.cb = (uint32_t)cb;
+  d.vr = op.vr;
+  x.free_mask = h->local_mask() & ~t.reg_mask;
+  x.reg_mask = t.reg_mask;
+  x.ctl = t.ctl_in | t.ctl_out;
+  x.nchunks = nchunks;
+  x.ar = op.a[0]; x.ai = op.a[1];
+  x.ubr = op.ub[0]; x.ubi = op.ub[1];
+  const unsigned grid2 = (unsigned)std::min<uint64_t>(nchunks, 1ull << 20);
+  SlabSum sum{h};
+  if (sums) HIP_TRY(sum.reserve(std::max<uint64_t>(grid2, 8), 2, 2));
+  int rc = QH_OK;
+  const void *dtab = nullptr;
+  if (!op.uniform() && (rc = stage_perm_table(h, op.tab.data(), op.tab.size() * sizeof(double), &dtab))) return rc;
+  const qh::perm_item *dvc = (const qh::perm_item *)dtab, *dub = dvc ? dvc + ((size_t)1 << k) : nullptr;
+  const size_t lds = (size_t)16 << cb;      // one complex double per amplitude of a chunk
+  with_real(h, [&](auto r) {
+    using R = decltype(r);
+    using A = typename qh::AmpT<R>::type;
+    const dim3 g1((unsigned)std::min<uint64_t>(d.nunits, 1ull << 20));
+    if (op.uniform()) hipLaunchKernelGGL((qh::k_rank1_dot<R, true>), g1, dim3(256), lds, h->stream, (const A *)h->d_psi, dvc, d, part);
+    else hipLaunchKernelGGL((qh::k_rank1_dot<R, false>), g1, dim3(256), lds, h->stream, (const A *)h->d_psi, dvc, d, part);
+    if (pl.split > 1)
+      hipLaunchKernelGGL(qh::k_rank1_fold, dim3(grid_for(pl.nfibres, 1ull << 16)), dim3(256), 0, h->stream, (const qh::perm_item *)part, m,
+                         pl.nfibres, pl.split);
+    double *slab = sums ? sum.slab : nullptr;
+    if (op.uniform()) hipLaunchKernelGGL((qh::k_rank1_axpy<R, true>), dim3(grid2), dim3(256), 0, h->stream, (A *)h->d_psi, dub, (const qh::perm_item *)m, x, slab);
+    else hipLaunchKernelGGL((qh::k_rank1_axpy<R, false>), dim3(grid2), dim3(256), 0, h->stream, (A *)h->d_psi, dub, (const qh::perm_item *)m, x, slab);
+  });
+  if ((rc = check_launch(h))) return rc;
+  if (!op.uniform()) HIP_TRY(h->tab.commit(h->stream, 0));
+  return finish_rank1(h, pl, sum, grid2, sums);
+}
+
+}  // namespace
+
+extern "C" {
+
+int qh_rank1_plan(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, int uniform, qh_rank1_info *out) {
+  if (!h || !bits || !out) return fail(QH_ERR_ARG, "rank1_plan: null handle, bits or out");
+  return plan_rank1_call(h, "rank1_plan", k, bits, ctl_mask, uniform, out);
+}
+
+int qh_apply_rank1(qh_handle h, int k, const int32_t *bits, uint64_t ctl_mask, const double *u, const double *v, const double a[2],
+                   const double b[2], double *sums) {
+  if (!h || !bits || !a || !b) return fail(QH_ERR_ARG, "apply_rank1: null handle, bits, a or b");
+  if (u && !v) return fail(QH_ERR_ARG, "apply_rank1: u without v (v == NULL is the uniform form and takes no u)");
+  const int uniform = v ? 0 : 1;
+  qh_rank1_info pl;
+  int rc = plan_rank1_call(h, "apply_rank1", k, bits, ctl_mask, uniform, &pl);
+  if (rc) return rc;
+  for (int i = 0; i < 2; ++i) {
+    if (!std::isfinite(a[i])) return fail(QH_ERR_ARG, "apply_rank1: a[%d] = %g is not finite", i, a[i]);
+    if (!std::isfinite(b[i])) return fail(QH_ERR_ARG, "apply_rank1: b[%d] = %g is not finite", i, b[i]);
+  }
+  if (v) {
+    int64_t bad = u ? qh::rank1_first_nonfinite(u, 2ull << k) : -1;
+    if (bad >= 0) return fail(QH_ERR_ARG, "apply_rank1: u[%lld] = %g (%s part) is not finite", (long long)(bad / 2), u[bad], bad % 2 ? "imaginary" : "real");
+    if ((bad = qh::rank1_first_nonfinite(v, 2ull << k)) >= 0)
+      return fail(QH_ERR_ARG, "apply_rank1: v[%lld] = %g (%s part) is not finite", (long long)(bad / 2), v[bad], bad % 2 ? "imaginary" : "real");
+  }
+  if ((rc = enter(h))) return rc;          // a barrier: what is queued runs first, on whatever layout it leaves
+  if ((rc = plan_rank1_call(h, "apply_rank1", k, bits, ctl_mask, uniform, &pl))) return rc;
+  if (!pl.tile.ctl_met) {                  // a shard-bit control that is 0 on this shard (met: dropped)
+    h->stats.gates_submitted++;
+    h->stats.gates_noop++;
+    if (sums) sums[0] = sums[1] = 0.0;
+    return QH_OK;
+  }
+  Rank1Op op;
+  op.a[0] = a[0]; op.a[1] = a[1];
+  op.vr = std::sqrt(std::ldexp(1.0, -k));
+  op.ub[0] = b[0] * op.vr; op.ub[1] = b[1] * op.vr;
+  if (v) {
+    std::vector<double> vc, ub;
+    qh::rank1_tables(k, pl.tile.reg_pos, u, v, b, &vc, &ub);
+    op.tab = std::move(vc);
+    op.tab.insert(op.tab.end(), ub.begin(), ub.end());
+  }
+  return pl.path == QH_RANK1_TILE ? run_rank1_tile(h, pl, op, sums) : run_rank1_two_pass(h, pl, op, sums);
 }
 
 }  // extern "C"

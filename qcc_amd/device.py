@@ -248,6 +248,41 @@ class DeviceState:
     native.check(self.lib.qh_perm_plan(self.h, len(b), b.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(ctl_mask), ctypes.byref(t)))
     return t.as_dict()
 
+  def apply_rank1(self, bits, u=None, v=None, a=-1.0, b=2.0, ctl_mask=0, sums=False):
+    """a I + b |u><v| on the register of LOGICAL bits `bits` (bits[0] the least significant bit of the table index) where every
+    bit of ctl_mask is 1 (qh_apply_rank1).  u, v: 2^k complex numbers, k <= 16; u=None means u = v; v=None (then u must be None)
+    is the uniform vector 2^(-k/2), any k up to the local bits.  The defaults a = -1, b = 2 are the reflection 2|v><v| - I.
+    sums=True returns (sum |psi'|^2 over the amplitudes whose controls are met, sum |<v|psi_r>|^2 over those fibres)."""
+    bb = np.ascontiguousarray([int(x) for x in bits], dtype=np.int32)
+    k = len(bb)
+    if v is None and u is not None:
+      raise ValueError('apply_rank1: u without v (v=None is the uniform form)')
+
+    def table(t, name):
+      if t is None:
+        return None
+      t = np.ascontiguousarray(t, dtype=np.complex128)
+      if t.shape != (1 << k,):
+        raise ValueError(f'apply_rank1: {name} of shape {t.shape} for {k} bits (want ({1 << k},))')
+      return t
+    tu, tv = table(u, 'u'), table(v, 'v')
+    ab = np.array([complex(a), complex(b)], dtype=np.complex128)
+    out = np.zeros(2, dtype=np.float64)
+    native.check(self.lib.qh_apply_rank1(self.h, k, bb.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(ctl_mask),
+                                         tu.ctypes.data_as(_dp) if tu is not None else None,
+                                         tv.ctypes.data_as(_dp) if tv is not None else None,
+                                         ab[0:1].ctypes.data_as(_dp), ab[1:2].ctypes.data_as(_dp),
+                                         out.ctypes.data_as(_dp) if sums else None))
+    return (float(out[0]), float(out[1])) if sums else None
+
+  def rank1_plan(self, bits, ctl_mask=0, uniform=False):
+    """How apply_rank1 on these bits would run right now (qh_rank1_plan), as a dict."""
+    b = np.ascontiguousarray([int(x) for x in bits], dtype=np.int32)
+    t = native.QhRank1Info()
+    native.check(self.lib.qh_rank1_plan(self.h, len(b), b.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(ctl_mask),
+                                        1 if uniform else 0, ctypes.byref(t)))
+    return t.as_dict()
+
   def apply_bits_raw(self, ctl_mask, tgt_bit, addr):
     """apply_bits with the gate given as the address of 8 contiguous doubles."""
     rc = self.lib.qh_apply_bits(self.h, ctl_mask, tgt_bit, ctypes.cast(addr, _dp))

@@ -781,6 +781,85 @@ class qc:
         a, b = s >> len(dst), s & ((1 << len(dst)) - 1)
         self.permutation((a << len(dst)) | ((a + b) & ((1 << len(dst)) - 1)), src + dst)
 
+    # rank-one register updates (the standing of permutation: eager, one call each): a I + b |u><v| on a register, identity on
+    # the rest -- reflections, Householder steps, projections onto a register state -- without ever forming a matrix
+    def _rank1(self, who, qubits, u, v, a, b, ctl, sums=False):
+        qubits, ctl = [int(q) for q in qubits], [int(c) for c in ctl]
+        k = len(qubits)
+        if v is None:                    # the uniform form: any number of qubits
+            every = qubits + ctl
+            if k < 1:
+                raise ValueError(f'{who}: no register qubits')
+            if any(q < 0 or q >= self._nbits for q in every):
+                raise ValueError(f'{who}: qubits {every} out of range for {self._nbits} qubits')
+            if len(set(every)) != len(every):
+                raise ValueError(f'{who}: a qubit appears twice in {every}')
+            dev = self._ensure_device()
+            if not hasattr(dev, 'apply_rank1'):
+                raise NotImplementedError(f'{who}: {type(dev).__name__} has no apply_rank1')
+            bits = [self._nbits - 1 - q for q in reversed(qubits)]
+        else:
+            if k < 1:
+                raise ValueError(f'{who}: no register qubits')
+            dev, bits = self._table_device(who, 'apply_rank1', qubits, np.shape(v)[0], ctl=ctl)
+        mask = 0
+        for c in ctl:
+            mask |= 1 << (self._nbits - 1 - c)
+        out = dev.apply_rank1(bits, u=u, v=v, a=a, b=b, ctl_mask=mask, sums=sums)
+        self._gate_done()
+        return out
+
+    @staticmethod
+    def _rank1_vector(who, name, vec, k):
+        t = np.asarray(vec, dtype=np.complex128)
+        if t.shape != (1 << k,):
+            raise ValueError(f'{who}: {name} of shape {t.shape} for {k} qubits (want ({1 << k},))')
+        if not np.all(np.isfinite(t.real) & np.isfinite(t.imag)):
+            raise ValueError(f'{who}: {name} has a non-finite entry')
+        return t
+
+    def rank_one(self, qubits, u, v=None, a=0.0, b=1.0, ctl=()):
+        """a I + b |u><v| on the register `qubits` (qubits[0] the most significant bit of the vectors' index, as in diagonal)
+        where every qubit of `ctl` is 1.  v=None means v = u.  Any complex a, b and any vectors: nothing is normalised."""
+        qubits = list(qubits)
+        tu = self._rank1_vector('rank_one', 'u', u, len(qubits))
+        tv = tu if v is None else self._rank1_vector('rank_one', 'v', v, len(qubits))
+        self._rank1('rank_one', qubits, None if v is None else tu, tv, complex(a), complex(b), ctl)
+
+    def reflect(self, qubits, state=None, ctl=()):
+        """The reflection 2|phi><phi| - I about a register state phi (normalised here; state=None: the uniform state) on the
+        register `qubits`, where every qubit of `ctl` is 1."""
+        qubits = list(qubits)
+        if state is None:
+            self._rank1('reflect', qubits, None, None, -1.0, 2.0, ctl)
+            return
+        phi = self._rank1_vector('reflect', 'state', state, len(qubits))
+        nrm = float(np.linalg.norm(phi))
+        if not nrm > 0:
+            raise ValueError('reflect: the state is the zero vector')
+        self._rank1('reflect', qubits, None, phi / nrm, -1.0, 2.0, ctl)
+
+    def diffusion(self, reg):
+        """Grover's inversion about the mean on the register `reg`: reflect(reg), i.e. H^k (2|0><0| - I) H^k."""
+        self.reflect(reg)
+
+    def project_onto(self, qubits, state=None, *, normalize=True):
+        """The projector |phi><phi| (x) I for a register state phi (normalised here; state=None: the uniform state): post-
+        selection of the register onto phi.  Returns the probability of finding it there (for a normalised state);
+        normalize=True then rescales to norm 1 and raises ValueError where the probability is 0."""
+        qubits = list(qubits)
+        phi = None
+        if state is not None:
+            phi = self._rank1_vector('project_onto', 'state', state, len(qubits))
+            nrm = float(np.linalg.norm(phi))
+            if not nrm > 0:
+                raise ValueError('project_onto: the state is the zero vector')
+            phi = phi / nrm
+        norm2, _overlap = self._rank1('project_onto', qubits, None, phi, 0.0, 1.0, (), sums=True)
+        if normalize:
+            self._rescale(norm2, 'project_onto')
+        return float(norm2)
+
     # ------------------------------------------------------------------ readers / measurement
     def maxprob(self):
         """(bits, probability) of the likeliest basis state, reduced on the device."""

@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB_PATH = os.environ.get('QCC_HIP_LIB') or os.path.join(PKG, 'libqcc_hip.so')  # env: A/B builds only
 SOURCES = [os.path.join(PKG, 'csrc', f) for f in
-           ('engine.hip', 'buffers.hip.h', 'kernels_common.hip.h', 'kernels_gate.hip.h', 'kernels_argmax.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_perm.hip.h', 'perm_plan.h', 'kernels_measure.hip.h', 'kernels_select.hip.h', 'select_plan.h', 'kernels_expect.hip.h', 'kernels_density.hip.h', 'density_plan.h', 'kernels_pauli.hip.h', 'pauli_plan.h', 'kernels_pauli_product.hip.h', 'pauli_product_plan.h', 'kernels_zpoly.hip.h', 'zpoly_plan.h', 'kernels_two_state.hip.h', 'kernels_inner.hip.h', 'kernels_axpby.hip.h', 'inner_plan.h', 'kernels_transition.hip.h', 'transition_plan.h', 'kernels_resize.hip.h', 'resize_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h', 'exchange_plan.h',
+           ('engine.hip', 'buffers.hip.h', 'kernels_common.hip.h', 'kernels_gate.hip.h', 'kernels_argmax.hip.h', 'kernels_dense.hip.h', 'kernels_mux.hip.h', 'kernels_perm.hip.h', 'perm_plan.h', 'kernels_rank1.hip.h', 'rank1_plan.h', 'kernels_measure.hip.h', 'kernels_select.hip.h', 'select_plan.h', 'kernels_expect.hip.h', 'kernels_density.hip.h', 'density_plan.h', 'kernels_pauli.hip.h', 'pauli_plan.h', 'kernels_pauli_product.hip.h', 'pauli_product_plan.h', 'kernels_zpoly.hip.h', 'zpoly_plan.h', 'kernels_two_state.hip.h', 'kernels_inner.hip.h', 'kernels_axpby.hip.h', 'inner_plan.h', 'kernels_transition.hip.h', 'transition_plan.h', 'kernels_resize.hip.h', 'resize_plan.h', 'kernels_sweep.hip.h', 'planner.h', 'exchange.hip.h', 'exchange_plan.h',
             'sweep_island_rb2.inc', 'sweep_island_rb3.inc', 'sweep_island_rb4.inc',
             'sweep_island_rb5.inc', 'sweep_island_f32_rb2.inc', 'sweep_island_f32_rb3.inc',
             'sweep_island_f32_rb4.inc', 'sweep_island_f32_rb5.inc', 'sweep_island_f32_rb6.inc', 'sweep_handlers.inc',
@@ -80,6 +80,23 @@ class QhPermTiles(ctypes.Structure):
 
   def as_dict(self):
     return {k: (int(getattr(self, k)) if isinstance(getattr(self, k), int) else list(getattr(self, k))) for k, _ in self._fields_}
+
+
+QH_RANK1_MAX_BITS = 16
+QH_RANK1_TILE, QH_RANK1_TWO_PASS = 0, 1
+
+
+class QhRank1Info(ctypes.Structure):
+  """include/qcc_hip.h qh_rank1_info: how qh_apply_rank1 would run."""
+  _u32 = ctypes.c_uint32
+  _fields_ = [('path', _u32), ('uniform', _u32), ('tile', QhPermTiles), ('scratch_bytes', _u64), ('bytes_swept', _u64),
+              ('nfibres', _u64), ('groups', _u64), ('fibres_per_chunk', _u64), ('walk', _u64), ('kernels', _u32),
+              ('chunk_bits', _u32), ('reg_in_chunk', _u32), ('reg_above', _u32), ('split', _u32), ('pad', _u32)]
+
+  def as_dict(self):
+    d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k not in ('tile', 'pad')}
+    d['tile'] = self.tile.as_dict()
+    return d
 
 
 QH_SELECT_MAX, QH_TOPK_MAX = 1 << 20, 4096
@@ -176,6 +193,8 @@ SIGNATURES = {
     'qh_apply_diag': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _dp]),
     'qh_apply_perm': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _u64, ctypes.POINTER(ctypes.c_uint32)]),
     'qh_perm_plan': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _u64, ctypes.POINTER(QhPermTiles)]),
+    'qh_apply_rank1': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _u64, _dp, _dp, _dp, _dp, _dp]),
+    'qh_rank1_plan': (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), _u64, _i32, ctypes.POINTER(QhRank1Info)]),
     'qh_set_fusion': (_i32, [_vp, _i32]),
     'qh_set_relayout': (_i32, [_vp, _i32, ctypes.POINTER(_i32)]),
     'qh_apply_stream': (_i32, [_vp, _u64, ctypes.POINTER(ctypes.c_int32), _dp]),
